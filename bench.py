@@ -3,7 +3,7 @@
 posterior pass of the 15-state gene model on b = 1024 sequences of L = 100 000 per GPU
 (BASELINE.json configs[2]), inputs resident in HBM, one process per GPU.
 
-    python bench.py [--gpus N --steps K --warmup W --scaling weak|strong]
+    python bench.py [--gpus N --steps K --warmup W --scaling weak|strong --full --dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself:
@@ -17,9 +17,11 @@ independent, so ranks own disjoint batches and nothing else is exchanged.  --sca
 every rank owns --batch sequences; --scaling strong: the --batch sequences are split over the ranks
 (1024 / 8 = 128 per GPU).
 
-Rank 0 prints one JSON line with the contract's fields plus
+A plain run sets up, warms up, times the --steps steps, writes the outputs if --dump-outputs is given,
+and prints the line.  Rank 0 prints one JSON line with the contract's fields plus
   roofline      the dominant kernel's algorithmic-bytes rate from HIP events recorded on the
                 launch stream inside the timed region (all kernels are listed under "kernels")
+With --full, after the timed region, also (each can be left out with its --no-* option)
   cpu_baseline  the oracle's PyTorch-CPU port of the reference path timed on this host
   accuracy      (N = 1, outside the timed region; the oracle is the checker here, nothing measured)
                 BASELINE.md section 3's gates on sampled sequences of the timed batch: max |gamma - gamma64|,
@@ -31,6 +33,12 @@ Rank 0 prints one JSON line with the contract's fields plus
                 `pipeline_input`: the posterior pass on EMITTER-GENERATED emissions (class probabilities +
                 one-hot nucleotides -> hmm_gene_emissions -> hmm_posterior, SURVEY.md 8(d)'s parity recipe) with
                 the number of sequences the device routed to the serial recomputation and their accuracy
+
+--dump-outputs DIR writes what the last timed step returned, as DIR/<name>.npy: gamma_sample (float32 posteriors
+of a fixed, seeded sample of the rank's sequences, whole sequences unless one alone exceeds the 48 MB share) with
+its indices in gamma_sample_sequences (and gamma_sample_positions when positions are sampled too), loglik (float64
+per-sequence log-likelihoods) and loglik_partials (float64 (sum ll, count), all-reduced when N > 1).  The inputs
+are seeded, so two builds given the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -67,13 +75,20 @@ def parse():
     ap.add_argument("--states", type=int, default=15)
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak: --batch sequences per GPU; strong: --batch sequences split over the GPUs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-variants", action="store_true")
-    ap.add_argument("--no-accuracy", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure accuracy, the variants and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: leave out the variants")
+    ap.add_argument("--no-accuracy", action="store_true", help="with --full: leave out the accuracy gates")
     ap.add_argument("--cpu-len", type=int, default=20000, help="sequence length of the CPU baseline sample")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic_latest.json"),
                     help="per-kernel HBM bytes per launch from a separate rocprofv3 --pmc pass")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (at most 64 MB)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def spawn_ranks(args):
@@ -412,6 +427,35 @@ def largeq_variant(engine, timed, q=1027, b=1024, L=64):
             "posterior_mfma_f32_frac": tp / MFMA_F32_PEAK_TFLOPS}
 
 
+DUMP_GAMMA_BYTES = 48 << 20      # the posterior sample's share of --dump-outputs' 64 MB
+DUMP_LOGLIK_BYTES = 8 << 20
+
+
+def dump_outputs(d, out, ll, part):
+    """--dump-outputs: the last timed step's results as float32 / float64 .npy files in `d`.  The posteriors
+    (1,b,L,q) are too large to keep whole: a fixed, seeded sample of sequences (and of positions when one
+    sequence alone exceeds the share), with the sampled indices beside it."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    _, b, L, q = out.shape
+    rng = np.random.default_rng(0)
+    nseq = max(1, min(b, DUMP_GAMMA_BYTES // (L * q * 4 + 8)))
+    seqs = np.sort(rng.choice(b, nseq, replace=False))
+    gam = out[0, torch.as_tensor(seqs, device=out.device)]
+    files = {"gamma_sample_sequences": seqs.astype(np.float64)}
+    if L * q * 4 > DUMP_GAMMA_BYTES:
+        pos = np.sort(rng.choice(L, DUMP_GAMMA_BYTES // (q * 4 + 8), replace=False))
+        gam = gam[:, torch.as_tensor(pos, device=out.device)]
+        files["gamma_sample_positions"] = pos.astype(np.float64)
+    files["gamma_sample"] = gam.cpu().numpy()
+    if ll.numel() * 8 > DUMP_LOGLIK_BYTES:
+        ll = ll[:, torch.as_tensor(seqs, device=ll.device)]
+    files["loglik"] = ll.cpu().numpy().astype(np.float64)
+    files["loglik_partials"] = part.cpu().numpy().astype(np.float64)
+    for name, a in files.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def main():
     args = parse()
     rank = int(os.environ.get("RANK", "0"))
@@ -450,7 +494,7 @@ def main():
         part = engine.loglik_partials(ll)                     # (1,2): sum ll, count
         if dist is not None:
             dist.all_reduce(part)                             # RCCL over xGMI, 16 bytes
-        return part
+        return ll, part
 
     for _ in range(args.warmup):
         step()
@@ -460,7 +504,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        part = step(prof)
+        ll, part = step(prof)
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
@@ -477,6 +521,8 @@ def main():
     if dist is not None:
         world = dist.get_world_size()                # what RCCL actually runs on
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, ll, part)
     if rank == 0:
         cells_rank = float(b) * L * q
         cells_all = nseq_all * L * q
@@ -525,15 +571,15 @@ def main():
                        "mean_loglik": mean_ll},
             "roofline": roofline,
         }
-        # everything below runs after the timed region, on rank 0 (its own shard of the batch); the other
-        # ranks wait at the barrier that follows
-        if not args.no_accuracy:
+        # with --full, everything below runs after the timed region, on rank 0 (its own shard of the batch); the
+        # other ranks wait at the barrier that follows
+        if args.full and not args.no_accuracy:
             _, ll = engine.posterior(A, pi, E, out=out)
             line["accuracy"] = accuracy(engine, A, pi, E, out, ll)
-        if not args.no_variants and world == 1:
+        if args.full and not args.no_variants and world == 1:
             del out
             line["variants"] = variants(engine, A, pi, E)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.cpu_len, b, q)
         print(json.dumps(line), flush=True)
     if dist is not None:

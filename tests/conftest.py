@@ -1,8 +1,15 @@
 import os
 import sys
 
-import numpy as np
-import pytest
+# The bit-exact fixtures under tests/golden/ are recorded with MKL's COMPATIBLE code path, ATen's AVX2
+# kernels and one thread (tests/golden/make_golden.py).  Left to themselves MKL and ATen pick their kernels
+# by CPU and split the work by thread count, and the CPU oracle's matmuls and elementwise ops then round
+# differently on another machine.  Set before torch first dispatches a CPU op.
+os.environ["MKL_CBWR"] = "COMPATIBLE"
+os.environ["ATEN_CPU_CAPABILITY"] = "avx2"
+
+import numpy as np  # noqa: E402
+import pytest  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
@@ -20,6 +27,11 @@ def load_golden(name):
         return {k: z[k] for k in z.files}
 
 
-@pytest.fixture(scope="session")
+@pytest.fixture
 def golden():
-    return load_golden
+    """load_golden, with torch's CPU ops on one thread for the test (as the fixtures were recorded)."""
+    import torch
+    n = torch.get_num_threads()
+    torch.set_num_threads(1)
+    yield load_golden
+    torch.set_num_threads(n)

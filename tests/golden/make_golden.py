@@ -18,8 +18,15 @@ import re
 import sys
 import types
 
-import numpy as np
-import torch
+# MKL's COMPATIBLE code path and ATen's AVX2 kernels on one thread round alike on every x86-64 CPU with
+# AVX2 (tests/conftest.py and its golden fixture set the same)
+os.environ["MKL_CBWR"] = "COMPATIBLE"
+os.environ["ATEN_CPU_CAPABILITY"] = "avx2"
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+torch.set_num_threads(1)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REF = "/root/reference"

@@ -8,8 +8,13 @@ Same harness as make_golden.py (build container only; writes tests/golden/grad_*
 import os
 import sys
 
-import numpy as np
-import torch
+os.environ["MKL_CBWR"] = "COMPATIBLE"          # as make_golden.py and tests/conftest.py
+os.environ["ATEN_CPU_CAPABILITY"] = "avx2"
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+torch.set_num_threads(1)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)

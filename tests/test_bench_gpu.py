@@ -27,7 +27,7 @@ def run_bench(*args):
 
 
 def test_single_gpu_line_small_shape():
-    line = run_bench("--steps", "2", "--warmup", "1", "--batch", "16", "--len", "3000", "--no-variants",
+    line = run_bench("--steps", "2", "--warmup", "1", "--batch", "16", "--len", "3000", "--full", "--no-variants",
                      "--cpu-len", "200")
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "accuracy"):
@@ -43,11 +43,47 @@ def test_single_gpu_line_small_shape():
     assert line["cpu_baseline"]["kind"] == "port" and line["cpu_baseline"]["cores"] >= 1
 
 
+def test_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """Without --full the line has the headline and the in-run roofline only; --dump-outputs writes the last timed
+    step's results, and two runs with the same shape (other step counts) see the same inputs."""
+    import numpy as np
+    dumps = []
+    for steps in (3, 1):
+        d = tmp_path / ("s%d" % steps)
+        line = run_bench("--steps", str(steps), "--warmup", "1", "--batch", "16", "--len", "100000",
+                         "--dump-outputs", str(d))
+        for key in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "dtype", "roofline"):
+            assert key in line, key
+        for key in ("accuracy", "variants", "cpu_baseline"):
+            assert key not in line, key
+        assert line["steps"] == steps
+        assert abs(line["value"] - 16 * 100000 * 15 / (line["ms_per_step"] * 1e-3)) <= 1e-6 * line["value"]
+        names = sorted(f[:-4] for f in os.listdir(d))
+        assert names == ["gamma_sample", "gamma_sample_sequences", "loglik", "loglik_partials"]
+        assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64 << 20
+        arr = {n: np.load(d / (n + ".npy")) for n in names}
+        assert all(a.dtype in (np.float32, np.float64) for a in arr.values())
+        seqs = arr["gamma_sample_sequences"]
+        assert len(seqs) == 8 and np.all(np.diff(seqs) > 0) and 0 <= seqs[0] and seqs[-1] < 16
+        g = arr["gamma_sample"]
+        assert g.shape == (8, 100000, 15) and g.dtype == np.float32
+        assert np.abs(g.sum(-1) - 1).max() <= 1e-4
+        ll, part = arr["loglik"], arr["loglik_partials"]
+        assert ll.shape == (1, 16) and part.shape == (1, 2) and part[0, 1] == 16
+        assert abs(part[0, 0] - ll.sum()) <= 1e-9 * abs(part[0, 0])
+        assert abs(line["config"]["mean_loglik"] - part[0, 0] / part[0, 1]) <= 1e-9 * abs(part[0, 0])
+        dumps.append(arr)
+    a, b = dumps
+    assert np.array_equal(a["gamma_sample_sequences"], b["gamma_sample_sequences"])
+    assert np.allclose(a["loglik"], b["loglik"], rtol=1e-9, atol=0)
+    assert np.abs(a["gamma_sample"] - b["gamma_sample"]).max() <= 1e-6
+
+
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs (the driver's scaling run has them)")
 @pytest.mark.parametrize("scaling", ["weak", "strong"])
 def test_two_ranks_self_spawned(scaling):
     line = run_bench("--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "16", "--len", "3000",
-                     "--scaling", scaling, "--cpu-len", "200")
+                     "--scaling", scaling, "--full", "--cpu-len", "200")
     assert line["n_gpus"] == 2 and line["scaling"] == scaling
     # an N > 1 line stands alone as a record: every object the N = 1 line has, except the N = 1 extras
     for key in ("roofline", "cpu_baseline", "accuracy"):

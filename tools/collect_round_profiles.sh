@@ -17,8 +17,8 @@ stats() {   # stats <name> <program args...>: rocprofv3 --kernel-trace --stats o
   f=$(find "$OUT/prof_$name" -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && cp "$f" "$OUT/${TAG}_${name}_kernel_stats.csv"
 }
-timeout -k 10 900 python3 "$R/bench.py" > "$OUT/${TAG}_bench.json" 2> "$OUT/bench.err" && echo "bench ok" &&
-stats bench "$R/bench.py" --steps 5 --warmup 2 --no-cpu-baseline --no-variants && echo "bench stats ok" &&
+timeout -k 10 900 python3 "$R/bench.py" --full > "$OUT/${TAG}_bench.json" 2> "$OUT/bench.err" && echo "bench ok" &&
+stats bench "$R/bench.py" --steps 5 --warmup 2 --full --no-cpu-baseline --no-variants && echo "bench stats ok" &&
 grep '^{' "$OUT/bench.log" | tail -1 > "$OUT/${TAG}_bench_under_rocprof.json" &&
 bash "$R/tools/collect_traffic.sh" "$TAG" && cp "$R/gpurun_out/traffic_$TAG.json" "$OUT/${TAG}_traffic.json" && echo "traffic ok" &&
 stats viterbi "$R/tools/experiments/vit_prof.py" && echo "viterbi stats ok" &&
