@@ -740,9 +740,9 @@ __device__ __forceinline__ void reduce_sparse_wave(const float *__restrict__ A, 
             else x[j] = y[j] * e[j];
         }
         if (SUM) {
-            // (32-lane rows — the 29-state model, whose one-directional entry points have no certificate of their own:
-            // a column that loses more than 2^-45 between two sums has met an observation that everything survives at
-            // the emission floor only; such sequences go to the serial kernels, k32_select)
+            // (32-lane rows — the 29-state model: a column that loses more than 2^-45 between two sums has met an
+            // observation that everything survives at the emission floor only; such sequences go to the serial kernels,
+            // k32_select, on top of the certificates of the 32-state apply kernels)
             if (W >= 32) {                      // ... EVERY column of the chain, whatever the start state
                 const unsigned long long keep = __builtin_amdgcn_ballot_w64(kc < Q && !(s < cs * 0x1p-45f));
                 const unsigned long long mine = W == 64 ? ~0ull : (((1ull << (W & 63)) - 1ull) << (W * cl));

@@ -14,7 +14,8 @@
 //
 // Which models take this path is decided on the device (k32_check): the support of A must lie inside the
 // compiled topology and be primitive (see k_topo_check); everything else — other 17..32-state
-// models, and sequences whose floor-transition certificate fires (see k_backward) — is served by the
+// models, and sequences whose certificate (psi, or the one-directional CERT / CERT3 sums) fires or that a reduce
+// marked (k32_select) — is served by the
 // one-wave-per-sequence kernels of hmm_midq.inc, which implement the cell's serial semantics exactly and
 // take a per-sequence mask.  hmm_posterior (all modes), hmm_forward and hmm_backward use this path; the
 // gradients run per chunk of this plan for up to 512 sequences (hmm_postgrad_chunked.inc), otherwise — and Viterbi
@@ -29,7 +30,8 @@
 struct Plan32 {
     Plan p;                           // shape and chunking (k, b, L, q, NB, T, C, nchains; nsub = T / SUB32)
     long long nwaves;                 // apply waves: 16 (sequence, chunk) pairs each, never straddling models
-    size_t o_ops, o_exps, o_prefix, o_llpre, o_suffix, o_lsuf, o_loglik, o_ckpt, o_phi, o_need, o_elig, o_nex, o_ll2, total;
+    size_t o_ops, o_exps, o_prefix, o_llpre, o_suffix, o_lsuf, o_loglik, o_ckpt, o_phi, o_need, o_elig, o_nex, o_ll2;
+    size_t o_risk, o_upi, total;      // the dense reduce's per-chain mark; hmm_backward's uniform start distribution
 };
 
 static int make_plan32(int op, int k, int b, int L, int q, Plan32 *pp, int T_fixed = 0) {
@@ -56,6 +58,8 @@ static int make_plan32(int op, int k, int b, int L, int q, Plan32 *pp, int T_fix
     pp->o_need = off;   off = align_up(off + (size_t)p.NB * sizeof(int));
     pp->o_elig = off;   off = align_up(off + (size_t)k * sizeof(int));
     pp->o_nex = off;    off = align_up(off + sizeof(int));
+    pp->o_risk = off;   off = align_up(off + (size_t)p.nchains * sizeof(int));
+    pp->o_upi = off;    off = align_up(off + (size_t)k * q * sizeof(float));
     pp->o_ckpt = off;
     if (op == HMM_OP_POSTERIOR)
         off = align_up(off + (size_t)pp->nwaves * p.nsub * 16 * Q32 * sizeof(float));
@@ -68,6 +72,7 @@ static int make_plan32(int op, int k, int b, int L, int q, Plan32 *pp, int T_fix
 // with the dense MFMA reduce (any other primitive model of 17..32 states: a learned dense A, other topologies).
 // One wave per model.
 #define ID_DENSE32 4
+#define ID_DENSE64 5                  // (hmm_scan64.inc's k64_check; k32_select serves both plans)
 __global__ __launch_bounds__(64) void k32_check(const float *__restrict__ A, int *__restrict__ elig, int q,
                                                 int exact_mode, float eps, int *__restrict__ nex,
                                                 int opt_force_dense32 = 0) {
@@ -372,13 +377,30 @@ __device__ __forceinline__ void flush32(const Out32 &o, int lane, int row0, int 
     __builtin_amdgcn_wave_barrier();
 }
 
-// LOGA = false: alpha_hat entering every SUB32-step block -> ckpt ([wave][block][chain][32]), nothing else;
+// max(d, eps)'s clamp-born part, component-wise: where the clamp was active the whole eps is born there, elsewhere the
+// carried clamp-born part df (forward_body's CERT / backward_body's CERT3 in hmm_engine.hip)
+__device__ __forceinline__ f4 born4(f4 d, f4 df, float eps) {
+    f4 r = {d.x > eps ? df.x : eps, d.y > eps ? df.y : eps, d.z > eps ? df.z : eps, d.w > eps ? df.w : eps};
+    return r;
+}
+__device__ __forceinline__ float dot32(const X32 &a, const X32 &b) {
+    return col_sum(hsum(a.t[0] * b.t[0]) + hsum(a.t[1] * b.t[1]));
+}
+
+// LOGA = false, CERT = false: alpha_hat entering every SUB32-step block -> ckpt ([wave][block][chain][32]), nothing else;
 // LOGA = true: log alpha_t = log alpha_hat_t + sum_{s<=t} log c_s -> out (hmm_forward with log alpha)
-template <bool LOGA>
+// CERT (hmm_forward, which has no backward pass to sum psi in): forward_body's CERT in hmm_engine.hip — the part of
+//   alpha_hat born from the forward cell's clamps inside this chunk is carried along (Fv) and weighed at the chunk's
+//   last position with the chunk scan's suffix vector there -> phi[chain]; with LOGA also the clamp-born share of
+//   alpha_hat itself at the chunk's end, and what it becomes under the next observation (shnext).  CERT without LOGA
+//   (the log-likelihood alone) writes nothing but phi.
+template <bool LOGA, bool CERT = false>
 __global__ __launch_bounds__(256) void k32_forward(const float *__restrict__ A, const float *__restrict__ E,
                                                    const float *__restrict__ prefix, const double *__restrict__ llpre,
                                                    float *__restrict__ ckpt, float *__restrict__ out,
-                                                   const int *__restrict__ elig, Plan p, float eps, long long nwaves) {
+                                                   const int *__restrict__ elig, Plan p, float eps, long long nwaves,
+                                                   const float *__restrict__ suffix = nullptr, float *__restrict__ phi = nullptr) {
+    constexpr bool CKPT = !LOGA && !CERT;
     const long long wave = (long long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (wave >= nwaves) return;
     const int lane = threadIdx.x & 63, g = lane >> 4, n = lane & 15;
@@ -392,7 +414,10 @@ __global__ __launch_bounds__(256) void k32_forward(const float *__restrict__ A, 
     X32 X;
     X.t[0] = *reinterpret_cast<const f4 *>(prefix + (size_t)tl.chain * Q32 + 4 * g);
     X.t[1] = *reinterpret_cast<const f4 *>(prefix + (size_t)tl.chain * Q32 + 16 + 4 * g);
-    float *ck = LOGA ? nullptr : ckpt + (((size_t)wave * p.nsub) * 16 + n) * Q32 + 4 * g;
+    const f4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    X32 Fv, Xc = X, Fc;                                      // CERT: clamp-born part of X; both at the chain's last step
+    Fv.t[0] = Fv.t[1] = Fc.t[0] = Fc.t[1] = zero4;
+    float *ck = CKPT ? ckpt + (((size_t)wave * p.nsub) * 16 + n) * Q32 + 4 * g : nullptr;
     __shared__ __attribute__((aligned(16))) float ostage[LOGA ? 4 * OUT32_SEG : 4];
     Out32 os = {};
     if (LOGA)
@@ -404,7 +429,7 @@ __global__ __launch_bounds__(256) void k32_forward(const float *__restrict__ A, 
     X32 en[SUB32];
     ld_rows32<SUB32>(tl.rsE, voff, rowb, en);
     for (int j = 0; j < p.nsub; ++j) {
-        if (!LOGA && tl.valid && j * SUB32 < tl.len) {
+        if (CKPT && tl.valid && j * SUB32 < tl.len) {
             *reinterpret_cast<f4 *>(ck + (size_t)j * 16 * Q32) = X.t[0];
             *reinterpret_cast<f4 *>(ck + (size_t)j * 16 * Q32 + 16) = X.t[1];
         }
@@ -415,8 +440,31 @@ __global__ __launch_bounds__(256) void k32_forward(const float *__restrict__ A, 
         float lacc = 0.f;
 #pragma unroll
         for (int s = 0; s < SUB32; ++s) {
+            const bool init = tl.first && j == 0 && s == 0;
             float lS;
-            X = fwd_step32(a, X, clamp32(e[s], bd), tl.first && j == 0 && s == 0, eps, &lS);
+            if (CERT) {
+                const X32 ec = clamp32(e[s], bd);
+                const X32 d = matvec32(a.f, X), df = matvec32(a.f, Fv);
+                X32 sf, rb;
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    sf.t[t] = fmax4(sel4(init, X.t[t], d.t[t]), eps) * ec.t[t];
+                    rb.t[t] = sel4(init, Fv.t[t], born4(d.t[t], df.t[t], eps)) * ec.t[t];   // (pi's own clamp: the scan has it)
+                }
+                const float S = sum32(sf);
+                const float inv = __builtin_amdgcn_rcpf(S);
+                lS = __logf(S);
+                const bool last = j * SUB32 + s + 1 == tl.len;
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    X.t[t] = sf.t[t] * inv;
+                    Fv.t[t] = rb.t[t] * inv;
+                    Xc.t[t] = sel4(last, X.t[t], Xc.t[t]);
+                    Fc.t[t] = sel4(last, Fv.t[t], Fc.t[t]);
+                }
+            } else {
+                X = fwd_step32(a, X, clamp32(e[s], bd), init, eps, &lS);
+            }
             if (LOGA) {
                 lacc += (j * SUB32 + s < tl.len) ? lS : 0.f;
                 const float base = (float)(llb + (double)lacc);
@@ -432,16 +480,48 @@ __global__ __launch_bounds__(256) void k32_forward(const float *__restrict__ A, 
         }
         voff += SUB32 * rowb;
     }
+    if (CERT) {
+        X32 sv;
+        sv.t[0] = *reinterpret_cast<const f4 *>(suffix + (size_t)tl.chain * Q32 + 4 * g);
+        sv.t[1] = *reinterpret_cast<const f4 *>(suffix + (size_t)tl.chain * Q32 + 16 + 4 * g);
+        float c = dot32(Fc, sv) * __builtin_amdgcn_rcpf(dot32(Xc, sv));
+        if (LOGA) {
+            // the clamp-born share of alpha_hat where the chunk hands over, and what it becomes one step on under the
+            // next observation (the first row of the chunk after, whose kernel starts from the floor-free prefix vector)
+            X32 en1;
+            en1.t[0] = en1.t[1] = zero4;
+            const bool more = tl.valid && tl.chain % p.C != p.C - 1;            // (not the sequence's last chunk)
+            if (more) {
+                X32 r1[1];
+                ld_rows32<1>(tl.rsE, tl.voff + tl.len * rowb, rowb, r1);
+                en1 = clamp32(r1[0], bd);
+            }
+            X32 dx = matvec32(a.f, Xc);
+            const X32 df = matvec32(a.f, Fc);
+            dx.t[0] = fmax4(dx.t[0], eps);
+            dx.t[1] = fmax4(dx.t[1], eps);
+            const float dn = dot32(en1, dx);
+            const float shnext = (more && dn > 0.f) ? dot32(en1, df) * __builtin_amdgcn_rcpf(dn) : 0.f;
+            c = fmaxf(fmaxf(c, sum32(Fc)), shnext);
+        }
+        if (tl.valid && g == 0) phi[tl.chain] = c;
+    }
 }
 
 // posteriors.  MODE 0: gamma, 1: log gamma, 2: log gamma + loglik, 3: log beta (no forward part).
 // phi: psi, the posterior mass of clamp-born paths (backward_body in hmm_engine.hip), per chain.
-template <int MODE>
+// CERT3 (MODE 3, hmm_backward): backward_body's CERT3 — the part of R born from the reverse cell's clamps inside this
+//   chunk is carried along (Gv) and weighed at the chunk's first position with alpha_hat there, one forward step from
+//   the chunk scan's prefix vector (a uniform start); also the clamp-born share of R where the chunk hands over to the
+//   one before, and what it becomes under that chunk's last observation -> phi[chain]
+template <int MODE, bool CERT3 = false>
 __global__ __launch_bounds__(256) void k32_backward(const float *__restrict__ A, const float *__restrict__ E,
                                                     const float *__restrict__ ckpt, const float *__restrict__ suffix,
                                                     const double *__restrict__ lsuf, const double *__restrict__ loglik,
                                                     float *__restrict__ out, float *__restrict__ phi,
-                                                    const int *__restrict__ elig, Plan p, float eps, long long nwaves) {
+                                                    const int *__restrict__ elig, Plan p, float eps, long long nwaves,
+                                                    const float *__restrict__ prefix = nullptr) {
+    static_assert(!CERT3 || MODE == 3, "CERT3 is the log beta certificate");
     const long long wave = (long long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (wave >= nwaves) return;
     const int lane = threadIdx.x & 63, g = lane >> 4, n = lane & 15;
@@ -465,6 +545,8 @@ __global__ __launch_bounds__(256) void k32_backward(const float *__restrict__ A,
     const float *ck = MODE == 3 ? nullptr : ckpt + (((size_t)wave * p.nsub) * 16 + n) * Q32 + 4 * g;
     float phiacc = 0.f;
     const f4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    X32 Gv, Rc = Rv, Gc, ec0;                                // CERT3: clamp-born part of R; R, Gv, E at the first position
+    Gv.t[0] = Gv.t[1] = Gc.t[0] = Gc.t[1] = ec0.t[0] = ec0.t[1] = zero4;
 
     X32 en[SUB32];
     ld_rows32<SUB32>(tl.rsE, tl.voff + (p.nsub - 1) * SUB32 * rowb, rowb, en);
@@ -533,6 +615,7 @@ __global__ __launch_bounds__(256) void k32_backward(const float *__restrict__ A,
                 }
             }
             stage32(os, n, g, srow + s, gm);
+            if (CERT3 && s == 0) { Rc = Rv; Gc = Gv; ec0 = e[0]; }      // (the last block executed is the chunk's first)
             X32 sf;
             sf.t[0] = MODE == 3 ? e[s].t[0] * Rv.t[0] : mul_abs4(Rv.t[0], e[s].t[0]);
             sf.t[1] = MODE == 3 ? e[s].t[1] * Rv.t[1] : mul_abs4(Rv.t[1], e[s].t[1]);
@@ -542,6 +625,14 @@ __global__ __launch_bounds__(256) void k32_backward(const float *__restrict__ A,
             sf.t[0] = sf.t[0] * ib;
             sf.t[1] = sf.t[1] * ib;
             const X32 d = matvec32(a.b, sf);
+            if (CERT3) {
+                X32 gs;
+                gs.t[0] = e[s].t[0] * Gv.t[0] * ib;
+                gs.t[1] = e[s].t[1] * Gv.t[1] * ib;
+                const X32 ug = matvec32(a.b, gs);
+                Gv.t[0] = sel4(act, born4(d.t[0], ug.t[0], eps), Gv.t[0]);
+                Gv.t[1] = sel4(act, born4(d.t[1], ug.t[1], eps), Gv.t[1]);
+            }
             Rv.t[0] = sel4(act, MODE == 3 ? fmax4(d.t[0], eps) : clamp_flag4(d.t[0], eps), Rv.t[0]);
             Rv.t[1] = sel4(act, MODE == 3 ? fmax4(d.t[1], eps) : clamp_flag4(d.t[1], eps), Rv.t[1]);
         }
@@ -553,15 +644,44 @@ __global__ __launch_bounds__(256) void k32_backward(const float *__restrict__ A,
     }
     phiacc = col_sum(phiacc);
     if (MODE != 3 && g == 0 && tl.valid) phi[tl.chain] = phiacc;
+    if (CERT3) {
+        // alpha_hat at the chunk's first position, up to scale: one forward step from the vector entering the chunk
+        X32 P, a0;
+        P.t[0] = *reinterpret_cast<const f4 *>(prefix + (size_t)tl.chain * Q32 + 4 * g);
+        P.t[1] = *reinterpret_cast<const f4 *>(prefix + (size_t)tl.chain * Q32 + 16 + 4 * g);
+        const X32 dp = matvec32(a.f, P);
+        a0.t[0] = fmax4(sel4(tl.first, P.t[0], dp.t[0]), eps) * ec0.t[0];
+        a0.t[1] = fmax4(sel4(tl.first, P.t[1], dp.t[1]), eps) * ec0.t[1];
+        float c = dot32(a0, Gc) * __builtin_amdgcn_rcpf(dot32(a0, Rc));
+        c = fmaxf(c, sum32(Gv) * __builtin_amdgcn_rcpf(sum32(Rv)));        // what the chunk before does not get
+        // ... and what that share becomes under the last row of the chunk before (whose kernel starts from the chunk
+        // scan's floor-free suffix vector)
+        X32 ep;
+        ep.t[0] = ep.t[1] = zero4;
+        if (tl.valid && tl.chain % p.C != 0) {               // (not the sequence's first chunk: the row exists)
+            const char *pe = reinterpret_cast<const char *>(tl.baseE) + (tl.voff - rowb);
+            const f4u r0 = *reinterpret_cast<const f4u *>(pe), r1 = *reinterpret_cast<const f4u *>(pe + 64);
+            X32 raw;
+            raw.t[0] = (f4){r0.x, r0.y, r0.z, r0.w};
+            raw.t[1] = (f4){r1.x, r1.y, r1.z, r1.w};
+            ep = clamp32(raw, bd);
+        }
+        const float dn = dot32(ep, Rv);
+        c = fmaxf(c, dn > 0.f ? dot32(ep, Gv) * __builtin_amdgcn_rcpf(dn) : 0.f);
+        if (g == 0 && tl.valid) phi[tl.chain] = c;
+    }
 }
 
 // need[seq] = 1: the serial kernels (hmm_midq.inc) compute this sequence — its model is not served by the
-// chunked scan, or its floor-transition bound is above EXACT_DELTA
-// exps (or null; rows of W ints): the sparse reduce marks chains whose operator columns went through the denormal
-// range in the pad lane of their exponent row (reduce_sparse_wave's `risk`): such a sequence is flagged as well
+// chunked scan, or its certificate (phi summed over its chunks: psi of the posterior, the one-directional CERT /
+// CERT3 sums of hmm_forward / hmm_backward) is above EXACT_DELTA, or a reduce marked one of its chains: the
+// operator columns went through the denormal range, or every column met an observation it survives at the emission
+// floor only.  The sparse reduce keeps that mark in the pad lane of the exponent row (rows of W ints; 29 < W
+// states), the dense reduces in risk[chain] (any q up to W).
 __global__ __launch_bounds__(256) void k32_select(const int *__restrict__ elig, const float *__restrict__ phi,
                                                   int *__restrict__ need, int *__restrict__ nex, Plan p, float eps,
-                                                  int exact_mode, const int *__restrict__ exps = nullptr, int W = 0) {
+                                                  int exact_mode, const int *__restrict__ exps, const int *__restrict__ risk,
+                                                  int W) {
     const int seq = blockIdx.x * 256 + threadIdx.x;
     if (seq >= p.NB) return;
     const int el = elig[seq / p.b];
@@ -571,8 +691,13 @@ __global__ __launch_bounds__(256) void k32_select(const int *__restrict__ elig, 
         for (int c = 0; c < p.C; ++c) s += phi[(size_t)seq * p.C + c];
         f = !(s <= EXACT_DELTA);
     }
-    if (!f && exps && exact_mode == HMM_EXACT_AUTO && p.q < W)                  // (q = W: no pad lane, no mark)
-        for (int c = 0; c < p.C; ++c) f = f || exps[((size_t)seq * p.C + c) * W + W - 1] != 0;
+    if (!f && exact_mode == HMM_EXACT_AUTO) {
+        const bool dense = el == ID_DENSE32 || el == ID_DENSE64;
+        for (int c = 0; c < p.C; ++c) {
+            const size_t chain = (size_t)seq * p.C + c;
+            f = f || (dense ? risk[chain] != 0 : exps[chain * W + W - 1] != 0);
+        }
+    }
     need[seq] = f ? 1 : 0;
     if (f) atomicAdd(nex, 1);
 }
@@ -585,7 +710,8 @@ __global__ __launch_bounds__(256) void k32_select(const int *__restrict__ elig, 
 // batch), but the serial kernels take their ~66 ms for 16 sequences as for 1024, and this scales with the work.
 __global__ __launch_bounds__(256) void k32_reduce_dense(const float *__restrict__ A, const float *__restrict__ E,
                                                         float *__restrict__ ops, int *__restrict__ exps,
-                                                        const int *__restrict__ elig, Plan p, float eps) {
+                                                        int *__restrict__ riskv, const int *__restrict__ elig, Plan p,
+                                                        float eps) {
     const int lane = threadIdx.x & 63, g = lane >> 4, n = lane & 15;
     const int q = p.q;
     const long long stride = (long long)gridDim.x * 4;
@@ -617,15 +743,17 @@ __global__ __launch_bounds__(256) void k32_reduce_dense(const float *__restrict_
             }
         int ex[2] = {0, 0};                         // column 16 cb + n holds X[:, .] * 2^-ex[cb]
         // risk: EVERY column lost more than 2^-45 in ONE step — an observation that everything survives at the emission floor
-        // only; the one-directional entry points of this path have no certificate of their own, so such sequences go to
-        // the serial kernels (the mark: pad lane of the exponent row, read by k32_select; q = 32 has no pad lane)
+        // only —, or a column's sum went below 2^-100 (the denormal range: reduce_sparse_wave's `risk`).  Such sequences
+        // go to the serial kernels (the mark: riskv[chain], read by k32_select).  The exponent is clamped at -100 so that
+        // the factor stays finite for a column in the denormal range.
         bool risk = false;
         auto rescale = [&]() {
             bool kept = false;                      // some column lost less than 2^-45 in this step
 #pragma unroll
             for (int cb = 0; cb < 2; ++cb) {
                 const float sden = sum32(X[cb]);
-                const int xe = __builtin_amdgcn_frexp_expf(sden);
+                risk = risk || (16 * cb + n < q && sden < 0x1p-100f);
+                const int xe = max(__builtin_amdgcn_frexp_expf(sden), -100);
                 kept = kept || (16 * cb + n < q && !(xe < -45));
                 const float sc = __builtin_amdgcn_ldexpf(1.0f, -xe);
                 X[cb].t[0] = X[cb].t[0] * sc;
@@ -678,9 +806,10 @@ __global__ __launch_bounds__(256) void k32_reduce_dense(const float *__restrict_
                 o[(16 * r + 4 * g + 2) * Q32 + 16 * cb + n] = X[cb].t[r].z;
                 o[(16 * r + 4 * g + 3) * Q32 + 16 * cb + n] = X[cb].t[r].w;
             }
-            const bool mark = q < Q32 && 16 * cb + n == Q32 - 1 && __builtin_amdgcn_ballot_w64(risk) != 0ull;
-            if (g == 0) exps[(size_t)chain * Q32 + 16 * cb + n] = mark ? 1 : ex[cb];
+            if (g == 0) exps[(size_t)chain * Q32 + 16 * cb + n] = 16 * cb + n < q ? ex[cb] : 0;
         }
+        const bool mark = __builtin_amdgcn_ballot_w64(risk) != 0ull;
+        if (lane == 0) riskv[chain] = mark ? 1 : 0;
     }
 }
 
@@ -701,20 +830,35 @@ static void scan32_reduce_scan(const float *A, const float *pi, const float *E, 
     {   // models outside the compiled topology: every chain its own wave (grid stride; exits at once otherwise)
         const long long nbd = (p.nchains + 3) / 4;
         hipLaunchKernelGGL(k32_reduce_dense, dim3((unsigned)(nbd < 8192 ? nbd : 8192)), dim3(256), 0, st, A, E, ops, exps,
-                           (const int *)elig, p, eps);
+                           (int *)(ws + pp.o_risk), (const int *)elig, p, eps);
     }
     hipLaunchKernelGGL(k32_scan, dim3(p.NB), dim3(128), 0, st, pi, (const float *)ops, (const int *)exps,
                        (float *)(ws + pp.o_prefix), (double *)(ws + pp.o_llpre), (float *)(ws + pp.o_suffix),
                        (double *)(ws + pp.o_lsuf), (double *)(ws + pp.o_loglik), (const int *)elig, p, eps);
 }
 
-// log-likelihoods of the models the chunked path serves -> ws loglik; need[] for the others
+// need[] from the certificate sums phi (or null: the reduces' marks only)
+static void scan32_select(const Plan32 &pp, const float *phi, char *ws, hipStream_t st) {
+    const Plan &p = pp.p;
+    hipLaunchKernelGGL(k32_select, dim3((p.NB + 255) / 256), dim3(256), 0, st, (const int *)(ws + pp.o_elig), phi,
+                       (int *)(ws + pp.o_need), (int *)(ws + pp.o_nex), p, 0.f, opt(HMM_OPT_EXACT),
+                       (const int *)(ws + pp.o_exps), (const int *)(ws + pp.o_risk), Q32);
+}
+
+// log-likelihoods of the models the chunked path serves -> ws loglik; need[] for the others.  The log-likelihood comes
+// out of the chunk scan; the forward apply kernel runs for the certificate only (k32_forward<false, true>), as
+// hmm_forward's scan plan does for 16 states.
 static void scan32_loglik(const float *A, const float *pi, const float *E, const Plan32 &pp, float eps, char *ws,
                           hipStream_t st) {
     const Plan &p = pp.p;
     scan32_reduce_scan(A, pi, E, pp, eps, ws, st);
-    hipLaunchKernelGGL(k32_select, dim3((p.NB + 255) / 256), dim3(256), 0, st, (const int *)(ws + pp.o_elig),
-                       (const float *)nullptr, (int *)(ws + pp.o_need), (int *)(ws + pp.o_nex), p, eps, opt(HMM_OPT_EXACT), (const int *)(ws + pp.o_exps), Q32);
+    const bool cert = opt(HMM_OPT_EXACT) == HMM_EXACT_AUTO;
+    float *phi = (float *)(ws + pp.o_phi);
+    if (cert)
+        hipLaunchKernelGGL((k32_forward<false, true>), dim3((unsigned)((pp.nwaves + 3) / 4)), dim3(256), 0, st, A, E,
+                           (const float *)(ws + pp.o_prefix), (const double *)nullptr, (float *)nullptr, (float *)nullptr,
+                           (const int *)(ws + pp.o_elig), p, eps, pp.nwaves, (const float *)(ws + pp.o_suffix), phi);
+    scan32_select(pp, cert ? phi : nullptr, ws, st);
 }
 
 static void scan32_posterior(const float *A, const float *pi, const float *E, const Plan32 &pp, float eps, int mode,
@@ -725,37 +869,50 @@ static void scan32_posterior(const float *A, const float *pi, const float *E, co
     float *ckpt = (float *)(ws + pp.o_ckpt);
     const dim3 grid((unsigned)((pp.nwaves + 3) / 4));
     hipLaunchKernelGGL(k32_forward<false>, grid, dim3(256), 0, st, A, E, (const float *)(ws + pp.o_prefix),
-                       (const double *)nullptr, ckpt, (float *)nullptr, elig, p, eps, pp.nwaves);
+                       (const double *)nullptr, ckpt, (float *)nullptr, elig, p, eps, pp.nwaves,
+                       (const float *)nullptr, (float *)nullptr);
     const float *sx = (const float *)(ws + pp.o_suffix);
     const double *ls = (const double *)(ws + pp.o_lsuf);
     const double *ll = (const double *)(ws + pp.o_loglik);
     float *phi = (float *)(ws + pp.o_phi);
     if (mode == HMM_POST_PROB)
-        hipLaunchKernelGGL((k32_backward<0>), grid, dim3(256), 0, st, A, E, (const float *)ckpt, sx, ls, ll, out, phi, elig, p, eps, pp.nwaves);
+        hipLaunchKernelGGL((k32_backward<0>), grid, dim3(256), 0, st, A, E, (const float *)ckpt, sx, ls, ll, out, phi, elig, p, eps, pp.nwaves,
+                           (const float *)nullptr);
     else if (mode == HMM_POST_LOG)
-        hipLaunchKernelGGL((k32_backward<1>), grid, dim3(256), 0, st, A, E, (const float *)ckpt, sx, ls, ll, out, phi, elig, p, eps, pp.nwaves);
+        hipLaunchKernelGGL((k32_backward<1>), grid, dim3(256), 0, st, A, E, (const float *)ckpt, sx, ls, ll, out, phi, elig, p, eps, pp.nwaves,
+                           (const float *)nullptr);
     else
-        hipLaunchKernelGGL((k32_backward<2>), grid, dim3(256), 0, st, A, E, (const float *)ckpt, sx, ls, ll, out, phi, elig, p, eps, pp.nwaves);
-    hipLaunchKernelGGL(k32_select, dim3((p.NB + 255) / 256), dim3(256), 0, st, elig, (const float *)phi,
-                       (int *)(ws + pp.o_need), (int *)(ws + pp.o_nex), p, eps, opt(HMM_OPT_EXACT), (const int *)(ws + pp.o_exps), Q32);
+        hipLaunchKernelGGL((k32_backward<2>), grid, dim3(256), 0, st, A, E, (const float *)ckpt, sx, ls, ll, out, phi, elig, p, eps, pp.nwaves,
+                           (const float *)nullptr);
+    scan32_select(pp, phi, ws, st);
 }
 
-// log alpha (and the log-likelihoods) of the models the chunked path serves; need[] for the others
+// log alpha (and the log-likelihoods) of the models the chunked path serves; need[] for the others.  The certificate
+// variant runs whatever the routing mode, so that EXACT_OFF and the automatic routing compute an unflagged sequence
+// with the same kernel.
 static void scan32_forward(const float *A, const float *pi, const float *E, const Plan32 &pp, float eps, float *log_alpha,
                            char *ws, hipStream_t st) {
     const Plan &p = pp.p;
-    scan32_loglik(A, pi, E, pp, eps, ws, st);
-    hipLaunchKernelGGL(k32_forward<true>, dim3((unsigned)((pp.nwaves + 3) / 4)), dim3(256), 0, st, A, E,
+    scan32_reduce_scan(A, pi, E, pp, eps, ws, st);
+    float *phi = (float *)(ws + pp.o_phi);
+    hipLaunchKernelGGL((k32_forward<true, true>), dim3((unsigned)((pp.nwaves + 3) / 4)), dim3(256), 0, st, A, E,
                        (const float *)(ws + pp.o_prefix), (const double *)(ws + pp.o_llpre), (float *)nullptr, log_alpha,
-                       (const int *)(ws + pp.o_elig), p, eps, pp.nwaves);
+                       (const int *)(ws + pp.o_elig), p, eps, pp.nwaves, (const float *)(ws + pp.o_suffix), phi);
+    scan32_select(pp, phi, ws, st);
 }
 
-// log beta of the models the chunked path serves; need[] for the others (pi only feeds the unused prefix chain)
+// log beta of the models the chunked path serves; need[] for the others.  hmm_backward has no start distribution: the
+// chunk scan's forward half, whose vectors weigh the certificate (k32_backward's CERT3), starts from the uniform one.
 static void scan32_backward(const float *A, const float *E, const Plan32 &pp, float eps, float *log_beta, char *ws,
                             hipStream_t st) {
     const Plan &p = pp.p;
-    scan32_loglik(A, A, E, pp, eps, ws, st);
-    hipLaunchKernelGGL((k32_backward<3>), dim3((unsigned)((pp.nwaves + 3) / 4)), dim3(256), 0, st, A, E,
+    float *upi = (float *)(ws + pp.o_upi);
+    (void)hipMemsetD32Async((hipDeviceptr_t)upi, __builtin_bit_cast(int, 1.0f / (float)p.q), (size_t)p.k * p.q, st);
+    scan32_reduce_scan(A, upi, E, pp, eps, ws, st);
+    float *phi = (float *)(ws + pp.o_phi);
+    hipLaunchKernelGGL((k32_backward<3, true>), dim3((unsigned)((pp.nwaves + 3) / 4)), dim3(256), 0, st, A, E,
                        (const float *)nullptr, (const float *)(ws + pp.o_suffix), (const double *)(ws + pp.o_lsuf),
-                       (const double *)nullptr, log_beta, (float *)nullptr, (const int *)(ws + pp.o_elig), p, eps, pp.nwaves);
+                       (const double *)nullptr, log_beta, phi, (const int *)(ws + pp.o_elig), p, eps, pp.nwaves,
+                       (const float *)(ws + pp.o_prefix));
+    scan32_select(pp, phi, ws, st);
 }

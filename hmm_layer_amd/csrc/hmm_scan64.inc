@@ -29,7 +29,6 @@
 #define SCAN64_MAX_SEQ 96             // sequences per call up to which 33..64 states take the chunked path
 #define SCAN64_MIN_LEN 256
 #define SCAN64_SPARSE_MAX_SEQ 56     // ... for sparse models (see k64_check)
-#define ID_DENSE64 5
 
 static bool scan64_wanted(int k, int b, int L, int q) {
     return q > Q32 && q <= Q64 && (long long)k * b <= SCAN64_MAX_SEQ && L >= SCAN64_MIN_LEN;
@@ -38,7 +37,8 @@ static bool scan64_wanted(int k, int b, int L, int q) {
 struct Plan64 {
     Plan p;                           // shape and chunking (nsub = T / SUB64)
     long long nwaves;                 // apply waves: 16 (sequence, chunk) pairs each, never straddling models
-    size_t o_ops, o_exps, o_prefix, o_llpre, o_suffix, o_lsuf, o_loglik, o_ckpt, o_phi, o_need, o_elig, o_nex, total;
+    size_t o_ops, o_exps, o_prefix, o_llpre, o_suffix, o_lsuf, o_loglik, o_ckpt, o_phi, o_need, o_elig, o_nex;
+    size_t o_risk, o_upi, total;      // the dense reduce's per-chain mark; hmm_backward's uniform start distribution
 };
 
 static int make_plan64(int op, int k, int b, int L, int q, Plan64 *pp) {
@@ -63,6 +63,8 @@ static int make_plan64(int op, int k, int b, int L, int q, Plan64 *pp) {
     pp->o_need = off;   off = align_up(off + (size_t)p.NB * sizeof(int));
     pp->o_elig = off;   off = align_up(off + (size_t)k * sizeof(int));
     pp->o_nex = off;    off = align_up(off + sizeof(int));
+    pp->o_risk = off;   off = align_up(off + (size_t)p.nchains * sizeof(int));
+    pp->o_upi = off;    off = align_up(off + (size_t)k * q * sizeof(float));
     pp->o_ckpt = off;
     if (op == HMM_OP_POSTERIOR)
         off = align_up(off + (size_t)pp->nwaves * p.nsub * 16 * Q64 * sizeof(float));
@@ -238,7 +240,8 @@ __device__ __forceinline__ void flush64(const Out64 &o, int lane, int row0, int 
 // ---- dense reduce: one wave per (sequence, chunk); X[cb].t[r]: rows 16 r + 4g .. + 3 of column 16 cb + n
 __global__ __launch_bounds__(256) void k64_reduce_dense(const float *__restrict__ A, const float *__restrict__ E,
                                                         float *__restrict__ ops, int *__restrict__ exps,
-                                                        const int *__restrict__ elig, Plan p, float eps) {
+                                                        int *__restrict__ riskv, const int *__restrict__ elig, Plan p,
+                                                        float eps) {
     const int lane = threadIdx.x & 63, g = lane >> 4, n = lane & 15;
     const int q = p.q;
     const long long stride = (long long)gridDim.x * 4;
@@ -269,13 +272,14 @@ __global__ __launch_bounds__(256) void k64_reduce_dense(const float *__restrict_
                 X[cb].t[r] = v;
             }
         int ex[4] = {0, 0, 0, 0};
-        bool risk = false;                           // every column lost more than 2^-45 in one step: see k32_reduce_dense
+        bool risk = false;                           // -> riskv[chain]: see k32_reduce_dense
         auto rescale = [&]() {
             bool kept = false;
 #pragma unroll
             for (int cb = 0; cb < 4; ++cb) {
                 const float sden = sum64(X[cb]);
-                const int xe = __builtin_amdgcn_frexp_expf(sden);
+                risk = risk || (16 * cb + n < q && sden < 0x1p-100f);
+                const int xe = max(__builtin_amdgcn_frexp_expf(sden), -100);
                 kept = kept || (16 * cb + n < q && !(xe < -45));
                 const float sc = __builtin_amdgcn_ldexpf(1.0f, -xe);
 #pragma unroll
@@ -321,9 +325,10 @@ __global__ __launch_bounds__(256) void k64_reduce_dense(const float *__restrict_
                 o[(16 * r + 4 * g + 2) * Q64 + 16 * cb + n] = X[cb].t[r].z;
                 o[(16 * r + 4 * g + 3) * Q64 + 16 * cb + n] = X[cb].t[r].w;
             }
-            const bool mark = q < Q64 && 16 * cb + n == Q64 - 1 && __builtin_amdgcn_ballot_w64(risk) != 0ull;
-            if (g == 0) exps[(size_t)chain * Q64 + 16 * cb + n] = mark ? 1 : ex[cb];
+            if (g == 0) exps[(size_t)chain * Q64 + 16 * cb + n] = 16 * cb + n < q ? ex[cb] : 0;
         }
+        const bool mark = __builtin_amdgcn_ballot_w64(risk) != 0ull;
+        if (lane == 0) riskv[chain] = mark ? 1 : 0;
     }
 }
 
@@ -398,13 +403,20 @@ __global__ __launch_bounds__(128) void k64_scan(const float *__restrict__ pi, co
     }
 }
 
-// ---- apply, forward.  LOGA = false: alpha_hat entering every SUB64-step block -> ckpt ([wave][block][chain][64]);
-// LOGA = true: log alpha -> out (hmm_forward with log alpha)
-template <bool LOGA>
+__device__ __forceinline__ float dot64(const X64 &a, const X64 &b) {
+    return col_sum((hsum(a.t[0] * b.t[0]) + hsum(a.t[1] * b.t[1])) + (hsum(a.t[2] * b.t[2]) + hsum(a.t[3] * b.t[3])));
+}
+
+// ---- apply, forward.  LOGA = false, CERT = false: alpha_hat entering every SUB64-step block -> ckpt
+// ([wave][block][chain][64]); LOGA = true: log alpha -> out (hmm_forward with log alpha); CERT: the clamp-born share
+// -> phi[chain], k32_forward's CERT
+template <bool LOGA, bool CERT = false>
 __global__ __launch_bounds__(256) void k64_forward(const float *__restrict__ A, const float *__restrict__ E,
                                                    const float *__restrict__ prefix, const double *__restrict__ llpre,
                                                    float *__restrict__ ckpt, float *__restrict__ out,
-                                                   const int *__restrict__ elig, Plan p, float eps, long long nwaves) {
+                                                   const int *__restrict__ elig, Plan p, float eps, long long nwaves,
+                                                   const float *__restrict__ suffix = nullptr, float *__restrict__ phi = nullptr) {
+    constexpr bool CKPT = !LOGA && !CERT;
     const long long wave = (long long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (wave >= nwaves) return;
     const int lane = threadIdx.x & 63, g = lane >> 4, n = lane & 15;
@@ -416,7 +428,11 @@ __global__ __launch_bounds__(256) void k64_forward(const float *__restrict__ A, 
     const B64 bd = make_bounds64(g, q, eps);
     const int rowb = q * (int)sizeof(float);
     X64 X = ld_vec64(prefix + (size_t)tl.chain * Q64, g);
-    float *ck = LOGA ? nullptr : ckpt + (((size_t)wave * p.nsub) * 16 + n) * Q64 + 4 * g;
+    const f4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    X64 Fv, Xc = X, Fc;                                      // CERT: clamp-born part of X; both at the chain's last step
+#pragma unroll
+    for (int t = 0; t < 4; ++t) Fv.t[t] = Fc.t[t] = zero4;
+    float *ck = CKPT ? ckpt + (((size_t)wave * p.nsub) * 16 + n) * Q64 + 4 * g : nullptr;
     __shared__ __attribute__((aligned(16))) float ostage[LOGA ? 4 * OUT64_SEG : 4];
     Out64 os = {};
     if (LOGA)
@@ -428,7 +444,7 @@ __global__ __launch_bounds__(256) void k64_forward(const float *__restrict__ A, 
     X64 en[SUB64];
     ld_rows64<SUB64>(tl.rsE, voff, rowb, en);
     for (int j = 0; j < p.nsub; ++j) {
-        if (!LOGA && tl.valid && j * SUB64 < tl.len) {
+        if (CKPT && tl.valid && j * SUB64 < tl.len) {
 #pragma unroll
             for (int t = 0; t < 4; ++t) *reinterpret_cast<f4 *>(ck + (size_t)j * 16 * Q64 + 16 * t) = X.t[t];
         }
@@ -447,8 +463,20 @@ __global__ __launch_bounds__(256) void k64_forward(const float *__restrict__ A, 
             for (int t = 0; t < 4; ++t) sf.t[t] = fmax4(sel4(init, X.t[t], d.t[t]), eps) * ec.t[t];
             const float S = sum64(sf);
             const float inv = __builtin_amdgcn_rcpf(S);
+            if (CERT) {
+                const X64 df = matvec64(a, Fv);
+                const bool last = j * SUB64 + s + 1 == tl.len;
 #pragma unroll
-            for (int t = 0; t < 4; ++t) X.t[t] = sf.t[t] * inv;
+                for (int t = 0; t < 4; ++t) {
+                    Fv.t[t] = sel4(init, Fv.t[t], born4(d.t[t], df.t[t], eps)) * ec.t[t] * inv;
+                    X.t[t] = sf.t[t] * inv;
+                    Xc.t[t] = sel4(last, X.t[t], Xc.t[t]);
+                    Fc.t[t] = sel4(last, Fv.t[t], Fc.t[t]);
+                }
+            } else {
+#pragma unroll
+                for (int t = 0; t < 4; ++t) X.t[t] = sf.t[t] * inv;
+            }
             if (LOGA) {
                 lacc += (j * SUB64 + s < tl.len) ? __logf(S) : 0.f;
                 const float base = (float)(llb + (double)lacc);
@@ -464,16 +492,42 @@ __global__ __launch_bounds__(256) void k64_forward(const float *__restrict__ A, 
         }
         voff += SUB64 * rowb;
     }
+    if (CERT) {
+        const X64 sv = ld_vec64(suffix + (size_t)tl.chain * Q64, g);
+        float c = dot64(Fc, sv) * __builtin_amdgcn_rcpf(dot64(Xc, sv));
+        if (LOGA) {                                          // (k32_forward's shmax and shnext)
+            X64 en1;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) en1.t[t] = zero4;
+            const bool more = tl.valid && tl.chain % p.C != p.C - 1;
+            if (more) {
+                X64 r1[1];
+                ld_rows64<1>(tl.rsE, tl.voff + tl.len * rowb, rowb, r1);
+                en1 = clamp64(r1[0], bd);
+            }
+            X64 dx = matvec64(a, Xc);
+            const X64 df = matvec64(a, Fc);
+#pragma unroll
+            for (int t = 0; t < 4; ++t) dx.t[t] = fmax4(dx.t[t], eps);
+            const float dn = dot64(en1, dx);
+            const float shnext = (more && dn > 0.f) ? dot64(en1, df) * __builtin_amdgcn_rcpf(dn) : 0.f;
+            c = fmaxf(fmaxf(c, sum64(Fc)), shnext);
+        }
+        if (tl.valid && g == 0) phi[tl.chain] = c;
+    }
 }
 
 // ---- apply, backward.  MODE 0: gamma, 1: log gamma, 2: log gamma + loglik, 3: log beta (no forward part).
 // phi: psi per chain (backward_body in hmm_engine.hip).  A's forward operands in registers, the backward ones in LDS.
-template <int MODE>
+// CERT3 (MODE 3): the clamp-born share of R -> phi[chain], k32_backward's CERT3
+template <int MODE, bool CERT3 = false>
 __global__ __launch_bounds__(256) void k64_backward(const float *__restrict__ A, const float *__restrict__ E,
                                                     const float *__restrict__ ckpt, const float *__restrict__ suffix,
                                                     const double *__restrict__ lsuf, const double *__restrict__ loglik,
                                                     float *__restrict__ out, float *__restrict__ phi,
-                                                    const int *__restrict__ elig, Plan p, float eps, long long nwaves) {
+                                                    const int *__restrict__ elig, Plan p, float eps, long long nwaves,
+                                                    const float *__restrict__ prefix = nullptr) {
+    static_assert(!CERT3 || MODE == 3, "CERT3 is the log beta certificate");
     const long long wave = (long long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (wave >= nwaves) return;
     const int lane = threadIdx.x & 63, g = lane >> 4, n = lane & 15;
@@ -507,6 +561,9 @@ __global__ __launch_bounds__(256) void k64_backward(const float *__restrict__ A,
     const float *ck = MODE == 3 ? nullptr : ckpt + (((size_t)wave * p.nsub) * 16 + n) * Q64 + 4 * g;
     float psacc = 0.f;
     const f4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    X64 Gv, Rc = Rv, Gc, ec0;                                // CERT3: clamp-born part of R; R, Gv, E at the first position
+#pragma unroll
+    for (int t = 0; t < 4; ++t) Gv.t[t] = Gc.t[t] = ec0.t[t] = zero4;
     constexpr int GB = OUT64_ROWS / SUB64;
     for (int j = p.nsub - 1; j >= 0; --j) {
         const int srow = (j % GB) * SUB64;
@@ -558,6 +615,7 @@ __global__ __launch_bounds__(256) void k64_backward(const float *__restrict__ A,
                 }
             }
             stage64(os, n, g, srow + s, gm);
+            if (CERT3 && s == 0) { Rc = Rv; Gc = Gv; ec0 = e[0]; }      // (the last block executed is the chunk's first)
             X64 sf;
 #pragma unroll
             for (int t = 0; t < 4; ++t) sf.t[t] = MODE == 3 ? e[s].t[t] * Rv.t[t] : mul_abs4(Rv.t[t], e[s].t[t]);
@@ -567,6 +625,14 @@ __global__ __launch_bounds__(256) void k64_backward(const float *__restrict__ A,
 #pragma unroll
             for (int t = 0; t < 4; ++t) sf.t[t] = sf.t[t] * ib;
             const X64 d = matvec64_lds(la, lane, sf);
+            if (CERT3) {
+                X64 gs;
+#pragma unroll
+                for (int t = 0; t < 4; ++t) gs.t[t] = e[s].t[t] * Gv.t[t] * ib;
+                const X64 ug = matvec64_lds(la, lane, gs);
+#pragma unroll
+                for (int t = 0; t < 4; ++t) Gv.t[t] = sel4(act, born4(d.t[t], ug.t[t], eps), Gv.t[t]);
+            }
 #pragma unroll
             for (int t = 0; t < 4; ++t)
                 Rv.t[t] = sel4(act, MODE == 3 ? fmax4(d.t[t], eps) : clamp_flag4(d.t[t], eps), Rv.t[t]);
@@ -576,6 +642,33 @@ __global__ __launch_bounds__(256) void k64_backward(const float *__restrict__ A,
     }
     psacc = col_sum(psacc);
     if (MODE != 3 && g == 0 && tl.valid) phi[tl.chain] = psacc;
+    if (CERT3) {                                             // (k32_backward's CERT3)
+        A64 afc;
+        load_A64(A + (size_t)tl.m * q * q, q, g, n, true, afc);
+        const X64 P = ld_vec64(prefix + (size_t)tl.chain * Q64, g);
+        const X64 dp = matvec64(afc, P);
+        X64 a0;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) a0.t[t] = fmax4(sel4(tl.first, P.t[t], dp.t[t]), eps) * ec0.t[t];
+        float c = dot64(a0, Gc) * __builtin_amdgcn_rcpf(dot64(a0, Rc));
+        c = fmaxf(c, sum64(Gv) * __builtin_amdgcn_rcpf(sum64(Rv)));
+        X64 ep;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) ep.t[t] = zero4;
+        if (tl.valid && tl.chain % p.C != 0) {
+            const char *pe = reinterpret_cast<const char *>(tl.baseE) + (tl.voff - rowb);
+            X64 raw;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const f4u r = *reinterpret_cast<const f4u *>(pe + 64 * t);
+                raw.t[t] = (f4){r.x, r.y, r.z, r.w};
+            }
+            ep = clamp64(raw, bd);
+        }
+        const float dn = dot64(ep, Rv);
+        c = fmaxf(c, dn > 0.f ? dot64(ep, Gv) * __builtin_amdgcn_rcpf(dn) : 0.f);
+        if (g == 0 && tl.valid) phi[tl.chain] = c;
+    }
 }
 
 // ---- host side
@@ -590,19 +683,31 @@ static void scan64_reduce_scan(const float *A, const float *pi, const float *E, 
     int *exps = (int *)(ws + pp.o_exps);
     const long long nbd = (p.nchains + 3) / 4;
     hipLaunchKernelGGL(k64_reduce_dense, dim3((unsigned)(nbd < 8192 ? nbd : 8192)), dim3(256), 0, st, A, E, ops, exps,
-                       (const int *)elig, p, eps);
+                       (int *)(ws + pp.o_risk), (const int *)elig, p, eps);
     hipLaunchKernelGGL(k64_scan, dim3(p.NB), dim3(128), 0, st, pi, (const float *)ops, (const int *)exps,
                        (float *)(ws + pp.o_prefix), (double *)(ws + pp.o_llpre), (float *)(ws + pp.o_suffix),
                        (double *)(ws + pp.o_lsuf), (double *)(ws + pp.o_loglik), (const int *)elig, p, eps);
 }
 
-// log-likelihoods of the models the chunked path serves -> ws loglik; need[] for the others
+static void scan64_select(const Plan64 &pp, const float *phi, char *ws, hipStream_t st) {
+    const Plan &p = pp.p;
+    hipLaunchKernelGGL(k32_select, dim3((p.NB + 255) / 256), dim3(256), 0, st, (const int *)(ws + pp.o_elig), phi,
+                       (int *)(ws + pp.o_need), (int *)(ws + pp.o_nex), p, 0.f, opt(HMM_OPT_EXACT),
+                       (const int *)(ws + pp.o_exps), (const int *)(ws + pp.o_risk), Q64);
+}
+
+// log-likelihoods of the models the chunked path serves -> ws loglik; need[] for the others (scan32_loglik)
 static void scan64_loglik(const float *A, const float *pi, const float *E, const Plan64 &pp, float eps, char *ws,
                           hipStream_t st) {
     const Plan &p = pp.p;
     scan64_reduce_scan(A, pi, E, pp, eps, ws, st);
-    hipLaunchKernelGGL(k32_select, dim3((p.NB + 255) / 256), dim3(256), 0, st, (const int *)(ws + pp.o_elig),
-                       (const float *)nullptr, (int *)(ws + pp.o_need), (int *)(ws + pp.o_nex), p, eps, opt(HMM_OPT_EXACT), (const int *)(ws + pp.o_exps), Q64);
+    const bool cert = opt(HMM_OPT_EXACT) == HMM_EXACT_AUTO;
+    float *phi = (float *)(ws + pp.o_phi);
+    if (cert)
+        hipLaunchKernelGGL((k64_forward<false, true>), dim3((unsigned)((pp.nwaves + 3) / 4)), dim3(256), 0, st, A, E,
+                           (const float *)(ws + pp.o_prefix), (const double *)nullptr, (float *)nullptr, (float *)nullptr,
+                           (const int *)(ws + pp.o_elig), p, eps, pp.nwaves, (const float *)(ws + pp.o_suffix), phi);
+    scan64_select(pp, cert ? phi : nullptr, ws, st);
 }
 
 static void scan64_posterior(const float *A, const float *pi, const float *E, const Plan64 &pp, float eps, int mode,
@@ -613,33 +718,46 @@ static void scan64_posterior(const float *A, const float *pi, const float *E, co
     float *ckpt = (float *)(ws + pp.o_ckpt);
     const dim3 grid((unsigned)((pp.nwaves + 3) / 4));
     hipLaunchKernelGGL(k64_forward<false>, grid, dim3(256), 0, st, A, E, (const float *)(ws + pp.o_prefix),
-                       (const double *)nullptr, ckpt, (float *)nullptr, elig, p, eps, pp.nwaves);
+                       (const double *)nullptr, ckpt, (float *)nullptr, elig, p, eps, pp.nwaves,
+                       (const float *)nullptr, (float *)nullptr);
     const float *sx = (const float *)(ws + pp.o_suffix);
     const double *ls = (const double *)(ws + pp.o_lsuf);
     const double *ll = (const double *)(ws + pp.o_loglik);
     float *phi = (float *)(ws + pp.o_phi);
     if (mode == HMM_POST_PROB)
-        hipLaunchKernelGGL((k64_backward<0>), grid, dim3(256), 0, st, A, E, (const float *)ckpt, sx, ls, ll, out, phi, elig, p, eps, pp.nwaves);
+        hipLaunchKernelGGL((k64_backward<0>), grid, dim3(256), 0, st, A, E, (const float *)ckpt, sx, ls, ll, out, phi, elig, p, eps, pp.nwaves,
+                           (const float *)nullptr);
     else if (mode == HMM_POST_LOG)
-        hipLaunchKernelGGL((k64_backward<1>), grid, dim3(256), 0, st, A, E, (const float *)ckpt, sx, ls, ll, out, phi, elig, p, eps, pp.nwaves);
+        hipLaunchKernelGGL((k64_backward<1>), grid, dim3(256), 0, st, A, E, (const float *)ckpt, sx, ls, ll, out, phi, elig, p, eps, pp.nwaves,
+                           (const float *)nullptr);
     else
-        hipLaunchKernelGGL((k64_backward<2>), grid, dim3(256), 0, st, A, E, (const float *)ckpt, sx, ls, ll, out, phi, elig, p, eps, pp.nwaves);
-    hipLaunchKernelGGL(k32_select, dim3((p.NB + 255) / 256), dim3(256), 0, st, elig, (const float *)phi,
-                       (int *)(ws + pp.o_need), (int *)(ws + pp.o_nex), p, eps, opt(HMM_OPT_EXACT), (const int *)(ws + pp.o_exps), Q64);
+        hipLaunchKernelGGL((k64_backward<2>), grid, dim3(256), 0, st, A, E, (const float *)ckpt, sx, ls, ll, out, phi, elig, p, eps, pp.nwaves,
+                           (const float *)nullptr);
+    scan64_select(pp, phi, ws, st);
 }
 
+// (scan32_forward)
 static void scan64_forward(const float *A, const float *pi, const float *E, const Plan64 &pp, float eps, float *log_alpha,
                            char *ws, hipStream_t st) {
-    scan64_loglik(A, pi, E, pp, eps, ws, st);
-    hipLaunchKernelGGL(k64_forward<true>, dim3((unsigned)((pp.nwaves + 3) / 4)), dim3(256), 0, st, A, E,
+    scan64_reduce_scan(A, pi, E, pp, eps, ws, st);
+    float *phi = (float *)(ws + pp.o_phi);
+    hipLaunchKernelGGL((k64_forward<true, true>), dim3((unsigned)((pp.nwaves + 3) / 4)), dim3(256), 0, st, A, E,
                        (const float *)(ws + pp.o_prefix), (const double *)(ws + pp.o_llpre), (float *)nullptr, log_alpha,
-                       (const int *)(ws + pp.o_elig), pp.p, eps, pp.nwaves);
+                       (const int *)(ws + pp.o_elig), pp.p, eps, pp.nwaves, (const float *)(ws + pp.o_suffix), phi);
+    scan64_select(pp, phi, ws, st);
 }
 
+// (scan32_backward: the chunk scan starts from the uniform distribution)
 static void scan64_backward(const float *A, const float *E, const Plan64 &pp, float eps, float *log_beta, char *ws,
                             hipStream_t st) {
-    scan64_loglik(A, A, E, pp, eps, ws, st);
-    hipLaunchKernelGGL((k64_backward<3>), dim3((unsigned)((pp.nwaves + 3) / 4)), dim3(256), 0, st, A, E,
+    const Plan &p = pp.p;
+    float *upi = (float *)(ws + pp.o_upi);
+    (void)hipMemsetD32Async((hipDeviceptr_t)upi, __builtin_bit_cast(int, 1.0f / (float)p.q), (size_t)p.k * p.q, st);
+    scan64_reduce_scan(A, upi, E, pp, eps, ws, st);
+    float *phi = (float *)(ws + pp.o_phi);
+    hipLaunchKernelGGL((k64_backward<3, true>), dim3((unsigned)((pp.nwaves + 3) / 4)), dim3(256), 0, st, A, E,
                        (const float *)nullptr, (const float *)(ws + pp.o_suffix), (const double *)(ws + pp.o_lsuf),
-                       (const double *)nullptr, log_beta, (float *)nullptr, (const int *)(ws + pp.o_elig), pp.p, eps, pp.nwaves);
+                       (const double *)nullptr, log_beta, phi, (const int *)(ws + pp.o_elig), p, eps, pp.nwaves,
+                       (const float *)(ws + pp.o_prefix));
+    scan64_select(pp, phi, ws, st);
 }

@@ -147,8 +147,8 @@ int hmm_backward(const float *A, const float *E,
  *
  * The cell clamps the predicted state MIXTURE at eps every step (hmm_layer/MsaHmmCell.py:87-88); the
  * chunk operators of the scan are the exactly linear products of A diag(max(E, eps)) and know nothing of it.
- * For q <= 16 the engine therefore decides on the device, with no host round trip, which inputs the scan
- * may serve:
+ * For q <= 64 wherever the chunked scan runs, the engine therefore decides on the device, with no host
+ * round trip, which inputs the scan may serve:
  *   - per model: the support of A (entries > eps) must be primitive (irreducible and aperiodic);
  *     reducible or periodic chains, states without incoming edges, all-zero rows (the reference's
  *     as-shipped matrices) and A = I go to serial kernels with the cell's exact step semantics;
@@ -164,6 +164,11 @@ int hmm_backward(const float *A, const float *E,
  *     each other, and sequences with more than 16 of them, are redone whole.  Chunks whose operator columns went
  *     through the denormal range (two observations in a row that every path survives at the emission floor only)
  *     count as flagged.
+ *     For 17..64 states (the chunked 32- / 64-state scans) the same certificates are summed per chunk — psi in
+ *     hmm_posterior, the forward cell's births in hmm_forward (log alpha and the log-likelihood alone), the reverse
+ *     cell's in hmm_backward — but a flagged sequence is recomputed WHOLE, there are no windows; a chain whose
+ *     operator columns went through the denormal range, or all met an observation they survive at the emission floor
+ *     only, is marked by the reduce and its sequence recomputed whole as well.
  * hmm_exact_count() reports how many of the last call's sequences took the serial kernels.
  */
 int hmm_posterior(const float *A, const float *pi, const float *E,
@@ -171,7 +176,7 @@ int hmm_posterior(const float *A, const float *pi, const float *E,
                   float *out, double *loglik,
                   void *workspace, size_t workspace_bytes, void *stream);
 
-/* Diagnostics of the routing above: reads, from the workspace of a finished q <= 16 call (the
+/* Diagnostics of the routing above: reads, from the workspace of a finished q <= 64 call (the
  * caller synchronises first), how many of its k*b sequences were served by the serial exact-clamp
  * kernels.  `op` and the shape are those of the call.  Returns the count or a negative error. */
 long long hmm_exact_count(int op, int k, int b, int L, int q, const void *workspace, size_t workspace_bytes);

@@ -12,7 +12,7 @@ from hmm_layer_amd.gene_pred_hmm_transitioner import GenePredMultiHMMTransitione
 from oracle import build as obuild
 from oracle import textbook
 
-from test_engine_gpu import check_all, dev, rand_model
+from test_engine_gpu import assert_log_close_in_probability_space, check_all, dev, rand_model
 
 pytestmark = pytest.mark.gpu
 
@@ -108,10 +108,20 @@ def test_three_models_in_one_call_sparse_dense_and_reducible(golden):
     assert np.array_equal(scan[0][[0, 1, 3]], out[0][[0, 1, 3]])              # unflagged sequences: untouched
     assert np.abs(scan[0][2] - out[0][2]).max() > 1e-4                       # what the routing repaired
     _, ll2 = engine.forward(dev(A), dev(pi), dev(E), want_log_alpha=False)
+    assert engine.exact_count(engine.OP_LOGLIK, (3, b, L, q)) == 1 + b
     ll2 = ll2.cpu().numpy()
-    ok = np.ones((3, b), bool)
-    ok[0, 2] = False                                       # (the log-likelihood entry point routes per model only)
-    assert np.all(np.abs(ll2 - ll)[ok] <= 1e-6 * np.abs(ll)[ok] + 2e-4)
+    assert np.all(np.abs(ll2 - ll) <= 1e-6 * np.abs(ll) + 2e-4)
+    # the flagged sequence through every one-directional entry point, against the fp64 oracle
+    la64, ll64 = textbook.log_alpha(A0, pi0, E[0, 2:3])
+    lb64 = textbook.log_beta(A0, E[0, 2:3])
+    la, ll3 = engine.forward(dev(A), dev(pi), dev(E))
+    assert engine.exact_count(engine.OP_FORWARD, (3, b, L, q)) == 1 + b
+    lb = engine.backward(dev(A), dev(E))
+    assert engine.exact_count(engine.OP_BACKWARD, (3, b, L, q)) == 1 + b
+    assert_log_close_in_probability_space(la.cpu().numpy()[0, 2:3], la64, "log alpha")
+    assert_log_close_in_probability_space(lb.cpu().numpy()[0, 2:3], lb64, "log beta")
+    for x in (ll2[0, 2:3], ll3.cpu().numpy()[0, 2:3]):
+        assert np.all(np.abs(x - ll64) <= 1e-6 * np.abs(ll64) + 2e-4), (x, ll64)
 
 
 def test_two_copy_model_at_the_reference_test_size():

@@ -9,8 +9,9 @@ import torch
 from hmm_layer_amd import engine
 from hmm_layer_amd.gene_pred_hmm_transitioner import GenePredMultiHMMTransitioner
 from oracle import build as obuild
+from oracle import textbook
 
-from test_engine_gpu import dev, rand_model
+from test_engine_gpu import assert_log_close_in_probability_space, dev, rand_model
 from test_scan32_gpu import check, post
 
 pytestmark = pytest.mark.gpu
@@ -83,6 +84,19 @@ def test_routing_per_model_per_sequence_and_by_batch_size():
     scan = scan.cpu().numpy()
     assert np.array_equal(scan[0][[0, 2]], out[0][[0, 2]])
     assert np.abs(scan[0][1] - out[0][1]).max() > 1e-4
+    # the flagged sequence through every one-directional entry point, against the fp64 oracle
+    la64, ll64 = textbook.log_alpha(A0, pi0, E[0, 1:2])
+    lb64 = textbook.log_beta(A0, E[0, 1:2])
+    la, lla = engine.forward(dev(A), dev(pi), dev(E))
+    assert engine.exact_count(engine.OP_FORWARD, (2, b, L, q)) == 1 + b
+    _, llo = engine.forward(dev(A), dev(pi), dev(E), want_log_alpha=False)
+    assert engine.exact_count(engine.OP_LOGLIK, (2, b, L, q)) == 1 + b
+    lb = engine.backward(dev(A), dev(E))
+    assert engine.exact_count(engine.OP_BACKWARD, (2, b, L, q)) == 1 + b
+    assert_log_close_in_probability_space(la.cpu().numpy()[0, 1:2], la64, "log alpha")
+    assert_log_close_in_probability_space(lb.cpu().numpy()[0, 1:2], lb64, "log beta")
+    for x in (lla.cpu().numpy()[0, 1:2], llo.cpu().numpy()[0, 1:2]):
+        assert np.all(np.abs(x - ll64) <= 1e-6 * np.abs(ll64) + 2e-4), (x, ll64)
     # above the batch limit and below the length limit: the serial kernels, same answers
     A0, pi0 = gene_k(3)
     for bb, LL in ((100, 300), (2, 100)):
