@@ -2,7 +2,9 @@
 docstring, hmm_layer/MsaHmmCell.py:13; learnMSA, which it ports, has a Viterbi module of this name).
 
 ``viterbi(inputs, cell)`` materialises log A, log pi and log E exactly as the layer does for the
-forward-backward engine and makes one ``hmm_viterbi`` call (include/hmm_engine.h)."""
+forward-backward engine and makes one Viterbi call (include/hmm_engine.h): ``hmm_viterbi`` for up to 64
+states, ``hmm_viterbi_large`` above — every cell the layer serves, up to 4096 states (e.g. the many-copy
+gene models and profile HMMs)."""
 import torch
 
 from . import engine

@@ -19,6 +19,7 @@ EPS = 1e-16
 ABI_VERSION = 3
 # tuning / test options (include/hmm_engine.h: HMM_OPT_*, HMM_EXACT_*)
 OPT_CHUNK, OPT_FORCE_DENSE, OPT_SCAN2, OPT_GROUPS, OPT_EXACT, OPT_PGCHUNK, OPT_VGROUPS = 0, 1, 2, 3, 4, 5, 6
+OPT_VLARGE = 7          # viterbi_large: 0 = by q, 1 = per-sequence walk, 2 = per-position tiles
 EXACT_AUTO, EXACT_OFF, EXACT_ALWAYS, EXACT_ALWAYS_NARROW = 0, 1, 2, 3
 
 _lib = None
@@ -85,6 +86,12 @@ def lib():
     L.hmm_viterbi_workspace_bytes.argtypes = [c_i] * 4
     L.hmm_viterbi.restype = c_i
     L.hmm_viterbi.argtypes = [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_sz, c_p]
+    if hasattr(L, "hmm_viterbi_large"):
+        L.hmm_viterbi_large_max_states.restype = c_i
+        L.hmm_viterbi_large_workspace_bytes.restype = c_sz
+        L.hmm_viterbi_large_workspace_bytes.argtypes = [c_i] * 4
+        L.hmm_viterbi_large.restype = c_i
+        L.hmm_viterbi_large.argtypes = L.hmm_viterbi.argtypes
     L.hmm_gene_emissions.restype = c_i
     L.hmm_gene_emissions.argtypes = [c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_f, c_f, c_i, c_p, c_p]
     L.hmm_profile_create.restype = c_p
@@ -176,7 +183,7 @@ def largeq_tile_cols(b, q):
 
 def set_option(option, value):
     """Sets a process-wide tuning / test option (OPT_*); returns the previous value."""
-    if not 0 <= int(option) <= OPT_VGROUPS:
+    if not 0 <= int(option) <= OPT_VLARGE:
         raise ValueError("unknown option %r" % (option,))
     return lib().hmm_set_option(int(option), int(value))
 
@@ -380,12 +387,13 @@ def viterbi(logA, logpi, logE):
     """Most probable state paths.  logA (k,q,q), logpi (k,q), logE (k,b,L,q) fp32 log-probabilities
     (-inf allowed: anything below -1024 counts as -1024).  -> (path (k,b,L) int32, score (k,b) fp64).
     Scores are Q16 fixed point, so the result is bit-identical to the serial recursion
-    (oracle/viterbi.py); ties take the lowest state index."""
+    (oracle/viterbi.py); ties take the lowest state index.  q <= 64 runs hmm_viterbi, larger models
+    viterbi_large (hmm_viterbi_large)."""
     logA, logpi, logE = _dev(logA, "logA"), _dev(logpi, "logpi"), _dev(logE, "logE")
     logA, logpi, dims = _shapes(logA, logE, logpi)
     k, b, L, q = dims
     if q > lib().hmm_viterbi_max_states():
-        raise ValueError("viterbi covers q <= %d states, got %d" % (lib().hmm_viterbi_max_states(), q))
+        return viterbi_large(logA, logpi, logE)
     with torch.cuda.device(logE.device):
         need = lib().hmm_viterbi_workspace_bytes(*dims)
         key = (logE.device.index, torch.cuda.current_stream(logE.device).cuda_stream, "viterbi")
@@ -398,6 +406,31 @@ def viterbi(logA, logpi, logE):
         _check(lib().hmm_viterbi(logA.data_ptr(), logpi.data_ptr(), logE.data_ptr(), *dims,
                                  path.data_ptr(), score.data_ptr(), ws.data_ptr(), ws.numel(),
                                  _stream(logE.device)))
+    return path, score
+
+
+def viterbi_large(logA, logpi, logE):
+    """viterbi() through hmm_viterbi_large, for any 1 <= q <= 4096 (same arguments, results and semantics;
+    the walk / tile evaluation is chosen by q or by OPT_VLARGE)."""
+    logA, logpi, logE = _dev(logA, "logA"), _dev(logpi, "logpi"), _dev(logE, "logE")
+    logA, logpi, dims = _shapes(logA, logE, logpi)
+    k, b, L, q = dims
+    if not hasattr(lib(), "hmm_viterbi_large"):
+        raise EngineError("the engine library predates hmm_viterbi_large: rebuild it")
+    if q > lib().hmm_viterbi_large_max_states():
+        raise ValueError("viterbi_large covers q <= %d states, got %d" % (lib().hmm_viterbi_large_max_states(), q))
+    with torch.cuda.device(logE.device):
+        need = lib().hmm_viterbi_large_workspace_bytes(*dims)
+        key = (logE.device.index, torch.cuda.current_stream(logE.device).cuda_stream, "viterbi_large")
+        ws = _workspaces.get(key)
+        if ws is None or ws.numel() < need:
+            ws = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=logE.device)
+            _workspaces[key] = ws
+        path = torch.empty((k, b, L), dtype=torch.int32, device=logE.device)
+        score = torch.empty((k, b), dtype=torch.float64, device=logE.device)
+        _check(lib().hmm_viterbi_large(logA.data_ptr(), logpi.data_ptr(), logE.data_ptr(), *dims,
+                                       path.data_ptr(), score.data_ptr(), ws.data_ptr(), ws.numel(),
+                                       _stream(logE.device)))
     return path, score
 
 

@@ -194,8 +194,10 @@ class GenePredHMMEmitter(SimpleGenePredHMMEmitter):
 
     # -- fused inference path (HIP kernel hmm_gene_emissions) ---------------------------------
     def can_fuse(self, inputs):
+        # (the fused kernel serves up to 64 states; larger models, e.g. five or more copies, take forward())
         return (inputs.is_cuda and inputs.shape[0] == 1 and self.num_models == 1
-                and not self.trainable_nucleotides_at_exons and self.built)
+                and not self.trainable_nucleotides_at_exons and self.built
+                and self.num_states <= 64)
 
     def state_tables(self, device):
         """(state -> kernel row, state -> codon-table row or -1) as int32 tensors."""

@@ -80,7 +80,8 @@ int hmm_abi_version(void);
 #define HMM_OPT_EXACT        4   /* HMM_EXACT_*: routing to the serial exact-clamp kernels (q <= 16)        */
 #define HMM_OPT_PGCHUNK      5   /* hmm_posterior_grad in chunks: 0 never, 1 when it pays (default), 2 always  */
 #define HMM_OPT_VGROUPS      6   /* hmm_viterbi: batch groups pipelined on an internal stream; 0 = chosen per shape, 1 = off */
-#define HMM_OPT_COUNT        7
+#define HMM_OPT_VLARGE       7   /* hmm_viterbi_large: 0 = by q (default), 1 = per-sequence walk, 2 = per-position tiles */
+#define HMM_OPT_COUNT        8
 #define HMM_EXACT_AUTO    0      /* decided on the device (see hmm_posterior)                               */
 #define HMM_EXACT_OFF     1      /* always the chunked scan                                                 */
 #define HMM_EXACT_ALWAYS  2      /* always the serial kernels                                               */
@@ -96,7 +97,8 @@ int hmm_get_option(int option);
  * sequence — with a SPARSE step (each lane gathers its own predecessors / successors) when no state of the model
  * has more than 8 of either, e.g. the multi-copy gene models; decided per model on the device, HMM_OPT_FORCE_DENSE = 1
  * forces the all-candidates step.  Zero entries of A are exact zeros in both steps; the two differ in rounding order only.
- * hmm_viterbi covers q <= hmm_viterbi_max_states() (64), hmm_loglik_grad q <= hmm_grad_max_states() (64). */
+ * hmm_viterbi covers q <= hmm_viterbi_max_states() (64) and hmm_viterbi_large every q up to
+ * hmm_viterbi_large_max_states() (4096); hmm_loglik_grad covers q <= hmm_grad_max_states() (64). */
 int hmm_max_states(void);
 int hmm_scan_max_states(void);
 int hmm_viterbi_max_states(void);
@@ -215,6 +217,26 @@ int hmm_viterbi(const float *logA, const float *logpi, const float *logE,
                 int k, int b, int L, int q,
                 int32_t *path, double *score,
                 void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Viterbi for 1 <= q <= hmm_viterbi_large_max_states() (4096): the same arguments, layouts, error codes and
+ * Q16 semantics as hmm_viterbi (bit-identical paths and scores wherever both run).  Two evaluations, chosen by
+ * HMM_OPT_VLARGE (0: by q — the walk up to 128 states, tiles above; 1: walk, q <= 1024; 2: tiles):
+ *   per-sequence walk   one workgroup per sequence, lane = state; a model whose states have at most 8
+ *                       explicit predecessors (entries above the matrix minimum) is stepped sparsely, decided
+ *                       per model on the device (HMM_OPT_FORCE_DENSE = 1 forces the all-candidates step);
+ *   per-position tiles  one launch per position over the whole batch: rows = sequences, columns = destination
+ *                       states, K = source states, integer max-plus with packed (value, index) keys.
+ * Workspace: 2*k*b*L*q bytes of 16-bit backpointers plus O(k*b*q + k*q) (hmm_viterbi_large_workspace_bytes is
+ * exactly what the call uses, whichever evaluation runs); every offset into logE, path and the backpointers is
+ * 64-bit.  Runs on `stream` only, no host synchronisation, capturable into a HIP graph.
+ */
+int hmm_viterbi_large_max_states(void);
+size_t hmm_viterbi_large_workspace_bytes(int k, int b, int L, int q);
+int hmm_viterbi_large(const float *logA, const float *logpi, const float *logE,
+                      int k, int b, int L, int q,
+                      int32_t *path, double *score,
+                      void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Fused emission producer of the gene-prediction models.  Replaces GenePredHMMEmitter.forward
