@@ -97,9 +97,11 @@ def _wants_grad(inputs, cell):
 
 def _graph_inputs(inputs, cell, end_hints, training, what="loglik"):
     """A, pi, E built by the cell's torch ops WITH their autograd graph (training)."""
-    limit = engine.lib().hmm_grad_max_states() if what == "loglik" else engine.lib().hmm_posterior_grad_max_states()
+    limit = (engine.lib().hmm_loglik_grad_large_max_states() if what == "loglik"
+             else engine.lib().hmm_posterior_grad_max_states())
     if cell.max_num_states > limit:
-        # fail before the forward pass, not in backward(): the analytic gradients cover q <= 64
+        # fail before the forward pass, not in backward(): the posterior gradients cover q <= 64, the
+        # log-likelihood gradient q <= 4096
         raise ValueError("training through the HIP engine covers models of at most %d states (got %d); "
                          "wrap inference calls in torch.no_grad()" % (limit, cell.max_num_states))
     cell.recurrent_init()

@@ -3,8 +3,8 @@
 The reference trains by letting autograd unroll the Python time loop
 (hmm_layer/BaseRNN.py:217-227 over HmmCell.forward, hmm_layer/MsaHmmCell.py:73-106), which keeps
 every step's tensors alive.  Here the graph holds ONE node: forward = hmm_forward (log-likelihood
-only, reads E once), backward = hmm_loglik_grad (one forward-backward pass producing dA, dpi and
-dE = w * gamma / E).  Nothing per position is saved between the two.
+only, reads E once), backward = hmm_loglik_grad (hmm_loglik_grad_large above 64 states: one
+forward-backward pass producing dA, dpi and dE = w * gamma / E).  Nothing per position is saved between the two.
 """
 import torch
 
@@ -24,7 +24,8 @@ class LogLikelihood(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_loglik):
         A, pi, E = ctx.saved_tensors
-        dA, dpi, dE, _ = engine.loglik_grad(A, pi, E, grad_loglik.to(torch.float32).contiguous(), eps=ctx.eps)
+        grad = engine.loglik_grad if A.shape[-1] <= engine.lib().hmm_grad_max_states() else engine.loglik_grad_large
+        dA, dpi, dE, _ = grad(A, pi, E, grad_loglik.to(torch.float32).contiguous(), eps=ctx.eps)
         need = ctx.needs_input_grad
         return (dA if need[0] else None, dpi.reshape(pi.shape) if need[1] else None,
                 dE if need[2] else None, None)

@@ -89,8 +89,8 @@ static std::once_flag g_opt_once;
 static void opt_seed() {
     static const char *names[HMM_OPT_COUNT] = {"HMM_ENGINE_CHUNK", "HMM_ENGINE_FORCE_DENSE", "HMM_ENGINE_SCAN2",
                                                "HMM_ENGINE_GROUPS", "HMM_ENGINE_EXACT", "HMM_ENGINE_PGCHUNK",
-                                               "HMM_ENGINE_VGROUPS", "HMM_ENGINE_VLARGE"};
-    static const int defaults[HMM_OPT_COUNT] = {0, 0, 1, 1, HMM_EXACT_AUTO, 1, 0, 0};
+                                               "HMM_ENGINE_VGROUPS", "HMM_ENGINE_VLARGE", "HMM_ENGINE_GLARGE"};
+    static const int defaults[HMM_OPT_COUNT] = {0, 0, 1, 1, HMM_EXACT_AUTO, 1, 0, 0, 0};
     for (int i = 0; i < HMM_OPT_COUNT; ++i) {
         const char *v = getenv(names[i]);
         g_opt[i].store(v ? atoi(v) : defaults[i]);
@@ -3377,3 +3377,4 @@ int hmm_loglik_partials(const double *loglik, const float *weights, int k, int b
 #include "hmm_emitter.inc"
 #include "hmm_grad.inc"
 #include "hmm_postgrad.inc"
+#include "hmm_grad_large.inc"

@@ -59,6 +59,8 @@ struct LqStep {
     long long ldp;
     float eps;
     int NT;                      // tile columns of the previous step's partials
+    int sign;                    // park with the sign bit set where the clamp of r was active (acc / S <= eps):
+                                 // the live bit hmm_loglik_grad_large's adjoint recursion reads
 };
 
 template <int NTW, bool BWD, bool COMBINE>
@@ -194,12 +196,16 @@ __global__ __launch_bounds__(LQ_THREADS) void k_lq_gemm(const float *__restrict_
             for (int r = 0; r < 4; ++r) {
                 const int rl = strip * 16 + 4 * g + r, row = m0 + rl;
                 if (row < M && col < q) {
-                    const float rr = fmaxf((acc[j][r] + o[r]) * sinv[rl], fw.eps);
+                    const float rraw = (acc[j][r] + o[r]) * sinv[rl];
+                    const float rr = fmaxf(rraw, fw.eps);
                     const float sf = fmaxf(ev[j][r], fw.eps) * rr;
                     const float val = BWD ? rr : sf;
                     fw.nxt[(long long)row * fw.ldn + col] = sf;
                     if (fw.lg) fw.lg[(long long)row * fw.ldl + col] = logf(val) + slln[rl];
-                    if (fw.park) fw.park[(long long)row * fw.ldp + col] = COMBINE ? val * pv[j][r] : val;
+                    if (fw.park) {
+                        const float pk = COMBINE ? val * pv[j][r] : val;
+                        fw.park[(long long)row * fw.ldp + col] = (fw.sign && !(rraw > fw.eps)) ? -pk : pk;
+                    }
                     rsum[r] += sf;
                 }
             }

@@ -20,6 +20,7 @@ ABI_VERSION = 3
 # tuning / test options (include/hmm_engine.h: HMM_OPT_*, HMM_EXACT_*)
 OPT_CHUNK, OPT_FORCE_DENSE, OPT_SCAN2, OPT_GROUPS, OPT_EXACT, OPT_PGCHUNK, OPT_VGROUPS = 0, 1, 2, 3, 4, 5, 6
 OPT_VLARGE = 7          # viterbi_large: 0 = by q, 1 = per-sequence walk, 2 = per-position tiles
+OPT_GLARGE = 8          # loglik_grad_large: 0 = by q, 1 = per-sequence walk, 2 = per-position GEMMs
 EXACT_AUTO, EXACT_OFF, EXACT_ALWAYS, EXACT_ALWAYS_NARROW = 0, 1, 2, 3
 
 _lib = None
@@ -92,6 +93,12 @@ def lib():
         L.hmm_viterbi_large_workspace_bytes.argtypes = [c_i] * 4
         L.hmm_viterbi_large.restype = c_i
         L.hmm_viterbi_large.argtypes = L.hmm_viterbi.argtypes
+    if hasattr(L, "hmm_loglik_grad_large"):
+        L.hmm_loglik_grad_large_max_states.restype = c_i
+        L.hmm_loglik_grad_large_workspace_bytes.restype = c_sz
+        L.hmm_loglik_grad_large_workspace_bytes.argtypes = [c_i] * 4
+        L.hmm_loglik_grad_large.restype = c_i
+        L.hmm_loglik_grad_large.argtypes = [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]
     L.hmm_gene_emissions.restype = c_i
     L.hmm_gene_emissions.argtypes = [c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_f, c_f, c_i, c_p, c_p]
     L.hmm_profile_create.restype = c_p
@@ -183,7 +190,7 @@ def largeq_tile_cols(b, q):
 
 def set_option(option, value):
     """Sets a process-wide tuning / test option (OPT_*); returns the previous value."""
-    if not 0 <= int(option) <= OPT_VLARGE:
+    if not 0 <= int(option) <= OPT_GLARGE:
         raise ValueError("unknown option %r" % (option,))
     return lib().hmm_set_option(int(option), int(value))
 
@@ -538,6 +545,34 @@ def loglik_grad(A, pi, E, grad_loglik=None, eps=EPS):
                                      grad_loglik.data_ptr() if grad_loglik is not None else None,
                                      dA.data_ptr(), dpi.data_ptr(), dE.data_ptr(), ll.data_ptr(),
                                      ws.data_ptr(), ws.numel(), _stream(E.device)))
+    return dA, dpi, dE, ll
+
+
+def loglik_grad_large(A, pi, E, grad_loglik=None, eps=EPS):
+    """loglik_grad() through hmm_loglik_grad_large, for any 1 <= q <= 4096 (same arguments, results and
+    semantics; the walk / GEMM evaluation is chosen by q or by OPT_GLARGE)."""
+    A, pi, E = _dev(A, "A"), _dev(pi, "pi"), _dev(E, "E")
+    A, pi, dims = _shapes(A, E, pi)
+    k, b, L, q = dims
+    if not hasattr(lib(), "hmm_loglik_grad_large"):
+        raise EngineError("the engine library predates hmm_loglik_grad_large: rebuild it")
+    if q > lib().hmm_loglik_grad_large_max_states():
+        raise ValueError("loglik_grad_large covers q <= %d states, got %d"
+                         % (lib().hmm_loglik_grad_large_max_states(), q))
+    if grad_loglik is not None:
+        grad_loglik = _dev(grad_loglik, "grad_loglik")
+        if tuple(grad_loglik.shape) != (k, b):
+            raise ValueError("grad_loglik must have shape %s" % ((k, b),))
+    with torch.cuda.device(E.device):
+        ws = _workspace(None, dims, E.device, need=lib().hmm_loglik_grad_large_workspace_bytes(*dims))
+        dA = torch.empty((k, q, q), dtype=torch.float32, device=E.device)
+        dpi = torch.empty((k, q), dtype=torch.float32, device=E.device)
+        dE = torch.empty_like(E)
+        ll = torch.empty((k, b), dtype=torch.float64, device=E.device)
+        _check(lib().hmm_loglik_grad_large(A.data_ptr(), pi.data_ptr(), E.data_ptr(), *dims, eps,
+                                           grad_loglik.data_ptr() if grad_loglik is not None else None,
+                                           dA.data_ptr(), dpi.data_ptr(), dE.data_ptr(), ll.data_ptr(),
+                                           ws.data_ptr(), ws.numel(), _stream(E.device)))
     return dA, dpi, dE, ll
 
 

@@ -81,7 +81,8 @@ int hmm_abi_version(void);
 #define HMM_OPT_PGCHUNK      5   /* hmm_posterior_grad in chunks: 0 never, 1 when it pays (default), 2 always  */
 #define HMM_OPT_VGROUPS      6   /* hmm_viterbi: batch groups pipelined on an internal stream; 0 = chosen per shape, 1 = off */
 #define HMM_OPT_VLARGE       7   /* hmm_viterbi_large: 0 = by q (default), 1 = per-sequence walk, 2 = per-position tiles */
-#define HMM_OPT_COUNT        8
+#define HMM_OPT_GLARGE       8   /* hmm_loglik_grad_large: 0 = by q (default), 1 = per-sequence walk, 2 = per-position GEMMs */
+#define HMM_OPT_COUNT        9
 #define HMM_EXACT_AUTO    0      /* decided on the device (see hmm_posterior)                               */
 #define HMM_EXACT_OFF     1      /* always the chunked scan                                                 */
 #define HMM_EXACT_ALWAYS  2      /* always the serial kernels                                               */
@@ -98,7 +99,8 @@ int hmm_get_option(int option);
  * has more than 8 of either, e.g. the multi-copy gene models; decided per model on the device, HMM_OPT_FORCE_DENSE = 1
  * forces the all-candidates step.  Zero entries of A are exact zeros in both steps; the two differ in rounding order only.
  * hmm_viterbi covers q <= hmm_viterbi_max_states() (64) and hmm_viterbi_large every q up to
- * hmm_viterbi_large_max_states() (4096); hmm_loglik_grad covers q <= hmm_grad_max_states() (64). */
+ * hmm_viterbi_large_max_states() (4096); hmm_loglik_grad covers q <= hmm_grad_max_states() (64) and
+ * hmm_loglik_grad_large every q up to hmm_loglik_grad_large_max_states() (4096). */
 int hmm_max_states(void);
 int hmm_scan_max_states(void);
 int hmm_viterbi_max_states(void);
@@ -345,6 +347,28 @@ int hmm_loglik_grad(const float *A, const float *pi, const float *E,
                     int k, int b, int L, int q, float eps, const float *grad_loglik,
                     float *dA, float *dpi, float *dE, double *loglik,
                     void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * The same gradient for any 1 <= q <= hmm_loglik_grad_large_max_states() (4096): arguments, outputs and
+ * clamp semantics exactly those of hmm_loglik_grad (grad_loglik and loglik may be NULL).  Two evaluations,
+ * picked by HMM_OPT_GLARGE (0: by q — the walk up to 128 states, the GEMMs above; 1: walk; 2: GEMMs):
+ *   walk   one workgroup per sequence, ceil(q/64) waves, lane = state, A staged in LDS; a forward sweep parks
+ *          the unnormalised forward vector (sign bit = the predicted state was clamped) in dE, the backward
+ *          sweep overwrites it with w gamma / E and sums row i of xi / A in lane i.  Serves q <= 128: forcing it
+ *          above returns HMM_ERR_BAD_ARGUMENT.
+ *   GEMMs  per position one f32-MFMA GEMM of the forward recursion, one of the adjoint recursion with an
+ *          elementwise pass for dE, and one (q x b)(b x q) product for dA, added into an fp64 accumulator.
+ * The workspace does not depend on L.  Sums run in a fixed order (fp32 within a sequence or a tile, fp64 across
+ * sequences and positions): repeated calls return bit-identical results.  Everything runs in order on `stream`.
+ * Argument checks, before any HIP call: bad shape -1, q > 4096 -2, a NULL A / pi / E / dA / dpi / dE / workspace
+ * -3, a small or misaligned (256 bytes) workspace -4.  workspace_bytes() returns 0 for an unsupported q.
+ */
+int hmm_loglik_grad_large_max_states(void);
+size_t hmm_loglik_grad_large_workspace_bytes(int k, int b, int L, int q);
+int hmm_loglik_grad_large(const float *A, const float *pi, const float *E,
+                          int k, int b, int L, int q, float eps, const float *grad_loglik,
+                          float *dA, float *dpi, float *dE, double *loglik,
+                          void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Gradient of a loss on the state posteriors (training through state_posterior_log_probs).  The

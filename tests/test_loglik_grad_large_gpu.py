@@ -1,0 +1,307 @@
+"""hmm_loglik_grad_large (engine.loglik_grad_large, q up to 4096) against the fp64 Baum-Welch oracle, under both
+evaluations (HMM_OPT_GLARGE = 1 per-sequence walk where q <= 128, 2 per-position GEMMs) and the default (0).
+
+Yardsticks, as in tests/test_grad_gpu.py: oracle.textbook.loglik_grad in fp64.  |g - g64| <= 2e-4 * max|g64| per
+tensor for dA and dpi (sums of up to b*L fp32 terms per entry); dE entries are single ratios, compared at 2e-5
+relative to the tensor's largest entry plus 1e-4 relative per entry; the log-likelihood to 1e-6 relative + 2e-4.
+Exception, stated: dA entries of ABSENT edges (A[i][j] == 0) of states sitting on the eps floor are decided by the
+steps at which the cell's clamp of the predicted state (MsaHmmCell.py:88) is active; fp32 recursions can cross that
+floor at other steps than the fp64 loop.  They are bounded by the size of the clamp effect itself:
+|g - g64| <= |g64(no clamp mask) - g64| + 5e-3 * max|g64|.  The reference never uses these entries: its A is
+scattered from per-edge parameters, structural zeros are constants."""
+import numpy as np
+import pytest
+import torch
+
+from hmm_layer_amd import engine
+from oracle import ref_cell, textbook
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+WALK_MAX = 128
+CODONS = dict(start_codons=[("ATG", 1.)], stop_codons=[("TAG", .34), ("TAA", .33), ("TGA", .33)],
+              intron_begin_pattern=[("NGT", .99), ("NGC", .005), ("NAT", .005)],
+              intron_end_pattern=[("AGN", .99), ("ACN", .01)])
+
+
+def dev(x):
+    return torch.as_tensor(np.asarray(x), dtype=torch.float32, device=DEV)
+
+
+def routes(q):
+    return (0, 1, 2) if q <= WALK_MAX else (0, 2)
+
+
+def run(A, pi, E, w=None, route=0, fn=None):
+    """A (k,q,q), pi (k,q), E (k,b,L,q) numpy -> numpy dA, dpi, dE, ll under OPT_GLARGE = route."""
+    fn = fn or engine.loglik_grad_large
+    with engine.option(engine.OPT_GLARGE, route):
+        out = fn(dev(A), dev(pi), dev(E), None if w is None else dev(w))
+        torch.cuda.synchronize()
+    return [t.cpu().numpy() for t in out]
+
+
+def check_model(got, A, pi, E, w, tag, check_dA=True):
+    """got = (dA, dpi, dE, ll) of ONE model (numpy); E (b,L,q) its emissions, w (b,) or None."""
+    dA, dpi, dE, ll = got
+    rA, rpi, rE = textbook.loglik_grad(A, pi, E, w)
+    assert np.isfinite(dA).all() and np.isfinite(dE).all() and np.isfinite(dpi).all(), tag
+    if check_dA:
+        rU = textbook.loglik_grad(A, pi, E, w, clamp_adjoint=False)[0]
+        tolA = np.where(A > 0, 2e-4 * np.abs(rA).max(), np.abs(rU - rA) + 5e-3 * np.abs(rA).max())
+        assert np.all(np.abs(dA - rA) <= tolA), (tag, np.abs(dA - rA).max(), np.abs(rA).max())
+        assert np.abs(dpi - rpi).max() <= 2e-4 * np.abs(rpi).max(), (tag, np.abs(dpi - rpi).max())
+    assert np.all(np.abs(dE - rE) <= 2e-5 * np.abs(rE).max() + 1e-4 * np.abs(rE)), \
+        (tag, np.abs(dE - rE).max(), np.abs(rE).max())
+    ll64 = textbook.loglik(A, pi, E)
+    assert np.all(np.abs(ll - ll64) <= 1e-6 * np.abs(ll64) + 2e-4), (tag, np.abs(ll - ll64).max())
+
+
+def check_all(A, pi, E, w=None, tag=""):
+    """Every route that applies, each model against the oracle; returns the results by route."""
+    k = E.shape[0]
+    res = {}
+    for r in routes(E.shape[-1]):
+        res[r] = run(A, pi, E, w, r)
+        for m in range(k):
+            check_model([x[m] for x in res[r]], A[m], pi[m], E[m], None if w is None else w[m], "%s route=%d m=%d" % (tag, r, m))
+    return res
+
+
+def rand_model(rng, q, sparse=False, dead=0, tiny_pi=0):
+    """Row-stochastic A; `dead` states nothing enters (their column is zero); `tiny_pi` entries of pi below eps."""
+    A = rng.random((q, q)) ** 2 + 1e-2
+    if sparse:
+        A *= rng.random((q, q)) < 0.1
+        A += np.eye(q) * 0.3
+        A[np.arange(q), (np.arange(q) + 1) % q] += 0.2
+    if dead:
+        A[:, q - dead:] = 0.0
+        A[q - dead:, q - dead:] = np.eye(dead) * 0.5
+        A[q - dead:, 0] += 0.5
+    A /= A.sum(-1, keepdims=True)
+    pi = rng.random(q) + 0.1
+    if tiny_pi:
+        pi[rng.choice(q, tiny_pi, replace=False)] = 1e-20
+    pi /= pi.sum()
+    return A.astype(np.float32), pi.astype(np.float32)
+
+
+def rand_E(rng, k, b, L, q, holes=True):
+    E = (rng.random((k, b, L, q)) * 0.9 + 0.05).astype(np.float32)
+    if holes:
+        E[..., ::5, q // 3] = 0.0                        # emissions below eps: no gradient there
+        E[..., 1::7, q // 2] = 1e-18
+    return E
+
+
+def five_copy():
+    from hmm_layer_amd.gene_pred_hmm_transitioner import GenePredMultiHMMTransitioner
+    tr = GenePredMultiHMMTransitioner(k=5, initial_exon_len=200, initial_intron_len=4500, initial_ir_len=10000)
+    with torch.no_grad():
+        A = tr.make_A()[0].numpy().astype(np.float32)
+        pi = tr.make_initial_distribution().reshape(-1).numpy().astype(np.float32)
+    return A, pi
+
+
+@pytest.mark.parametrize("q,kind", [(65, "dense"), (100, "sparse"), (127, "dense"), (128, "sparse"), (129, "dense"),
+                                    (257, "sparse")])
+def test_models_against_the_oracle(q, kind):
+    rng = np.random.default_rng(q)
+    A, pi = rand_model(rng, q, sparse=kind == "sparse", dead=3, tiny_pi=2)
+    E = rand_E(rng, 1, 3, 40, q)
+    w = np.array([[1.0, -0.5, 2.0]], dtype=np.float32)
+    check_all(A[None], pi[None], E, w, "q=%d %s" % (q, kind))
+
+
+def test_five_copy_gene_model():
+    rng = np.random.default_rng(71)
+    A, pi = five_copy()
+    assert A.shape == (71, 71)
+    E = rand_E(rng, 1, 4, 300, 71)
+    check_all(A[None], pi[None], E, None, "five-copy")
+
+
+def test_two_models_weights_and_short_sequences():
+    """k = 2 with separate matrices, grad_loglik with zeros and negative values, L = 1..7 (L = 1: dA = 0)."""
+    rng = np.random.default_rng(5)
+    q = 90
+    m1, m2 = rand_model(rng, q, dead=2), rand_model(rng, q, sparse=True, tiny_pi=3)
+    A, pi = np.stack([m1[0], m2[0]]), np.stack([m1[1], m2[1]])
+    w = np.array([[0.0, -1.5, 0.7, 2.0, 0.0], [1.0, 0.0, -0.3, 0.5, 3.0]], dtype=np.float32)
+    for L in range(1, 8):
+        E = rand_E(rng, 2, 5, L, q)
+        res = check_all(A, pi, E, w, "L=%d" % L)
+        if L == 1:
+            for r in res.values():
+                assert np.all(r[0] == 0.0)
+        for r in res.values():                           # zero weight: no gradient from that sequence
+            assert np.all(r[2][0, 0] == 0.0) and np.all(r[2][1, 1] == 0.0)
+
+
+@pytest.mark.parametrize("q", [15, 29, 43, 64])
+def test_equals_hmm_loglik_grad_up_to_64_states(q):
+    rng = np.random.default_rng(100 + q)
+    A, pi = rand_model(rng, q, sparse=q % 2 == 1)
+    E = rand_E(rng, 1, 4, 120, q)
+    w = np.array([[1.0, 0.5, -2.0, 1.5]], dtype=np.float32)
+    old = run(A[None], pi[None], E, w, fn=engine.loglik_grad)
+    for r in (0, 1, 2):
+        got = run(A[None], pi[None], E, w, r)
+        tol = [2e-4 * np.abs(old[0]).max(), 2e-4 * np.abs(old[1]).max()]
+        assert np.all(np.where(A[None] > 0, np.abs(got[0] - old[0]), 0.0) <= tol[0]), (q, r)   # absent edges: oracle
+        assert np.abs(got[1] - old[1]).max() <= tol[1], (q, r)
+        assert np.all(np.abs(got[2] - old[2]) <= 2e-5 * np.abs(old[2]).max() + 1e-4 * np.abs(old[2])), (q, r)
+        check_model([x[0] for x in got], A, pi, E[0], w[0], "q=%d route=%d" % (q, r))
+        # the log-likelihood is the forward pass's
+        ll_fwd = engine.forward(dev(A[None]), dev(pi[None]), dev(E), want_log_alpha=False)[1].cpu().numpy()
+        assert np.all(np.abs(got[3] - ll_fwd) <= 1e-6 * np.abs(ll_fwd) + 2e-4), (q, r)
+
+
+def test_loglik_matches_the_forward_pass_above_64_states():
+    rng = np.random.default_rng(9)
+    for q in (71, 200):
+        A, pi = rand_model(rng, q)
+        E = rand_E(rng, 1, 3, 50, q, holes=False)
+        ll_fwd = engine.forward(dev(A[None]), dev(pi[None]), dev(E), want_log_alpha=False)[1].cpu().numpy()
+        for r in routes(q):
+            ll = run(A[None], pi[None], E, None, r)[3]
+            assert np.all(np.abs(ll - ll_fwd) <= 1e-6 * np.abs(ll_fwd) + 2e-4), (q, r)
+
+
+def test_config5_shape_1027_states():
+    """BASELINE config 5's model size and batch (q = 1027, b = 1024), short sequences: the full dA and dpi,
+    and sampled sequences' dE and log-likelihoods."""
+    rng = np.random.default_rng(1027)
+    q, b, L = 1027, 1024, 3
+    A, pi = rand_model(rng, q, sparse=True, dead=4, tiny_pi=5)
+    E = rand_E(rng, 1, b, L, q)
+    got = run(A[None], pi[None], E)
+    check_model([x[0] for x in got], A, pi, E[0], None, "q=1027")
+
+
+def test_walk_and_gemms_at_the_switch_point():
+    """q = 128 is the last walk default; both evaluations agree closely with each other there."""
+    rng = np.random.default_rng(128)
+    A, pi = rand_model(rng, 128, dead=2)
+    E = rand_E(rng, 1, 6, 64, 128)
+    a, g = run(A[None], pi[None], E, None, 1), run(A[None], pi[None], E, None, 2)
+    d0 = run(A[None], pi[None], E, None, 0)
+    for x, z in zip(a, d0):
+        assert np.array_equal(x, z)                       # the default at 128 is the walk
+    # absent edges into floor states follow each recursion's own clamp pattern (module docstring)
+    assert np.abs(np.where(A > 0, a[0][0] - g[0][0], 0.0)).max() <= 2e-4 * np.abs(a[0]).max()
+    for x, y in zip(a[1:], g[1:]):
+        assert np.abs(x - y).max() <= 1e-4 * np.abs(x).max() + 1e-7
+
+
+def test_offsets_beyond_2_to_31():
+    """k*b*L*q > 2^31 elements (dE beyond 8 GB): sampled sequences, the last included, under both evaluations."""
+    k, b, L, q = 1, 1024, 30000, 71
+    assert k * b * L * q > 2 ** 31
+    A, pi = five_copy()
+    g = torch.Generator(device=DEV).manual_seed(9)
+    E = torch.rand((k, b, L, q), generator=g, device=DEV) * 0.9 + 0.05
+    rows = [0, 517, b - 1]
+    Es = E[0, rows].cpu().numpy()
+    rE = textbook.loglik_grad(A, pi, Es)[2]
+    ll64 = textbook.loglik(A, pi, Es)
+    for r in (1, 2):
+        with engine.option(engine.OPT_GLARGE, r):
+            dA, dpi, dE, ll = engine.loglik_grad_large(dev(A[None]), dev(pi[None]), E)
+            torch.cuda.synchronize()
+        assert bool(torch.isfinite(dA).all()) and bool(torch.isfinite(dpi).all())
+        assert bool(torch.isfinite(dE[0, -1]).all()) and bool(torch.isfinite(dE[0, :, -1]).all())
+        got = dE[0, rows].cpu().numpy()
+        assert np.all(np.abs(got - rE) <= 2e-5 * np.abs(rE).max() + 1e-4 * np.abs(rE)), (r, np.abs(got - rE).max())
+        llr = ll[0, rows].cpu().numpy()
+        assert np.all(np.abs(llr - ll64) <= 1e-6 * np.abs(ll64) + 2e-4), r
+        del dA, dpi, dE, ll
+    del E
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("q,route", [(71, 1), (71, 2), (300, 2)])
+def test_deterministic(q, route):
+    rng = np.random.default_rng(q + route)
+    A, pi = rand_model(rng, q, sparse=True, dead=2)
+    E = rand_E(rng, 1, 200, 50, q)
+    w = (rng.random((1, 200)) - 0.3).astype(np.float32)
+    a = run(A[None], pi[None], E, w, route)
+    b = run(A[None], pi[None], E, w, route)
+    for x, y in zip(a, b):
+        assert np.array_equal(x, y)
+
+
+def test_routing_and_limits():
+    A, pi = rand_model(np.random.default_rng(0), 129)
+    E = rand_E(np.random.default_rng(1), 1, 2, 5, 129)
+    with engine.option(engine.OPT_GLARGE, 1):
+        with pytest.raises(engine.EngineError):          # the forced walk above 128 states: HMM_ERR_BAD_ARGUMENT
+            engine.loglik_grad_large(dev(A[None]), dev(pi[None]), dev(E))
+    with pytest.raises(ValueError):                      # the old entry point keeps its limit
+        engine.loglik_grad(torch.eye(70, device=DEV)[None], torch.full((1, 70), 1 / 70, device=DEV),
+                           torch.rand(1, 2, 8, 70, device=DEV))
+    with pytest.raises(ValueError):
+        engine.loglik_grad_large(torch.zeros(1, 4097, 4097, device=DEV), torch.zeros(1, 4097, device=DEV),
+                                 torch.zeros(1, 1, 1, 4097, device=DEV))
+
+
+def test_five_copy_gene_model_is_trainable():
+    """loss.backward() through the 71-state model (the layer's log-likelihood path): the transition kernel's gradient
+    against autograd through the restated reference loop on the same A, pi, E."""
+    from hmm_layer_amd.MsaHmmCell import HmmCell
+    from hmm_layer_amd.MsaHMMLayer import MsaHmmLayer
+    from hmm_layer_amd.gene_pred_hmm_emitter import GenePredHMMEmitter
+    from hmm_layer_amd.gene_pred_hmm_transitioner import GenePredMultiHMMTransitioner
+    b, L = 2, 160
+    g = torch.Generator().manual_seed(13)
+    cls = torch.softmax(2 * torch.randn((1, b, L, 15), generator=g), -1)
+    nuc = torch.nn.functional.one_hot(torch.randint(0, 4, (1, b, L), generator=g), 5).float()
+    x = torch.cat([cls, nuc], -1).to(DEV)
+    em = GenePredHMMEmitter(**CODONS, num_copies=5)
+    em.build((1, b, L, 15))
+    tr = GenePredMultiHMMTransitioner(k=5, initial_exon_len=200, initial_intron_len=4500, initial_ir_len=10000)
+    cell = HmmCell([71], 15, em, tr).to(DEV)
+    layer = MsaHmmLayer(cell, use_prior=False)
+    layer.build(x.shape)
+    loglik, mean = layer(x, training=True)
+    (-mean).backward()
+    gk = cell.transitioner.transition_kernel.grad
+    assert gk is not None and bool(torch.isfinite(gk).all()) and float(gk.abs().max()) > 0
+    cell.recurrent_init()
+    E = cell.emission_probs(x, end_hints=None, training=True).to(torch.float32)
+    A, pi = cell.A, cell.init_dist.reshape(1, 71)
+    gl = torch.full((1, b), -1.0 / b)
+    dA, dpi, dE, ll_ref = ref_cell.loglik_grad(A.detach().cpu(), pi.detach().cpu(), E.detach().cpu(), gl)
+    want = torch.autograd.grad([A, E], [cell.transitioner.transition_kernel], [dA.to(DEV), dE.to(DEV)])[0]
+    assert float((gk - want).abs().max()) <= 5e-4 * float(want.abs().max()) + 1e-7
+    assert np.abs(loglik.detach().cpu().numpy() - ll_ref.numpy()).max() <= 2e-3
+
+
+@pytest.mark.parametrize("q", [70, 150])
+def test_clamped_predicted_state_passes_nothing_back(q):
+    """A state on the eps floor at every position, entered by a PRESENT edge of weight 1e-20 and emitting with
+    probability 1: the cell clamps its predicted mass at every step, so autograd passes nothing through it, and
+    dA of that edge is 0.  Without the live-bit mask the same entry would exceed every other entry of dA."""
+    rng = np.random.default_rng(q)
+    D = q - 1
+    A = rng.random((q, q)) ** 2 + 1e-2
+    A[:, D] = 0.0
+    A[0, D] = 1e-20
+    A[D, :] = 0.0
+    A[D, 0] = 1.0
+    A /= A.sum(-1, keepdims=True)
+    pi = rng.random(q) + 0.1
+    pi[D] = 0.0
+    pi /= pi.sum()
+    A, pi = A.astype(np.float32), pi.astype(np.float32)
+    E = (rng.random((1, 3, 60, q)) * 0.9 + 0.05).astype(np.float32)
+    E[..., D] = 1.0
+    rA = textbook.loglik_grad(A, pi, E[0])[0]
+    rU = textbook.loglik_grad(A, pi, E[0], clamp_adjoint=False)[0]
+    assert abs(rA[0, D]) == 0.0 and abs(rU[0, D]) > np.abs(rA).max()        # the mask decides this entry
+    for r in routes(q):
+        got = run(A[None], pi[None], E, None, r)
+        check_model([x[0] for x in got], A, pi, E[0], None, "floor q=%d route=%d" % (q, r))
+        assert abs(got[0][0, 0, D]) <= 2e-4 * np.abs(rA).max()
