@@ -20,8 +20,8 @@ parameter (or the input) requires grad, A, pi and E are built by the cell's torc
 graph and the log-likelihood is ONE autograd node (hmm_layer_amd.autograd.LogLikelihood) whose
 backward is the engine's analytic gradient (hmm_loglik_grad) — instead of the reference's
 autograd through the unrolled time loop.  ``state_posterior_log_probs`` is differentiable the same
-way (hmm_posterior_grad), as training through the posteriors needs, including the ``no_loglik``
-variant; forward / backward variables return inference values.
+way (hmm_posterior_grad; hmm_posterior_grad_large above 64 states), as training through the posteriors
+needs, including the ``no_loglik`` variant; forward / backward variables return inference values.
 """
 import torch
 import torch.nn as nn
@@ -98,10 +98,10 @@ def _wants_grad(inputs, cell):
 def _graph_inputs(inputs, cell, end_hints, training, what="loglik"):
     """A, pi, E built by the cell's torch ops WITH their autograd graph (training)."""
     limit = (engine.lib().hmm_loglik_grad_large_max_states() if what == "loglik"
-             else engine.lib().hmm_posterior_grad_max_states())
+             else engine.lib().hmm_posterior_grad_large_max_states())
     if cell.max_num_states > limit:
-        # fail before the forward pass, not in backward(): the posterior gradients cover q <= 64, the
-        # log-likelihood gradient q <= 4096
+        # fail before the forward pass, not in backward(): the log-likelihood and posterior gradients cover
+        # q <= 4096 (hmm_loglik_grad_large, hmm_posterior_grad_large)
         raise ValueError("training through the HIP engine covers models of at most %d states (got %d); "
                          "wrap inference calls in torch.no_grad()" % (limit, cell.max_num_states))
     cell.recurrent_init()

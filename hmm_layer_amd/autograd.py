@@ -39,7 +39,8 @@ def loglik(A, pi, E, eps=engine.EPS):
 class Posterior(torch.autograd.Function):
     """State posteriors (k,b,L,q), probabilities or logs, differentiable in A, pi and E.  Forward =
     hmm_posterior (the chunked kernels), backward = hmm_posterior_grad (its four sweeps per chunk of the
-    scan plan, or over whole sequences where the device-side routing says so) — the reference gets this gradient by autograd through its forward and backward loops
+    scan plan, or over whole sequences where the device-side routing says so; hmm_posterior_grad_large above
+    64 states) — the reference gets this gradient by autograd through its forward and backward loops
     (hmm_layer/MsaHMMLayer.py:422-521 with training=True)."""
 
     @staticmethod
@@ -53,15 +54,17 @@ class Posterior(torch.autograd.Function):
     def backward(ctx, grad_out):
         A, pi, E = ctx.saved_tensors
         grad_out = grad_out.to(torch.float32).contiguous()
+        small = A.shape[-1] <= engine.lib().hmm_posterior_grad_max_states()
+        post = engine.posterior_grad if small else engine.posterior_grad_large
         if ctx.mode == engine.POST_LOG_NO_LL:
             # out = log gamma + loglik (the reference's no_loglik=True): the log-posterior gradient plus the
             # log-likelihood gradient weighted by the per-sequence sum of the upstream gradient
-            dA, dpi, dE = engine.posterior_grad(A, pi, E, grad_out, mode=engine.POST_LOG, eps=ctx.eps)
+            dA, dpi, dE = post(A, pi, E, grad_out, mode=engine.POST_LOG, eps=ctx.eps)
             w = grad_out.sum(dim=(2, 3)).contiguous()
-            dA2, dpi2, dE2, _ = engine.loglik_grad(A, pi, E, w, eps=ctx.eps)
+            dA2, dpi2, dE2, _ = (engine.loglik_grad if small else engine.loglik_grad_large)(A, pi, E, w, eps=ctx.eps)
             dA, dpi, dE = dA + dA2, dpi + dpi2, dE.add_(dE2)
         else:
-            dA, dpi, dE = engine.posterior_grad(A, pi, E, grad_out, mode=ctx.mode, eps=ctx.eps)
+            dA, dpi, dE = post(A, pi, E, grad_out, mode=ctx.mode, eps=ctx.eps)
         need = ctx.needs_input_grad
         return (dA if need[0] else None, dpi.reshape(pi.shape) if need[1] else None, dE if need[2] else None, None, None)
 

@@ -3378,3 +3378,4 @@ int hmm_loglik_partials(const double *loglik, const float *weights, int k, int b
 #include "hmm_grad.inc"
 #include "hmm_postgrad.inc"
 #include "hmm_grad_large.inc"
+#include "hmm_postgrad_large.inc"

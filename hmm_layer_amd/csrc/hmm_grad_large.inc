@@ -56,10 +56,12 @@ __device__ __forceinline__ float gl_wave_sum(float v) {
 
 // ------------------------------------------------------------------ per-sequence walk
 // forward: grid k*b, block NP = 64 ceil(q/64); dynamic LDS As[i][j] = A[i][j] for i < ceil4(q) (zero padded), row
-// stride NP.  Writes signed U_t into dE and the fp64 log-likelihood.
+// stride NP.  Writes signed U_t into dE and the fp64 log-likelihood; Sst (or null) receives the normalisers
+// S_t = sum U_t, [row][t] (hmm_posterior_grad_large).
 __global__ __launch_bounds__(GL_WALK_MAX) void k_gl_walk_fwd(const float *__restrict__ A, const float *__restrict__ pi,
                                                              const float *__restrict__ E, int b, int L, int q, float eps,
-                                                             float *__restrict__ dE, double *__restrict__ ll) {
+                                                             float *__restrict__ dE, double *__restrict__ ll,
+                                                             float *__restrict__ Sst) {
     extern __shared__ float As[];
     __shared__ __attribute__((aligned(16))) float xs[2][GL_WALK_MAX];
     __shared__ float ws[2][2];
@@ -85,6 +87,7 @@ __global__ __launch_bounds__(GL_WALK_MAX) void k_gl_walk_fwd(const float *__rest
             float S = ws[cur][0];
             for (int x = 1; x < nw; ++x) S += ws[cur][x];
             lacc += log((double)S);
+            if (Sst && j == 0) Sst[(size_t)row * L + t - 1] = S;
             float a[4] = {0.f, 0.f, 0.f, 0.f};
             for (int i = 0; i < q4; i += 4) {
                 const f4 xv = *reinterpret_cast<const f4 *>(&xs[cur][i]);
@@ -107,6 +110,7 @@ __global__ __launch_bounds__(GL_WALK_MAX) void k_gl_walk_fwd(const float *__rest
         float S = ws[last][0];
         for (int x = 1; x < nw; ++x) S += ws[last][x];
         ll[row] = lacc + log((double)S);
+        if (Sst) Sst[(size_t)row * L + L - 1] = S;
     }
 }
 
@@ -300,7 +304,7 @@ static void gl_walk(const float *A, const float *pi, const float *E, int k, int 
     const dim3 grid((unsigned)((size_t)k * b));
     const int NP = q <= 64 ? 64 : 128, q4 = (q + 3) & ~3;
     const size_t lds = (size_t)q4 * NP * sizeof(float);
-    hipLaunchKernelGGL(k_gl_walk_fwd, grid, dim3(NP), lds, st, A, pi, E, b, L, q, eps, dE, ll);
+    hipLaunchKernelGGL(k_gl_walk_fwd, grid, dim3(NP), lds, st, A, pi, E, b, L, q, eps, dE, ll, (float *)nullptr);
     if (NP == 64)
         hipLaunchKernelGGL(k_gl_walk_bwd<64>, grid, dim3(64), lds, st, A, E, b, L, q, eps, gw, dE, gpart);
     else

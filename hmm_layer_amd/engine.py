@@ -20,7 +20,7 @@ ABI_VERSION = 3
 # tuning / test options (include/hmm_engine.h: HMM_OPT_*, HMM_EXACT_*)
 OPT_CHUNK, OPT_FORCE_DENSE, OPT_SCAN2, OPT_GROUPS, OPT_EXACT, OPT_PGCHUNK, OPT_VGROUPS = 0, 1, 2, 3, 4, 5, 6
 OPT_VLARGE = 7          # viterbi_large: 0 = by q, 1 = per-sequence walk, 2 = per-position tiles
-OPT_GLARGE = 8          # loglik_grad_large: 0 = by q, 1 = per-sequence walk, 2 = per-position GEMMs
+OPT_GLARGE = 8          # loglik_grad_large, posterior_grad_large: 0 = by q, 1 = per-sequence walk, 2 = per-position GEMMs
 EXACT_AUTO, EXACT_OFF, EXACT_ALWAYS, EXACT_ALWAYS_NARROW = 0, 1, 2, 3
 
 _lib = None
@@ -99,6 +99,12 @@ def lib():
         L.hmm_loglik_grad_large_workspace_bytes.argtypes = [c_i] * 4
         L.hmm_loglik_grad_large.restype = c_i
         L.hmm_loglik_grad_large.argtypes = [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]
+    if hasattr(L, "hmm_posterior_grad_large"):
+        L.hmm_posterior_grad_large_max_states.restype = c_i
+        L.hmm_posterior_grad_large_workspace_bytes.restype = c_sz
+        L.hmm_posterior_grad_large_workspace_bytes.argtypes = [c_i] * 4
+        L.hmm_posterior_grad_large.restype = c_i
+        L.hmm_posterior_grad_large.argtypes = L.hmm_posterior_grad.argtypes
     L.hmm_gene_emissions.restype = c_i
     L.hmm_gene_emissions.argtypes = [c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_f, c_f, c_i, c_p, c_p]
     L.hmm_profile_create.restype = c_p
@@ -598,4 +604,31 @@ def posterior_grad(A, pi, E, grad_out, mode=POST_LOG, eps=EPS):
         _check(lib().hmm_posterior_grad(A.data_ptr(), pi.data_ptr(), E.data_ptr(), *dims, eps, int(mode),
                                         grad_out.data_ptr(), dA.data_ptr(), dpi.data_ptr(), dE.data_ptr(),
                                         ws.data_ptr(), ws.numel(), _stream(E.device)))
+    return dA, dpi, dE
+
+
+def posterior_grad_large(A, pi, E, grad_out, mode=POST_LOG, eps=EPS):
+    """posterior_grad() through hmm_posterior_grad_large, for any 1 <= q <= 4096 (same arguments, results and
+    semantics; the walk / GEMM evaluation is chosen by q or by OPT_GLARGE).  POST_LOG_NO_LL is not a mode of
+    this call: the autograd node composes it with loglik_grad_large."""
+    if int(mode) not in (POST_PROB, POST_LOG):
+        raise ValueError("posterior_grad_large supports mode POST_PROB or POST_LOG")
+    A, pi, E, grad_out = _dev(A, "A"), _dev(pi, "pi"), _dev(E, "E"), _dev(grad_out, "grad_out")
+    A, pi, dims = _shapes(A, E, pi)
+    k, b, L, q = dims
+    if not hasattr(lib(), "hmm_posterior_grad_large"):
+        raise EngineError("the engine library predates hmm_posterior_grad_large: rebuild it")
+    if q > lib().hmm_posterior_grad_large_max_states():
+        raise ValueError("posterior_grad_large covers q <= %d states, got %d"
+                         % (lib().hmm_posterior_grad_large_max_states(), q))
+    if grad_out.shape != E.shape:
+        raise ValueError("grad_out must be shaped like E")
+    with torch.cuda.device(E.device):
+        ws = _workspace(None, dims, E.device, need=lib().hmm_posterior_grad_large_workspace_bytes(*dims))
+        dA = torch.empty((k, q, q), dtype=torch.float32, device=E.device)
+        dpi = torch.empty((k, q), dtype=torch.float32, device=E.device)
+        dE = torch.empty_like(E)
+        _check(lib().hmm_posterior_grad_large(A.data_ptr(), pi.data_ptr(), E.data_ptr(), *dims, eps, int(mode),
+                                              grad_out.data_ptr(), dA.data_ptr(), dpi.data_ptr(), dE.data_ptr(),
+                                              ws.data_ptr(), ws.numel(), _stream(E.device)))
     return dA, dpi, dE

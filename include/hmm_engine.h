@@ -81,7 +81,8 @@ int hmm_abi_version(void);
 #define HMM_OPT_PGCHUNK      5   /* hmm_posterior_grad in chunks: 0 never, 1 when it pays (default), 2 always  */
 #define HMM_OPT_VGROUPS      6   /* hmm_viterbi: batch groups pipelined on an internal stream; 0 = chosen per shape, 1 = off */
 #define HMM_OPT_VLARGE       7   /* hmm_viterbi_large: 0 = by q (default), 1 = per-sequence walk, 2 = per-position tiles */
-#define HMM_OPT_GLARGE       8   /* hmm_loglik_grad_large: 0 = by q (default), 1 = per-sequence walk, 2 = per-position GEMMs */
+#define HMM_OPT_GLARGE       8   /* hmm_loglik_grad_large and hmm_posterior_grad_large: 0 = by q (default),
+                                    1 = per-sequence walk, 2 = per-position GEMMs                            */
 #define HMM_OPT_COUNT        9
 #define HMM_EXACT_AUTO    0      /* decided on the device (see hmm_posterior)                               */
 #define HMM_EXACT_OFF     1      /* always the chunked scan                                                 */
@@ -100,7 +101,9 @@ int hmm_get_option(int option);
  * forces the all-candidates step.  Zero entries of A are exact zeros in both steps; the two differ in rounding order only.
  * hmm_viterbi covers q <= hmm_viterbi_max_states() (64) and hmm_viterbi_large every q up to
  * hmm_viterbi_large_max_states() (4096); hmm_loglik_grad covers q <= hmm_grad_max_states() (64) and
- * hmm_loglik_grad_large every q up to hmm_loglik_grad_large_max_states() (4096). */
+ * hmm_loglik_grad_large every q up to hmm_loglik_grad_large_max_states() (4096); hmm_posterior_grad covers
+ * q <= hmm_posterior_grad_max_states() (64) and hmm_posterior_grad_large every q up to
+ * hmm_posterior_grad_large_max_states() (4096). */
 int hmm_max_states(void);
 int hmm_scan_max_states(void);
 int hmm_viterbi_max_states(void);
@@ -405,6 +408,32 @@ int hmm_posterior_grad(const float *A, const float *pi, const float *E,
                        int k, int b, int L, int q, float eps, int mode, const float *grad_out,
                        float *dA, float *dpi, float *dE,
                        void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * The same gradient for any 1 <= q <= hmm_posterior_grad_large_max_states() (4096): arguments, outputs, modes and
+ * clamp handling exactly those of hmm_posterior_grad (all four clamps pass nothing: max(E, eps), max(pi, eps), the
+ * forward cell's clamp of the predicted state and the backward max(A bh, eps)).  The four sweeps of
+ * hmm_posterior_grad run serial in time with the cell's exact step, in one of two evaluations picked by
+ * HMM_OPT_GLARGE (0: by q — the walk up to 128 states, the GEMMs above; 1: walk; 2: GEMMs):
+ *   walk   one workgroup per sequence, ceil(q/64) waves, lane = state, A staged in LDS; two value sweeps store the
+ *          forward and backward vectors with their clamp bits, two adjoint sweeps write dE and sum row i of the
+ *          sequence's dA in lane i.  Serves q <= 128: forcing it above returns HMM_ERR_BAD_ARGUMENT.
+ *   GEMMs  per position one f32-MFMA GEMM for each of the two value recursions and of the two adjoint recursions,
+ *          an elementwise pass per adjoint, and two (q x b)(b x q) products for dA into an fp64 accumulator.
+ * The workspace grows with L (both value recursions are kept at every position: three k*b*L*q float arrays and
+ * k*b*L normalisers, plus per-sequence q x q partials for the walk or O(k b q) and k q^2 doubles for the GEMMs).
+ * Sums run in a fixed order (fp32 within a sequence or a tile, fp64 across sequences and positions): repeated
+ * calls return bit-identical results.  Everything runs in order on `stream`.
+ * Argument checks, before any HIP call: bad shape -1, q > 4096 -2, mode not HMM_POST_PROB / HMM_POST_LOG -6, a NULL
+ * A / pi / E / grad_out / dA / dpi / dE / workspace -3, a small or misaligned (256 bytes) workspace -4, the walk
+ * forced above 128 states -6.  workspace_bytes() returns 0 for an unsupported shape or q.
+ */
+int hmm_posterior_grad_large_max_states(void);
+size_t hmm_posterior_grad_large_workspace_bytes(int k, int b, int L, int q);
+int hmm_posterior_grad_large(const float *A, const float *pi, const float *E,
+                             int k, int b, int L, int q, float eps, int mode, const float *grad_out,
+                             float *dA, float *dpi, float *dE,
+                             void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }
