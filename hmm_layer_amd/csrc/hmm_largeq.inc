@@ -295,11 +295,14 @@ __global__ __launch_bounds__(256) void k_lq_normalise(float *__restrict__ out, l
     }
     const float Sg = lq_block_sum(part, red);
     const float ig = 1.0f / Sg;
-    const float sh = mode == 0 ? 0.f : logf(Sg) - (mode == 2 ? (float)loglik[rt / L] : 0.f);
+    const float sh = mode == 0 ? 0.f : logf(Sg);
+    // mode 2: the three terms are added in double and rounded once.  Added in float, the result carried three half
+    // ulps of |loglik| (1.4e-3 at |loglik| = 8400, L = 3000) instead of one.
+    const double shd = mode == 2 ? (double)sh - loglik[rt / L] : 0.0;
 #pragma unroll
     for (int u = 0; u < LQ_NORM_PER; ++u) {
         const int j = threadIdx.x + u * 256;
-        if (j < q) o[j] = mode == 0 ? v[u] * ig : logf(v[u]) - sh;
+        if (j < q) o[j] = mode == 0 ? v[u] * ig : mode == 1 ? logf(v[u]) - sh : (float)((double)logf(v[u]) - shd);
     }
 }
 

@@ -391,7 +391,9 @@ def test_group_pipeline_is_invisible():
 
 @pytest.mark.parametrize("q,b,L", [(17, 3, 40), (29, 5, 120), (64, 4, 50), (100, 70, 33), (257, 9, 25)])
 def test_large_q_path_all_outputs(q, b, L):
-    """q > 16: serial in time, one f32-MFMA GEMM per position + exact cell semantics per row."""
+    """q > 64 (100, 257): serial in time, one f32-MFMA GEMM per position + exact cell semantics per row.  The cases
+    17, 29 and 64 date from when that path began at 17 states; they now run on the 17-64-state paths
+    (hmm_midq.inc and the chunked scans)."""
     rng = np.random.default_rng(q)
     A, pi = rand_model(rng, q, dense=False)
     E = (rng.random((b, L, q)) * 0.9 + 0.05).astype(np.float32)
