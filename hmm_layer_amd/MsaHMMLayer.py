@@ -105,7 +105,12 @@ def _graph_inputs(inputs, cell, end_hints, training, what="loglik"):
         raise ValueError("training through the HIP engine covers models of at most %d states (got %d); "
                          "wrap inference calls in torch.no_grad()" % (limit, cell.max_num_states))
     cell.recurrent_init()
-    E = cell.emission_probs(inputs, end_hints=end_hints, training=training).to(torch.float32)
+    em = cell.emitter[0] if len(cell.emitter) == 1 else None
+    if em is not None and getattr(em, "fused_training", False) and em.can_fuse(inputs):
+        # HIP kernels forward and backward (autograd.GeneEmissions); input nucleotide columns get zero gradient
+        E = em.forward_fused_trainable(inputs, end_hints=end_hints, training=training).to(torch.float32)
+    else:
+        E = cell.emission_probs(inputs, end_hints=end_hints, training=training).to(torch.float32)
     if not E.is_cuda:
         raise engine.EngineError("inputs must live on a HIP device (got %s); the engine has no CPU path" % E.device)
     A = cell.A.to(E.device, torch.float32)

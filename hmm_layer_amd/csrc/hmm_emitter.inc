@@ -79,24 +79,13 @@ __device__ __forceinline__ float em_slow_factor(const float *__restrict__ x, lon
     return prod;
 }
 
-// NT / KT: 16-state / 16-class tiles.  FAST: s in 11..16, rows loaded with one unguarded 16-byte
-// load per lane (elements past the s classes are the row's own nucleotide floats, masked to 0).
-template <int NT, int KT, bool FAST>
-#ifndef HMM_EM_NT
-#define HMM_EM_NT 0
-#endif
-__global__ __launch_bounds__(EM_THREADS) void k_gene_emissions(const float *__restrict__ x, long long npos, int L, int s,
-                                                               const float *__restrict__ B,
-                                                               const int *__restrict__ state_row,
-                                                               const float *__restrict__ codon, int nc,
-                                                               const int *__restrict__ state_codon, int q,
-                                                               float free_value, float add, float n_mass,
-                                                               float *__restrict__ E) {
-    extern __shared__ __attribute__((aligned(16))) float T9[];     // [2][max(nc,1)][512], then the output stages
-    const int tid = threadIdx.x;
-    const int w = s + 5;
-    const int ncp = nc > 0 ? nc : 1;
-    // ---- the window tables: index = code(slot 0) | code(slot 1) << 3 | code(slot 2) << 6
+// ---- pieces shared with the backward (hmm_emitter_grad.inc)
+
+struct EmNuc { f4 nv; float nN; };                           // the five nucleotide floats of one position
+struct EmCodes { unsigned long long v; unsigned soft; };     // 16 x 3-bit codes; positions holding a soft distribution
+
+// the window tables: index = code(slot 0) | code(slot 1) << 3 | code(slot 2) << 6
+__device__ __forceinline__ void em_build_tables(float *T9, const float *__restrict__ codon, int nc, float n_mass, int tid) {
     for (int e = tid; e < 2 * nc * 512; e += EM_THREADS) {
         const int idx = e & 511, sr = e >> 9;
         const int side = sr >= nc ? 1 : 0, c = sr - side * nc;
@@ -117,6 +106,131 @@ __global__ __launch_bounds__(EM_THREADS) void k_gene_emissions(const float *__re
         }
         T9[e] = val;
     }
+}
+
+__device__ __forceinline__ EmNuc em_load_nuc(const float *xr, int s) {
+    EmNuc nu;
+    nu.nv = *reinterpret_cast<const f4u *>(xr + s);
+    nu.nN = xr[s + 4];
+    return nu;
+}
+
+// lane (g, n) holds the nucleotides of position n of the tile -> the tile's wave-uniform code word
+__device__ __forceinline__ EmCodes em_classify(const EmNuc &rw, int n) {
+    const f4 nv = rw.nv;
+    const bool isN = rw.nN == 1.f;                  // the reference counts N only when the flag is exactly 1
+    const float sum = (nv.x + nv.y) + (nv.z + nv.w);
+    const bool hot = !isN && sum == 1.f && (nv.x == 1.f || nv.y == 1.f || nv.z == 1.f || nv.w == 1.f);
+    const bool exactN = isN && sum == 0.f;
+    const int code = hot ? (nv.y == 1.f ? 1 : nv.z == 1.f ? 2 : nv.w == 1.f ? 3 : 0) : 4;
+    // pack: positions 0..9 in one word, 10..15 in the other, OR over the 16 lanes of the row
+    int lo = n < 10 ? code << (3 * n) : 0, hi = n < 10 ? 0 : code << (3 * (n - 10));
+    auto bor = [](int a, int b) { return a | b; };
+    lo = row_allreduce_i(lo, bor);
+    hi = row_allreduce_i(hi, bor);
+    EmCodes cd;
+    cd.v = (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane(lo) |
+           ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane(hi) << 30);
+    cd.soft = (unsigned)__ballot(!(hot || exactN)) & 0xFFFFu;
+    return cd;
+}
+
+// One tile in the D layout (lane (g, n): state 16 nt + n at positions 4g..4g+3 of the tile starting at
+// P, tb = P's position in its sequence): stage[pl * stride + j] = D[nt][r] * (cod[pl][j] + add) for every
+// position below npos and state below q; other entries of the stage are left as they are.  The forward
+// passes emit and its output stage (stride q), the backward dE and its H stage.
+template <int NT>
+__device__ __forceinline__ void em_scale_tile(const f4 (&D)[NT], float *stage, int stride, const int (&cj)[NT], int q,
+                                              const float *T9, int ncp, const EmCodes &prev, const EmCodes &cur,
+                                              const EmCodes &nxt, int tb, int L, long long P, long long npos, int g, int n,
+                                              const float *__restrict__ x, int s, int w, float free_value, float add,
+                                              float n_mass) {
+    // 20-position window, 3 bits each: field p <-> position P - 2 + p
+    const unsigned long long Wv = (prev.v >> 42) | (cur.v << 6) | (nxt.v << 54);
+    const unsigned Ws = (prev.soft >> 14) | (cur.soft << 2) | (nxt.soft << 18);
+    // this lane's positions 4g..4g+3 see fields 4g..4g+7: 24 bits
+    const unsigned u = (unsigned)(Wv >> (12 * g));
+    const bool plain = Ws == 0u && tb >= 2 && tb + 18 <= L && P + 16 <= npos;     // wave-uniform
+    if (__builtin_expect(plain, 1)) {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const int j = 16 * nt + n;
+            if (j >= q) continue;
+            const int c = cj[nt];
+            const float *TL = T9 + (c >= 0 ? c : 0) * 512, *TR = TL + ncp * 512;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float f = TL[(u >> (3 * r + 6)) & 511u] * TR[(u >> (3 * r)) & 511u];
+                stage[(4 * g + r) * stride + j] = D[nt][r] * ((c >= 0 ? f : free_value) + add);
+            }
+        }
+    } else {
+        // a soft distribution, a sequence border or the end of the tensor inside the window:
+        // per output, table lookup or the generic product-sum
+        unsigned slowmask = 0;                      // bit 4 nt + r: that output needs the generic path
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int pl = 4 * g + r;
+            const long long pos = P + pl;
+            int t = tb + pl;
+            if (t >= L) t %= L;
+            const bool slow = ((Ws >> pl) & 0x1Fu) != 0u || t < 2 || t >= L - 2;
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+                const int j = 16 * nt + n;
+                const int c = cj[nt];
+                float cod = free_value;
+                if (c >= 0) cod = T9[c * 512 + ((u >> (3 * r + 6)) & 511u)] * T9[(ncp + c) * 512 + ((u >> (3 * r)) & 511u)];
+                const bool ok = pos < npos && j < q;
+                if (ok && c >= 0 && slow) slowmask |= 1u << (4 * nt + r);
+                else if (ok) stage[pl * stride + j] = D[nt][r] * (cod + add);
+            }
+        }
+        if (__ballot(slowmask != 0u) != 0ull) {
+            // one copy of the generic code, walked with run-time indices (the tile values are
+            // picked by compare-select)
+#pragma unroll 1
+            for (int o = 0; o < 4 * NT; ++o) {
+                if (!((slowmask >> o) & 1u)) continue;
+                const int nt = o >> 2, r = o & 3;
+                float d = 0.f;
+                int c = -1;
+#pragma unroll
+                for (int a = 0; a < NT; ++a) {
+                    const float v = r == 0 ? D[a][0] : r == 1 ? D[a][1] : r == 2 ? D[a][2] : D[a][3];
+                    d = a == nt ? v : d;
+                    c = a == nt ? cj[a] : c;
+                }
+                const int pl = 4 * g + r;
+                const long long pos = P + pl;
+                int t = tb + pl;
+                if (t >= L) t %= L;
+                const float cod = em_slow_factor(x, pos, t, L, s, w, T9 + (size_t)c * 512,
+                                                 T9 + (size_t)(ncp + c) * 512, n_mass);
+                stage[pl * stride + 16 * nt + n] = d * (cod + add);
+            }
+        }
+    }
+}
+
+// NT / KT: 16-state / 16-class tiles.  FAST: s in 11..16, rows loaded with one unguarded 16-byte
+// load per lane (elements past the s classes are the row's own nucleotide floats, masked to 0).
+template <int NT, int KT, bool FAST>
+#ifndef HMM_EM_NT
+#define HMM_EM_NT 0
+#endif
+__global__ __launch_bounds__(EM_THREADS) void k_gene_emissions(const float *__restrict__ x, long long npos, int L, int s,
+                                                               const float *__restrict__ B,
+                                                               const int *__restrict__ state_row,
+                                                               const float *__restrict__ codon, int nc,
+                                                               const int *__restrict__ state_codon, int q,
+                                                               float free_value, float add, float n_mass,
+                                                               float *__restrict__ E) {
+    extern __shared__ __attribute__((aligned(16))) float T9[];     // [2][max(nc,1)][512], then the output stages
+    const int tid = threadIdx.x;
+    const int w = s + 5;
+    const int ncp = nc > 0 ? nc : 1;
+    em_build_tables(T9, codon, nc, n_mass, tid);
     __syncthreads();
 
     const int lane = tid & 63, g = lane >> 4, n = lane & 15;
@@ -141,8 +255,7 @@ __global__ __launch_bounds__(EM_THREADS) void k_gene_emissions(const float *__re
     float *stage = T9 + (size_t)2 * ncp * 512 + (size_t)(tid >> 6) * (16 * q);
     const int npieces = 4 * q;                              // 16-byte pieces per tile
 
-    struct Raw { f4 xa[KT]; f4 nv; float nN; };
-    struct Codes { unsigned long long v; unsigned soft; };   // 16 x 3-bit codes; positions holding a soft distribution
+    struct Raw { f4 xa[KT]; EmNuc nu; };
 
     const long long nruns = (npos + EM_RUN - 1) / EM_RUN;
     const long long wave0 = (long long)blockIdx.x * (EM_THREADS / 64) + (tid >> 6);
@@ -179,30 +292,12 @@ __global__ __launch_bounds__(EM_THREADS) void k_gene_emissions(const float *__re
 #pragma unroll
                 for (int kk = 0; kk < 4; ++kk) rw.xa[kt][kk] = (16 * kt + 4 * g + kk < s) ? v[kk] : 0.f;
             }
-            rw.nv = *reinterpret_cast<const f4u *>(xr + s);
-            rw.nN = xr[s + 4];
+            rw.nu = em_load_nuc(xr, s);
             return rw;
         };
-        auto classify = [&](const Raw &rw) {
-            const f4 nv = rw.nv;
-            const bool isN = rw.nN == 1.f;                  // the reference counts N only when the flag is exactly 1
-            const float sum = (nv.x + nv.y) + (nv.z + nv.w);
-            const bool hot = !isN && sum == 1.f && (nv.x == 1.f || nv.y == 1.f || nv.z == 1.f || nv.w == 1.f);
-            const bool exactN = isN && sum == 0.f;
-            const int code = hot ? (nv.y == 1.f ? 1 : nv.z == 1.f ? 2 : nv.w == 1.f ? 3 : 0) : 4;
-            // pack: positions 0..9 in one word, 10..15 in the other, OR over the 16 lanes of the row
-            int lo = n < 10 ? code << (3 * n) : 0, hi = n < 10 ? 0 : code << (3 * (n - 10));
-            auto bor = [](int a, int b) { return a | b; };
-            lo = row_allreduce_i(lo, bor);
-            hi = row_allreduce_i(hi, bor);
-            Codes cd;
-            cd.v = (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane(lo) |
-                   ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane(hi) << 30);
-            cd.soft = (unsigned)__ballot(!(hot || exactN)) & 0xFFFFu;
-            return cd;
-        };
+        auto classify = [&](const Raw &rw) { return em_classify(rw.nu, n); };
 
-        Codes prev, cur;
+        EmCodes prev, cur;
         f4 xa[KT];
         {
             const Raw rp = load_tile(-16);                  // codes only (clamped at the tensor start)
@@ -224,73 +319,9 @@ __global__ __launch_bounds__(EM_THREADS) void k_gene_emissions(const float *__re
 #pragma unroll
                 for (int kt = 0; kt < KT; ++kt) D[nt] = mfma4v(xa[kt], bw[nt][kt], D[nt]);
             }
-            const Codes nxt = classify(ra);
-            // 20-position window, 3 bits each: field p <-> position P - 2 + p
-            const unsigned long long Wv = (prev.v >> 42) | (cur.v << 6) | (nxt.v << 54);
-            const unsigned Ws = (prev.soft >> 14) | (cur.soft << 2) | (nxt.soft << 18);
-            // this lane's positions 4g..4g+3 see fields 4g..4g+7: 24 bits
-            const unsigned u = (unsigned)(Wv >> (12 * g));
-            const bool plain = Ws == 0u && tb >= 2 && tb + 18 <= L && P + 16 <= npos;     // wave-uniform
-            if (__builtin_expect(plain, 1)) {
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    const int j = 16 * nt + n;
-                    if (j >= q) continue;
-                    const int c = cj[nt];
-                    const float *TL = T9 + (c >= 0 ? c : 0) * 512, *TR = TL + ncp * 512;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float f = TL[(u >> (3 * r + 6)) & 511u] * TR[(u >> (3 * r)) & 511u];
-                        stage[(4 * g + r) * q + j] = D[nt][r] * ((c >= 0 ? f : free_value) + add);
-                    }
-                }
-            } else {
-                // a soft distribution, a sequence border or the end of the tensor inside the window:
-                // per output, table lookup or the generic product-sum
-                unsigned slowmask = 0;                      // bit 4 nt + r: that output needs the generic path
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int pl = 4 * g + r;
-                    const long long pos = P + pl;
-                    int t = tb + pl;
-                    if (t >= L) t %= L;
-                    const bool slow = ((Ws >> pl) & 0x1Fu) != 0u || t < 2 || t >= L - 2;
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) {
-                        const int j = 16 * nt + n;
-                        const int c = cj[nt];
-                        float cod = free_value;
-                        if (c >= 0) cod = T9[c * 512 + ((u >> (3 * r + 6)) & 511u)] * T9[(ncp + c) * 512 + ((u >> (3 * r)) & 511u)];
-                        const bool ok = pos < npos && j < q;
-                        if (ok && c >= 0 && slow) slowmask |= 1u << (4 * nt + r);
-                        else if (ok) stage[pl * q + j] = D[nt][r] * (cod + add);
-                    }
-                }
-                if (__ballot(slowmask != 0u) != 0ull) {
-                    // one copy of the generic code, walked with run-time indices (the tile values are
-                    // picked by compare-select)
-#pragma unroll 1
-                    for (int o = 0; o < 4 * NT; ++o) {
-                        if (!((slowmask >> o) & 1u)) continue;
-                        const int nt = o >> 2, r = o & 3;
-                        float d = 0.f;
-                        int c = -1;
-#pragma unroll
-                        for (int a = 0; a < NT; ++a) {
-                            const float v = r == 0 ? D[a][0] : r == 1 ? D[a][1] : r == 2 ? D[a][2] : D[a][3];
-                            d = a == nt ? v : d;
-                            c = a == nt ? cj[a] : c;
-                        }
-                        const int pl = 4 * g + r;
-                        const long long pos = P + pl;
-                        int t = tb + pl;
-                        if (t >= L) t %= L;
-                        const float cod = em_slow_factor(x, pos, t, L, s, w, T9 + (size_t)c * 512,
-                                                         T9 + (size_t)(ncp + c) * 512, n_mass);
-                        stage[pl * q + 16 * nt + n] = d * (cod + add);
-                    }
-                }
-            }
+            const EmCodes nxt = classify(ra);
+            em_scale_tile<NT>(D, stage, q, cj, q, T9, ncp, prev, cur, nxt, tb, L, P, npos, g, n, x, s, w, free_value, add,
+                              n_mass);
             __builtin_amdgcn_wave_barrier();                // stage is wave-private: LDS ops of a wave execute in order
             {   // flush the tile: 64 q contiguous bytes of E, 16 bytes per lane
                 const long long nfl = (npos - P < 16 ? npos - P : 16) * q;      // floats that exist

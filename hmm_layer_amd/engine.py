@@ -107,6 +107,12 @@ def lib():
         L.hmm_posterior_grad_large.argtypes = L.hmm_posterior_grad.argtypes
     L.hmm_gene_emissions.restype = c_i
     L.hmm_gene_emissions.argtypes = [c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_f, c_f, c_i, c_p, c_p]
+    if hasattr(L, "hmm_gene_emissions_grad"):
+        L.hmm_gene_emissions_grad_workspace_bytes.restype = c_sz
+        L.hmm_gene_emissions_grad_workspace_bytes.argtypes = [c_i] * 5
+        L.hmm_gene_emissions_grad.restype = c_i
+        L.hmm_gene_emissions_grad.argtypes = [c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_f, c_f, c_i,
+                                              c_p, c_p, c_p, c_p, c_sz, c_p]
     L.hmm_profile_create.restype = c_p
     L.hmm_profile_destroy.argtypes = [c_p]
     L.hmm_posterior_profiled.restype = c_i
@@ -394,6 +400,47 @@ def gene_emissions(x, B, state_row, codon, state_codon, free_value=1.0 / 4096.0,
                                         codon.data_ptr(), nc, state_codon.data_ptr(), q, float(free_value),
                                         float(add), int(n_mass), E.data_ptr(), _stream(x.device)))
     return E
+
+
+def gene_emissions_grad(x, B, state_row, codon, state_codon, dE, free_value=1.0 / 4096.0, add=0.0, n_mass=1,
+                        want_dx=True, want_dB=True):
+    """Backward of gene_emissions (hmm_gene_emissions_grad): dE (b,L,q) = dL/dE -> (dx (b,L,s+5) | None,
+    dB (rows,s) | None).  The five nucleotide columns of dx are exactly 0 (one-hot nucleotides are data); dB is
+    written whole by the call and summed in a fixed order, so repeated calls are bit-identical.  The workspace
+    (one (rows,s) partial per workgroup, at most 1024 of them) comes from the engine's cache under a key of its
+    own per device and stream, so it never overwrites the routing records that exact_count() and its kin read
+    from the recursions' workspace."""
+    x, B, codon, dE = _dev(x, "x"), _dev(B, "B"), _dev(codon, "codon"), _dev(dE, "dE")
+    state_row = _dev(state_row, "state_row", torch.int32)
+    state_codon = _dev(state_codon, "state_codon", torch.int32)
+    if not hasattr(lib(), "hmm_gene_emissions_grad"):
+        raise EngineError("the engine library predates hmm_gene_emissions_grad: rebuild it")
+    if x.dim() != 3:
+        raise ValueError("x must have shape (b, L, s+5), got %s" % (tuple(x.shape),))
+    b, L, w = x.shape
+    s = w - 5
+    rows, q, nc = B.shape[0], state_row.numel(), codon.shape[1]
+    if B.shape[1] != s or tuple(codon.shape) != (2, nc, 64) or state_codon.numel() != q:
+        raise ValueError("inconsistent emitter tables")
+    if tuple(dE.shape) != (b, L, q):
+        raise ValueError("dE must have shape %s, got %s" % ((b, L, q), tuple(dE.shape)))
+    if not (want_dx or want_dB):
+        return None, None
+    with torch.cuda.device(x.device):
+        need = lib().hmm_gene_emissions_grad_workspace_bytes(b, L, s, rows, q)
+        key = (x.device.index, torch.cuda.current_stream(x.device).cuda_stream, "emitter_grad")
+        ws = _workspaces.get(key)
+        if ws is None or ws.numel() < need:
+            ws = torch.empty(need, dtype=torch.uint8, device=x.device)      # at most 1024 x rows x s floats
+            _workspaces[key] = ws
+        dx = torch.empty_like(x) if want_dx else None
+        dB = torch.empty_like(B) if want_dB else None
+        _check(lib().hmm_gene_emissions_grad(x.data_ptr(), b, L, s, B.data_ptr(), rows, state_row.data_ptr(),
+                                             codon.data_ptr(), nc, state_codon.data_ptr(), q, float(free_value),
+                                             float(add), int(n_mass), dE.data_ptr(),
+                                             dx.data_ptr() if want_dx else None, dB.data_ptr() if want_dB else None,
+                                             ws.data_ptr(), ws.numel(), _stream(x.device)))
+    return dx, dB
 
 
 def viterbi(logA, logpi, logE):

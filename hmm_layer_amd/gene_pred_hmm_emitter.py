@@ -123,7 +123,7 @@ class GenePredHMMEmitter(SimpleGenePredHMMEmitter):
 
     def __init__(self, start_codons, stop_codons, intron_begin_pattern, intron_end_pattern, l2_lambda=0.01,
                  nucleotide_kernel_init=None, trainable_nucleotides_at_exons=False, n_mass_compat=False,
-                 **kwargs):
+                 fused_training=False, **kwargs):
         super().__init__(**kwargs)
         self.num_states = 1 + 14 * self.num_copies
         self.start_codons, self.stop_codons = start_codons, stop_codons
@@ -132,6 +132,7 @@ class GenePredHMMEmitter(SimpleGenePredHMMEmitter):
         self.nucleotide_kernel_init = nucleotide_kernel_init
         self.trainable_nucleotides_at_exons = trainable_nucleotides_at_exons
         self.n_mass_compat = n_mass_compat
+        self.fused_training = fused_training      # the layer trains through forward_fused_trainable where can_fuse holds
         start = make_codon_probs(start_codons, True)
         stop = make_codon_probs(stop_codons, False)
         ibeg = make_codon_probs(intron_begin_pattern, True)
@@ -224,6 +225,23 @@ class GenePredHMMEmitter(SimpleGenePredHMMEmitter):
                                       add=1e-7 if training else 0.0, n_mass=2 if self.n_mass_compat else 1)
             return self.apply_end_hints(E.unsqueeze(0), end_hints)
 
+    def forward_fused_trainable(self, inputs, end_hints=None, training=False):
+        """forward() with its autograd graph, through the HIP kernels: make_B() (softmax, torch), ONE node
+        (autograd.GeneEmissions: hmm_gene_emissions forward, hmm_gene_emissions_grad backward), apply_end_hints
+        (torch).  Between forward and backward only the input, B and the small tables are kept.
+
+        Difference from forward(): the gradient of the five nucleotide columns of the input is exactly zero.
+        One-hot nucleotides are data, and the ``== 1`` test on the N flag is not differentiable anyway; autograd
+        through forward() returns small non-zero values there (up to about 3e-2 in fp64 on test-sized inputs).
+        A caller who concatenates network output with one-hot nucleotides never sees them.  Needs can_fuse(inputs)."""
+        from . import autograd
+        B = self.make_B()
+        row, cod = self.state_tables(inputs.device)
+        E = autograd.gene_emissions(inputs[0].to(torch.float32), B[0].to(torch.float32), row,
+                                    self.codon_probs.to(inputs.device, torch.float32).contiguous(), cod,
+                                    add=1e-7 if training else 0.0, n_mass=2 if self.n_mass_compat else 1)
+        return self.apply_end_hints(E.unsqueeze(0), end_hints)
+
     def get_config(self):
         config = super().get_config()
         config.update({"start_codons": self.start_codons, "stop_codons": self.stop_codons,
@@ -231,5 +249,6 @@ class GenePredHMMEmitter(SimpleGenePredHMMEmitter):
                        "intron_end_pattern": self.intron_end_pattern, "l2_lambda": self.l2_lambda,
                        "nucleotide_kernel_init": self.nucleotide_kernel_init,
                        "trainable_nucleotides_at_exons": self.trainable_nucleotides_at_exons,
-                       "n_mass_compat": self.n_mass_compat})          # D5 compatibility switch
+                       "n_mass_compat": self.n_mass_compat,           # D5 compatibility switch
+                       "fused_training": self.fused_training})
         return config

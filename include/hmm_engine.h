@@ -261,6 +261,32 @@ int hmm_gene_emissions(const float *x, int b, int L, int s, const float *B, int 
                        float free_value, float add, int n_mass, float *E, void *stream);
 
 /*
+ * Backward of hmm_gene_emissions: what autograd through GenePredHMMEmitter.forward
+ * (hmm_layer/gene_pred_hmm_emitter.py:231-277, class part :93-121, kmer.make_k_mers hmm_layer/kmer.py:3-47)
+ * computes for the class probabilities and for B, from x, the tables and the upstream gradient alone
+ * (the 3-mer factor is recomputed; E is not an input).  Arguments as for hmm_gene_emissions, and
+ *   dE          (b,L,q)    upstream gradient dL/dE
+ *   dx          (b,L,s+5)  dL/dx, or NULL: class columns sum_j dE*(cod+add)*B[state_row[j]]; the five
+ *                          nucleotide columns are written as 0 (one-hot nucleotides are data; autograd
+ *                          through the reference's ops yields small non-zero values there)
+ *   dB          (rows,s)   dL/dB, or NULL.  Written whole by the call: the caller does not zero it.
+ * Limits as for the forward: q <= 64, s <= 32, rows <= 32, nc <= 16.  Checked before any HIP call, in this
+ * order: shape (HMM_ERR_BAD_SHAPE), limits (HMM_ERR_Q_UNSUPPORTED), pointers (HMM_ERR_NULL_POINTER: any input,
+ * the workspace, or both outputs NULL), workspace (HMM_ERR_WORKSPACE: fewer than
+ * hmm_gene_emissions_grad_workspace_bytes bytes, or not 256-byte aligned).  The workspace holds one (rows,s)
+ * partial of dB per workgroup; the grid depends on b*L only (at most 1024 workgroups), so the workspace stops
+ * growing with b*L.  dB is summed in a fixed order (waves of a workgroup, states of a row, workgroups in fp64):
+ * repeated calls give bit-identical results.  hmm_gene_emissions_grad_workspace_bytes returns 0 for an
+ * unsupported shape.  Runs on `stream` only, no host synchronisation, capturable into a HIP graph.
+ */
+size_t hmm_gene_emissions_grad_workspace_bytes(int b, int L, int s, int rows, int q);
+int hmm_gene_emissions_grad(const float *x, int b, int L, int s, const float *B, int rows,
+                            const int *state_row, const float *codon, int nc, const int *state_codon, int q,
+                            float free_value, float add, int n_mass, const float *dE,
+                            float *dx /* (b,L,s+5) or NULL */, float *dB /* (rows,s) or NULL */,
+                            void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Per-kernel timing for the roofline report (bench.py): the same computation as
  * hmm_posterior with every kernel launch bracketed by HIP events recorded on `stream`.
  * hmm_profile_read() waits for the recorded events, returns the summed milliseconds and
