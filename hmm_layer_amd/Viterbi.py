@@ -3,7 +3,9 @@ docstring, hmm_layer/MsaHmmCell.py:13; learnMSA, which it ports, has a Viterbi m
 
 ``viterbi(inputs, cell)`` materialises log A, log pi and log E exactly as the layer does for the
 forward-backward engine and makes one Viterbi call (include/hmm_engine.h): ``hmm_viterbi`` for up to 64
-states, ``hmm_viterbi_large`` above — every cell the layer serves, up to 4096 states (e.g. the many-copy
+states — for 17 to 64 states (the two- to four-copy gene models) and the few long sequences where
+``hmm_viterbi_scan_pays`` says so, the time-parallel ``hmm_viterbi_scan`` instead, with bit-identical
+results —, ``hmm_viterbi_large`` above: every cell the layer serves, up to 4096 states (e.g. the many-copy
 gene models and profile HMMs)."""
 import torch
 

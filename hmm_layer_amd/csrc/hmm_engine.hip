@@ -3373,6 +3373,7 @@ int hmm_loglik_partials(const double *loglik, const float *weights, int k, int b
 
 #include "hmm_seqshard.inc"
 #include "hmm_viterbi.inc"
+#include "hmm_viterbi_scan.inc"
 #include "hmm_viterbi_large.inc"
 #include "hmm_emitter.inc"
 #include "hmm_emitter_grad.inc"

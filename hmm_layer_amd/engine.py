@@ -93,6 +93,16 @@ def lib():
         L.hmm_viterbi_large_workspace_bytes.argtypes = [c_i] * 4
         L.hmm_viterbi_large.restype = c_i
         L.hmm_viterbi_large.argtypes = L.hmm_viterbi.argtypes
+    if hasattr(L, "hmm_viterbi_scan"):
+        L.hmm_viterbi_scan_max_states.restype = c_i
+        L.hmm_viterbi_scan_chunk_len.restype = c_i
+        L.hmm_viterbi_scan_chunk_len.argtypes = [c_i] * 4
+        L.hmm_viterbi_scan_pays.restype = c_i
+        L.hmm_viterbi_scan_pays.argtypes = [c_i] * 4
+        L.hmm_viterbi_scan_workspace_bytes.restype = c_sz
+        L.hmm_viterbi_scan_workspace_bytes.argtypes = [c_i] * 4
+        L.hmm_viterbi_scan.restype = c_i
+        L.hmm_viterbi_scan.argtypes = L.hmm_viterbi.argtypes
     if hasattr(L, "hmm_loglik_grad_large"):
         L.hmm_loglik_grad_large_max_states.restype = c_i
         L.hmm_loglik_grad_large_workspace_bytes.restype = c_sz
@@ -447,13 +457,16 @@ def viterbi(logA, logpi, logE):
     """Most probable state paths.  logA (k,q,q), logpi (k,q), logE (k,b,L,q) fp32 log-probabilities
     (-inf allowed: anything below -1024 counts as -1024).  -> (path (k,b,L) int32, score (k,b) fp64).
     Scores are Q16 fixed point, so the result is bit-identical to the serial recursion
-    (oracle/viterbi.py); ties take the lowest state index.  q <= 64 runs hmm_viterbi, larger models
-    viterbi_large (hmm_viterbi_large)."""
+    (oracle/viterbi.py); ties take the lowest state index.  q <= 64 runs hmm_viterbi — or, for 17..64 states
+    and the few long sequences where hmm_viterbi_scan_pays says so, viterbi_scan: bit-identical results, only
+    faster —, larger models viterbi_large (hmm_viterbi_large)."""
     logA, logpi, logE = _dev(logA, "logA"), _dev(logpi, "logpi"), _dev(logE, "logE")
     logA, logpi, dims = _shapes(logA, logE, logpi)
     k, b, L, q = dims
     if q > lib().hmm_viterbi_max_states():
         return viterbi_large(logA, logpi, logE)
+    if q > lib().hmm_scan_max_states() and hasattr(lib(), "hmm_viterbi_scan") and lib().hmm_viterbi_scan_pays(*dims):
+        return viterbi_scan(logA, logpi, logE)
     with torch.cuda.device(logE.device):
         need = lib().hmm_viterbi_workspace_bytes(*dims)
         key = (logE.device.index, torch.cuda.current_stream(logE.device).cuda_stream, "viterbi")
@@ -466,6 +479,32 @@ def viterbi(logA, logpi, logE):
         _check(lib().hmm_viterbi(logA.data_ptr(), logpi.data_ptr(), logE.data_ptr(), *dims,
                                  path.data_ptr(), score.data_ptr(), ws.data_ptr(), ws.numel(),
                                  _stream(logE.device)))
+    return path, score
+
+
+def viterbi_scan(logA, logpi, logE):
+    """viterbi() through hmm_viterbi_scan, the time-parallel chunk scan for 1 <= q <= 64 (same arguments, results
+    and semantics): what few, long sequences of the 17..64-state models want.  OPT_CHUNK forces the chunk length,
+    OPT_SCAN2 = 0 the single-level chunk scans, OPT_FORCE_DENSE = 1 the all-candidates reduce."""
+    logA, logpi, logE = _dev(logA, "logA"), _dev(logpi, "logpi"), _dev(logE, "logE")
+    logA, logpi, dims = _shapes(logA, logE, logpi)
+    k, b, L, q = dims
+    if not hasattr(lib(), "hmm_viterbi_scan"):
+        raise EngineError("the engine library predates hmm_viterbi_scan: rebuild it")
+    if q > lib().hmm_viterbi_scan_max_states():
+        raise ValueError("viterbi_scan covers q <= %d states, got %d" % (lib().hmm_viterbi_scan_max_states(), q))
+    with torch.cuda.device(logE.device):
+        need = lib().hmm_viterbi_scan_workspace_bytes(*dims)
+        key = (logE.device.index, torch.cuda.current_stream(logE.device).cuda_stream, "viterbi_scan")
+        ws = _workspaces.get(key)
+        if ws is None or ws.numel() < need:
+            ws = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=logE.device)
+            _workspaces[key] = ws
+        path = torch.empty((k, b, L), dtype=torch.int32, device=logE.device)
+        score = torch.empty((k, b), dtype=torch.float64, device=logE.device)
+        _check(lib().hmm_viterbi_scan(logA.data_ptr(), logpi.data_ptr(), logE.data_ptr(), *dims,
+                                      path.data_ptr(), score.data_ptr(), ws.data_ptr(), ws.numel(),
+                                      _stream(logE.device)))
     return path, score
 
 

@@ -244,6 +244,36 @@ int hmm_viterbi_large(const float *logA, const float *logpi, const float *logE,
                       void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * Time-parallel Viterbi for 1 <= q <= hmm_viterbi_scan_max_states() (64): the same arguments, layouts, error
+ * codes and Q16 semantics as hmm_viterbi (bit-identical paths and scores wherever both run), evaluated by the
+ * three-phase chunk scan with q x q max-plus operators in 32-state (q <= 32) or 64-state tiles: reduce (one wave
+ * per chunk, lane = start state; a model whose states have at most 8 explicit predecessors is reduced over its
+ * predecessors plus the one off-edge candidate, decided per model on the device, HMM_OPT_FORCE_DENSE = 1 forces
+ * all q candidates), forward chunk scan, apply (the step of hmm_viterbi's walk from the true entering scores, one
+ * backpointer byte per position and state), backward chunk scan, backtrace of every chunk in parallel.  Both
+ * chunk scans run in two levels from 32 chunks per sequence on (HMM_OPT_SCAN2 = 0: one level); HMM_OPT_CHUNK
+ * forces the chunk length.  It serves FEW LONG sequences: the reduce does about q times the work of the walk.
+ *   hmm_viterbi_scan_chunk_len        chunk length the call would use (a multiple of 16, <= 512); 0 for an
+ *                                     unsupported shape
+ *   hmm_viterbi_scan_pays             1 where the measured rule prefers the scan to hmm_viterbi's
+ *                                     walk, else 0; the host wrapper (engine.viterbi) routes by it
+ *   hmm_viterbi_scan_workspace_bytes  exactly what the call uses: 64*k*b*L bytes of backpointers plus a QT x QT
+ *                                     operator per chunk; 0 for an unsupported shape
+ * Argument checks, before any HIP call, in this order: shape (HMM_ERR_BAD_SHAPE), q > 64 (HMM_ERR_Q_UNSUPPORTED),
+ * any NULL pointer (HMM_ERR_NULL_POINTER), workspace too small or not 256-byte aligned (HMM_ERR_WORKSPACE).
+ * Every offset into logE, path and the backpointers is 64-bit.  Runs on `stream` only, no host synchronisation,
+ * capturable into a HIP graph, deterministic.  hmm_viterbi itself never takes this path.
+ */
+int hmm_viterbi_scan_max_states(void);
+int hmm_viterbi_scan_chunk_len(int k, int b, int L, int q);
+int hmm_viterbi_scan_pays(int k, int b, int L, int q);
+size_t hmm_viterbi_scan_workspace_bytes(int k, int b, int L, int q);
+int hmm_viterbi_scan(const float *logA, const float *logpi, const float *logE,
+                     int k, int b, int L, int q,
+                     int32_t *path, double *score,
+                     void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Fused emission producer of the gene-prediction models.  Replaces GenePredHMMEmitter.forward
  * (hmm_layer/gene_pred_hmm_emitter.py:231-277, class part :93-121) and kmer.make_k_mers
  * (hmm_layer/kmer.py:3-47) for inference with one model:
