@@ -2692,9 +2692,9 @@ static hipStream_t *helper_streams() {
     return pool[dev];
 }
 
-static int check_ws(const Plan &p, void *ws, size_t bytes) {
+static int check_ws(size_t total, void *ws, size_t bytes) {
     if (!ws) return HMM_ERR_NULL_POINTER;
-    if (bytes < p.total || ((uintptr_t)ws & 255)) return HMM_ERR_WORKSPACE;
+    if (bytes < total || ((uintptr_t)ws & 255)) return HMM_ERR_WORKSPACE;
     return HMM_OK;
 }
 
@@ -2702,6 +2702,7 @@ static int check_ws(const Plan &p, void *ws, size_t bytes) {
 #include "hmm_midq.inc"
 #include "hmm_scan32.inc"
 #include "hmm_scan64.inc"
+#include "hmm_scan_mid.inc"
 
 extern "C" {
 
@@ -2750,15 +2751,11 @@ size_t hmm_workspace_bytes(int op, int k, int b, int L, int q) {
     if (q > QP) {
         LqPlan lp;
         if (make_lqplan(k, b, L, q, &lp)) return 0;
-        if (q <= Q32 && op != HMM_OP_VITERBI) {                               // + the chunked scan's region
-            Plan32 p32;
-            if (make_plan32(op, k, b, L, q, &p32)) return 0;
-            return lp.total + p32.total;
-        }
-        if (scan64_wanted(k, b, L, q) && op != HMM_OP_VITERBI) {               // few sequences of 33..64 states: likewise
-            Plan64 p64;
-            if (make_plan64(op, k, b, L, q, &p64)) return 0;
-            return lp.total + p64.total;
+        const int W = op != HMM_OP_VITERBI ? mid_width(k, b, L, q) : 0;
+        if (W) {                                                               // + the chunked scan's region
+            MidPlan mp;
+            if (make_midplan(op, k, b, L, q, W, &mp)) return 0;
+            return lp.total + mp.total;
         }
         return lp.total;
     }
@@ -2772,12 +2769,6 @@ size_t hmm_workspace_bytes(int op, int k, int b, int L, int q) {
     return p.total;
 }
 
-static int lq_check(const LqPlan &lp, void *ws, size_t bytes) {
-    if (!ws) return HMM_ERR_NULL_POINTER;
-    if (bytes < lp.total || ((uintptr_t)ws & 255)) return HMM_ERR_WORKSPACE;
-    return HMM_OK;
-}
-
 int hmm_forward(const float *A, const float *pi, const float *E, int k, int b, int L, int q, float eps,
                 float *log_alpha, double *loglik, void *workspace, size_t workspace_bytes, void *stream) {
     if (q > QP) {
@@ -2785,49 +2776,38 @@ int hmm_forward(const float *A, const float *pi, const float *E, int k, int b, i
         int rc = make_lqplan(k, b, L, q, &lp);
         if (rc) return rc;
         if (!A || !pi || !E || !loglik) return HMM_ERR_NULL_POINTER;
-        if ((rc = lq_check(lp, workspace, workspace_bytes))) return rc;
+        if ((rc = check_ws(lp.total, workspace, workspace_bytes))) return rc;
         char *ws = (char *)workspace;
-        if (q <= Q32) {
-            // 17..32 states: chunk operators + chunk scan (+ the forward apply kernel for log alpha) for the
-            // models the chunked path serves (decided on the device), one wave per sequence for the others
-            Plan32 p32;
-            if ((rc = make_plan32(log_alpha ? HMM_OP_FORWARD : HMM_OP_LOGLIK, k, b, L, q, &p32))) return rc;
-            if (workspace_bytes < lp.total + p32.total) return HMM_ERR_WORKSPACE;
-            if (log_alpha) scan32_forward(A, pi, E, p32, eps, log_alpha, ws + lp.total, (hipStream_t)stream);
-            else scan32_loglik(A, pi, E, p32, eps, ws + lp.total, (hipStream_t)stream);
-            mq_forward(A, pi, E, k, b, L, q, eps, nullptr, log_alpha, (double *)(ws + lp.total + p32.o_loglik),
-                       (hipStream_t)stream, (const int *)(ws + lp.total + p32.o_need), (MqSp *)(ws + lp.o_sp));
-            hipLaunchKernelGGL(k_copy_loglik, dim3((lp.NB + 255) / 256), dim3(256), 0, (hipStream_t)stream,
-                               (const double *)(ws + lp.total + p32.o_loglik), loglik, lp.NB);
-            return check_launch();
-        }
-        if (scan64_wanted(k, b, L, q)) {
-            // 33..64 states, few sequences: the chunked scan for primitive models, one wave per sequence for the rest
-            Plan64 p64;
-            if ((rc = make_plan64(log_alpha ? HMM_OP_FORWARD : HMM_OP_LOGLIK, k, b, L, q, &p64))) return rc;
-            if (workspace_bytes < lp.total + p64.total) return HMM_ERR_WORKSPACE;
-            if (log_alpha) scan64_forward(A, pi, E, p64, eps, log_alpha, ws + lp.total, (hipStream_t)stream);
-            else scan64_loglik(A, pi, E, p64, eps, ws + lp.total, (hipStream_t)stream);
-            mq_forward(A, pi, E, k, b, L, q, eps, nullptr, log_alpha, (double *)(ws + lp.total + p64.o_loglik),
-                       (hipStream_t)stream, (const int *)(ws + lp.total + p64.o_need), (MqSp *)(ws + lp.o_sp));
-            hipLaunchKernelGGL(k_copy_loglik, dim3((lp.NB + 255) / 256), dim3(256), 0, (hipStream_t)stream,
-                               (const double *)(ws + lp.total + p64.o_loglik), loglik, lp.NB);
-            return check_launch();
-        }
-        if (q <= MQ_MAX)                                     // one wave per sequence, no launches per step
-            mq_forward(A, pi, E, k, b, L, q, eps, nullptr, log_alpha, (double *)(ws + lp.o_ll), (hipStream_t)stream, nullptr,
+        hipStream_t st = (hipStream_t)stream;
+        double *ll = (double *)(ws + lp.o_ll);
+        if (const int W = mid_width(k, b, L, q)) {
+            // 17..32 states, or few long sequences of 33..64: chunk operators + chunk scan (+ the forward apply kernel
+            // for log alpha) for the models the chunked path serves (decided on the device), one wave per sequence
+            // for the others
+            MidPlan mp;
+            if ((rc = make_midplan(log_alpha ? HMM_OP_FORWARD : HMM_OP_LOGLIK, k, b, L, q, W, &mp))) return rc;
+            if (workspace_bytes < lp.total + mp.total) return HMM_ERR_WORKSPACE;
+            char *wm = ws + lp.total;
+            if (log_alpha && W == Q32) scan_forward<Scan32>(A, pi, E, mp, eps, log_alpha, wm, st);
+            else if (log_alpha) scan_forward<Scan64>(A, pi, E, mp, eps, log_alpha, wm, st);
+            else if (W == Q32) scan_loglik<Scan32>(A, pi, E, mp, eps, wm, st);
+            else scan_loglik<Scan64>(A, pi, E, mp, eps, wm, st);
+            ll = (double *)(wm + mp.o_loglik);
+            mq_forward(A, pi, E, k, b, L, q, eps, nullptr, log_alpha, ll, st, (const int *)(wm + mp.o_need),
                        (MqSp *)(ws + lp.o_sp));
-        else
-            lq_forward(A, pi, E, lp, eps, ws, log_alpha, (hipStream_t)stream);
-        hipLaunchKernelGGL(k_copy_loglik, dim3((lp.NB + 255) / 256), dim3(256), 0, (hipStream_t)stream,
-                           (const double *)(ws + lp.o_ll), loglik, lp.NB);
+        } else if (q <= MQ_MAX) {                            // one wave per sequence, no launches per step
+            mq_forward(A, pi, E, k, b, L, q, eps, nullptr, log_alpha, ll, st, nullptr, (MqSp *)(ws + lp.o_sp));
+        } else {
+            lq_forward(A, pi, E, lp, eps, ws, log_alpha, st);
+        }
+        hipLaunchKernelGGL(k_copy_loglik, dim3((lp.NB + 255) / 256), dim3(256), 0, st, (const double *)ll, loglik, lp.NB);
         return check_launch();
     }
     Plan p;
     int rc = make_plan(log_alpha ? HMM_OP_FORWARD : HMM_OP_LOGLIK, k, b, L, q, &p);
     if (rc) return rc;
     if (!A || !pi || !E || !loglik) return HMM_ERR_NULL_POINTER;
-    if ((rc = check_ws(p, workspace, workspace_bytes))) return rc;
+    if ((rc = check_ws(p.total, workspace, workspace_bytes))) return rc;
     char *ws = (char *)workspace;
     hipStream_t st = (hipStream_t)stream;
     Plan px;
@@ -2900,28 +2880,17 @@ int hmm_backward(const float *A, const float *E, int k, int b, int L, int q, flo
         int rc = make_lqplan(k, b, L, q, &lp);
         if (rc) return rc;
         if (!A || !E || !log_beta) return HMM_ERR_NULL_POINTER;
-        if ((rc = lq_check(lp, workspace, workspace_bytes))) return rc;
-        if (q <= Q32) {
-            Plan32 p32;
-            if ((rc = make_plan32(HMM_OP_BACKWARD, k, b, L, q, &p32))) return rc;
-            if (workspace_bytes < lp.total + p32.total) return HMM_ERR_WORKSPACE;
-            char *w32 = (char *)workspace + lp.total;
-            scan32_backward(A, E, p32, eps, log_beta, w32, (hipStream_t)stream);
-            mq_backward(A, E, k, b, L, q, eps, log_beta, nullptr, 3, (hipStream_t)stream, (const int *)(w32 + p32.o_need),
+        if ((rc = check_ws(lp.total, workspace, workspace_bytes))) return rc;
+        if (const int W = mid_width(k, b, L, q)) {
+            MidPlan mp;
+            if ((rc = make_midplan(HMM_OP_BACKWARD, k, b, L, q, W, &mp))) return rc;
+            if (workspace_bytes < lp.total + mp.total) return HMM_ERR_WORKSPACE;
+            char *wm = (char *)workspace + lp.total;
+            if (W == Q32) scan_backward<Scan32>(A, E, mp, eps, log_beta, wm, (hipStream_t)stream);
+            else scan_backward<Scan64>(A, E, mp, eps, log_beta, wm, (hipStream_t)stream);
+            mq_backward(A, E, k, b, L, q, eps, log_beta, nullptr, 3, (hipStream_t)stream, (const int *)(wm + mp.o_need),
                         (MqSp *)((char *)workspace + lp.o_sp));
-            return check_launch();
-        }
-        if (scan64_wanted(k, b, L, q)) {
-            Plan64 p64;
-            if ((rc = make_plan64(HMM_OP_BACKWARD, k, b, L, q, &p64))) return rc;
-            if (workspace_bytes < lp.total + p64.total) return HMM_ERR_WORKSPACE;
-            char *w64 = (char *)workspace + lp.total;
-            scan64_backward(A, E, p64, eps, log_beta, w64, (hipStream_t)stream);
-            mq_backward(A, E, k, b, L, q, eps, log_beta, nullptr, 3, (hipStream_t)stream, (const int *)(w64 + p64.o_need),
-                        (MqSp *)((char *)workspace + lp.o_sp));
-            return check_launch();
-        }
-        if (q <= MQ_MAX)
+        } else if (q <= MQ_MAX)
             mq_backward(A, E, k, b, L, q, eps, log_beta, nullptr, 3, (hipStream_t)stream, nullptr,
                         (MqSp *)((char *)workspace + lp.o_sp));
         else
@@ -2932,7 +2901,7 @@ int hmm_backward(const float *A, const float *E, int k, int b, int L, int q, flo
     int rc = make_plan(HMM_OP_BACKWARD, k, b, L, q, &p);
     if (rc) return rc;
     if (!A || !E || !log_beta) return HMM_ERR_NULL_POINTER;
-    if ((rc = check_ws(p, workspace, workspace_bytes))) return rc;
+    if ((rc = check_ws(p.total, workspace, workspace_bytes))) return rc;
     char *ws = (char *)workspace;
     hipStream_t st = (hipStream_t)stream;
     // hmm_backward has no start distribution: the chunk scan's forward half (whose vectors weigh the certificate,
@@ -3071,41 +3040,23 @@ static int posterior_impl(const float *A, const float *pi, const float *E, int k
         if (rc) return rc;
         if (!A || !pi || !E || !out) return HMM_ERR_NULL_POINTER;
         if (mode < HMM_POST_PROB || mode > HMM_POST_LOG_NO_LL) return HMM_ERR_BAD_ARGUMENT;
-        if ((rc = lq_check(lp, workspace, workspace_bytes))) return rc;
+        if ((rc = check_ws(lp.total, workspace, workspace_bytes))) return rc;
         char *ws = (char *)workspace;
         hipStream_t st = (hipStream_t)stream;
-        if (q <= Q32) {
-            // 17..32 states: the chunked scan for the models it serves, the serial kernels for the rest
-            // and for the sequences the certificate flags (all decided on the device)
-            Plan32 p32;
-            if ((rc = make_plan32(HMM_OP_POSTERIOR, k, b, L, q, &p32))) return rc;
-            if (workspace_bytes < lp.total + p32.total) return HMM_ERR_WORKSPACE;
-            char *w32 = ws + lp.total;
-            scan32_posterior(A, pi, E, p32, eps, mode, out, w32, st);
-            const int *need = (const int *)(w32 + p32.o_need);
-            double *ll = (double *)(w32 + p32.o_loglik);
+        if (const int W = mid_width(k, b, L, q)) {
+            // 17..32 states, or few long sequences of 33..64: the chunked scan for the models it serves, the serial
+            // kernels for the rest and for the sequences the certificate flags (all decided on the device)
+            MidPlan mp;
+            if ((rc = make_midplan(HMM_OP_POSTERIOR, k, b, L, q, W, &mp))) return rc;
+            if (workspace_bytes < lp.total + mp.total) return HMM_ERR_WORKSPACE;
+            char *wm = ws + lp.total;
+            if (W == Q32) scan_posterior<Scan32>(A, pi, E, mp, eps, mode, out, wm, st);
+            else scan_posterior<Scan64>(A, pi, E, mp, eps, mode, out, wm, st);
+            const int *need = (const int *)(wm + mp.o_need);
+            double *ll = (double *)(wm + mp.o_loglik);
             if (mode != HMM_POST_LOG_NO_LL && L >= 2) {
                 mq_posterior2(A, pi, E, k, b, L, q, eps, out, ll, mode, st, need, (MqSp *)(ws + lp.o_sp));
             } else {
-                mq_forward(A, pi, E, k, b, L, q, eps, out, nullptr, ll, st, need, (MqSp *)(ws + lp.o_sp));
-                mq_backward(A, E, k, b, L, q, eps, out, (const double *)ll, mode, st, need, (MqSp *)(ws + lp.o_sp));
-            }
-            if (loglik)
-                hipLaunchKernelGGL(k_copy_loglik, dim3((lp.NB + 255) / 256), dim3(256), 0, st, (const double *)ll, loglik,
-                                   lp.NB);
-            return check_launch();
-        }
-        if (scan64_wanted(k, b, L, q)) {
-            Plan64 p64;
-            if ((rc = make_plan64(HMM_OP_POSTERIOR, k, b, L, q, &p64))) return rc;
-            if (workspace_bytes < lp.total + p64.total) return HMM_ERR_WORKSPACE;
-            char *w64 = ws + lp.total;
-            scan64_posterior(A, pi, E, p64, eps, mode, out, w64, st);
-            const int *need = (const int *)(w64 + p64.o_need);
-            double *ll = (double *)(w64 + p64.o_loglik);
-            if (mode != HMM_POST_LOG_NO_LL)
-                mq_posterior2(A, pi, E, k, b, L, q, eps, out, ll, mode, st, need, (MqSp *)(ws + lp.o_sp));
-            else {
                 mq_forward(A, pi, E, k, b, L, q, eps, out, nullptr, ll, st, need, (MqSp *)(ws + lp.o_sp));
                 mq_backward(A, E, k, b, L, q, eps, out, (const double *)ll, mode, st, need, (MqSp *)(ws + lp.o_sp));
             }
@@ -3134,8 +3085,7 @@ static int posterior_impl(const float *A, const float *pi, const float *E, int k
     if (rc) return rc;
     if (!A || !pi || !E || !out) return HMM_ERR_NULL_POINTER;
     if (mode < HMM_POST_PROB || mode > HMM_POST_LOG_NO_LL) return HMM_ERR_BAD_ARGUMENT;
-    if (!workspace) return HMM_ERR_NULL_POINTER;
-    if (workspace_bytes < G.total || ((uintptr_t)workspace & 255)) return HMM_ERR_WORKSPACE;
+    if ((rc = check_ws(G.total, workspace, workspace_bytes))) return rc;
     char *ws = (char *)workspace;
     hipStream_t st = (hipStream_t)stream;
 #ifdef HMM_GROUPS_SERIAL
@@ -3191,26 +3141,15 @@ int hmm_posterior(const float *A, const float *pi, const float *E, int k, int b,
 }
 
 long long hmm_exact_count(int op, int k, int b, int L, int q, const void *workspace, size_t workspace_bytes) {
-    if (q > QP && q <= Q32 && op != HMM_OP_VITERBI) {
+    if (const int W = op != HMM_OP_VITERBI ? mid_width(k, b, L, q) : 0) {
         // sequences of the last call that the one-wave-per-sequence kernels served
         LqPlan lp;
-        Plan32 p32;
-        if (make_lqplan(k, b, L, q, &lp) || make_plan32(op, k, b, L, q, &p32)) return HMM_ERR_BAD_SHAPE;
+        MidPlan mp;
+        if (make_lqplan(k, b, L, q, &lp) || make_midplan(op, k, b, L, q, W, &mp)) return HMM_ERR_BAD_SHAPE;
         if (!workspace) return HMM_ERR_NULL_POINTER;
-        if (workspace_bytes < lp.total + p32.total) return HMM_ERR_WORKSPACE;
+        if (workspace_bytes < lp.total + mp.total) return HMM_ERR_WORKSPACE;
         int v = 0;
-        if (hipMemcpy(&v, (const char *)workspace + lp.total + p32.o_nex, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
-            return HMM_ERR_LAUNCH;
-        return v;
-    }
-    if (scan64_wanted(k, b, L, q) && op != HMM_OP_VITERBI) {
-        LqPlan lp;
-        Plan64 p64;
-        if (make_lqplan(k, b, L, q, &lp) || make_plan64(op, k, b, L, q, &p64)) return HMM_ERR_BAD_SHAPE;
-        if (!workspace) return HMM_ERR_NULL_POINTER;
-        if (workspace_bytes < lp.total + p64.total) return HMM_ERR_WORKSPACE;
-        int v = 0;
-        if (hipMemcpy(&v, (const char *)workspace + lp.total + p64.o_nex, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+        if (hipMemcpy(&v, (const char *)workspace + lp.total + mp.o_nex, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
             return HMM_ERR_LAUNCH;
         return v;
     }
@@ -3240,42 +3179,39 @@ long long hmm_exact_count(int op, int k, int b, int L, int q, const void *worksp
 }
 
 int hmm_exact_detail(int k, int b, int L, int q, const void *workspace, size_t workspace_bytes, long long *detail) {
-    if (!workspace || !detail) return HMM_ERR_NULL_POINTER;
-    if (q > QP) return HMM_ERR_Q_UNSUPPORTED;
-    Groups G;
-    int rc = plan_groups(k, b, L, q, &G);
-    if (rc) return rc;
-    for (int i = 0; i < 5; ++i) detail[i] = 0;
-    for (int g = 0; g < G.n; ++g) {
-        const Plan &p = G.plan[g];
-        if (workspace_bytes < G.off[g] + p.total) return HMM_ERR_WORKSPACE;
-        int nx = 0, wc[4] = {0, 0, 0, 0};
-        const char *ws = (const char *)workspace + G.off[g];
-        if (hipMemcpy(&nx, ws + p.o_nexact, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(wc, ws + p.o_wcnt, sizeof(wc), hipMemcpyDeviceToHost) != hipSuccess)
-            return HMM_ERR_LAUNCH;
-        detail[0] += nx; detail[1] += wc[0]; detail[2] += wc[2]; detail[3] += wc[1]; detail[4] += wc[3];
-    }
-    return HMM_OK;
+    return hmm_exact_detail_op(HMM_OP_POSTERIOR, k, b, L, q, workspace, workspace_bytes, detail);
 }
 
 int hmm_exact_detail_op(int op, int k, int b, int L, int q, const void *workspace, size_t workspace_bytes,
                         long long *detail) {
-    if (op == HMM_OP_POSTERIOR) return hmm_exact_detail(k, b, L, q, workspace, workspace_bytes, detail);
     if (!workspace || !detail) return HMM_ERR_NULL_POINTER;
     if (q > QP) return HMM_ERR_Q_UNSUPPORTED;
+    // the routing counters of the plan at `off` in the workspace, added to detail[]
+    auto read = [&](const Plan &p, size_t off) -> int {
+        if (workspace_bytes < off + p.total) return HMM_ERR_WORKSPACE;
+        int nx = 0, wc[4] = {0, 0, 0, 0};
+        const char *ws = (const char *)workspace + off;
+        if (hipMemcpy(&nx, ws + p.o_nexact, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(wc, ws + p.o_wcnt, sizeof(wc), hipMemcpyDeviceToHost) != hipSuccess)
+            return HMM_ERR_LAUNCH;
+        detail[0] += nx; detail[1] += wc[0]; detail[2] += wc[2]; detail[3] += wc[1]; detail[4] += wc[3];
+        return HMM_OK;
+    };
+    int rc;
+    if (op == HMM_OP_POSTERIOR) {                            // one plan per group of sequences
+        Groups G;
+        if ((rc = plan_groups(k, b, L, q, &G))) return rc;
+        for (int i = 0; i < 5; ++i) detail[i] = 0;
+        for (int g = 0; g < G.n; ++g)
+            if ((rc = read(G.plan[g], G.off[g]))) return rc;
+        return HMM_OK;
+    }
     if (op != HMM_OP_LOGLIK && op != HMM_OP_FORWARD && op != HMM_OP_BACKWARD) return HMM_ERR_BAD_ARGUMENT;
     Plan p;
-    int rc = make_plan(op, k, b, L, q, &p);
-    if (rc) return rc;
+    if ((rc = make_plan(op, k, b, L, q, &p))) return rc;
     if (workspace_bytes < p.total) return HMM_ERR_WORKSPACE;
-    int nx = 0, wc[4] = {0, 0, 0, 0};
-    const char *ws = (const char *)workspace;
-    if (hipMemcpy(&nx, ws + p.o_nexact, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(wc, ws + p.o_wcnt, sizeof(wc), hipMemcpyDeviceToHost) != hipSuccess)
-        return HMM_ERR_LAUNCH;
-    detail[0] = nx; detail[1] = wc[0]; detail[2] = wc[2]; detail[3] = wc[1]; detail[4] = wc[3];
-    return HMM_OK;
+    for (int i = 0; i < 5; ++i) detail[i] = 0;
+    return read(p, 0);
 }
 
 int hmm_window_table(int op, int k, int b, int L, int q, const void *workspace, size_t workspace_bytes, int seq,

@@ -47,9 +47,9 @@
 //     exceeds PC_LOG_EXPOSED of sum w.
 
 struct PcPlan {
-    int W;                                   // states per row: 16 (main pipeline's scan plan) or 32 (hmm_scan32.inc's)
+    int W;                                   // states per row: 16 (main pipeline's scan plan) or 32 (hmm_scan_mid.inc's)
     Plan p;                                  // shape and chunks
-    Plan32 p32;                              // W = 32: the 32-state scan plan (its p is copied into `p`)
+    MidPlan p32;                             // W = 32: the 32-state scan plan (its p is copied into `p`)
     PgPlan pg;                               // AH, RB, dEa, S, per-sequence partials (shared with the serial sweeps)
     size_t o_ops, o_exps, o_prefix, o_suffix, o_route;       // inside the scan plan's part of the workspace
     size_t o_pg, o_c, o_lam, o_gpart, o_side, o_need, o_sp, total;
@@ -106,7 +106,7 @@ static int make_pcplan(int k, int b, int L, int q, PcPlan *pc) {
         pc->o_route = pc->p.o_topo;
         off = pc->p.total;
     } else {
-        int rc = make_plan32(HMM_OP_BACKWARD, k, b, L, q, &pc->p32, pc_chunk_len(k, b, L));
+        int rc = make_midplan(HMM_OP_BACKWARD, k, b, L, q, Q32, &pc->p32, pc_chunk_len(k, b, L));
         if (rc) return rc;
         pc->p = pc->p32.p;
         pc->o_ops = pc->p32.o_ops; pc->o_exps = pc->p32.o_exps; pc->o_prefix = pc->p32.o_prefix;
@@ -714,7 +714,7 @@ static int pc_launch(const float *A, const float *pi, const float *E, int k, int
         if (rc) return rc;
         return pc_launch_w<QP>(A, pi, E, k, b, L, q, eps, mode, G, dA, dpi, dE, ws, pc, st);
     }
-    scan32_reduce_scan(A, pi, E, pc.p32, eps, ws, st);
+    scan_reduce_scan<Scan32>(A, pi, E, pc.p32, eps, ws, st);
     return pc_launch_w<Q32>(A, pi, E, k, b, L, q, eps, mode, G, dA, dpi, dE, ws, pc, st);
 }
 
@@ -812,7 +812,7 @@ static int pc_loglik_grad(const float *A, const float *pi, const float *E, int k
     if (ws_bytes < pc.total || ((uintptr_t)ws & 255)) return HMM_ERR_WORKSPACE;
     const Plan &p = pc.p;
     const PgPlan &pp = pc.pg;
-    scan32_reduce_scan(A, pi, E, pc.p32, eps, ws, st);
+    scan_reduce_scan<Scan32>(A, pi, E, pc.p32, eps, ws, st);
     char *wp = ws + pc.o_pg;
     float *AH = (float *)(wp + pp.o_ah), *RB = (float *)(wp + pp.o_rb), *S = (float *)(wp + pp.o_s);
     float *gseq = (float *)(wp + pp.o_gpart), *gpart = (float *)(ws + pc.o_gpart), *inv_sg = (float *)(ws + pc.o_c);

@@ -19,53 +19,14 @@
 // one-wave-per-sequence kernels of hmm_midq.inc, which implement the cell's serial semantics exactly and
 // take a per-sequence mask.  hmm_posterior (all modes), hmm_forward and hmm_backward use this path; the
 // gradients run per chunk of this plan for up to 512 sequences (hmm_postgrad_chunked.inc), otherwise — and Viterbi
-// always — on hmm_midq.inc.
+// always — on hmm_midq.inc.  This file holds the kernels; the plan (MidPlan) and the host drivers (scan_*<Scan32>)
+// are shared with the 64-state rows: hmm_scan_mid.inc.
 
 #define Q32 32
 #define SUB32 4                       // steps per apply block = checkpoint spacing
 #define OUT32_ROWS 8                  // rows per chain staged in LDS per flush
 #define OUT32_STRIDE (OUT32_ROWS * Q32 + 4)
 #define OUT32_SEG (16 * OUT32_STRIDE + 32)
-
-struct Plan32 {
-    Plan p;                           // shape and chunking (k, b, L, q, NB, T, C, nchains; nsub = T / SUB32)
-    long long nwaves;                 // apply waves: 16 (sequence, chunk) pairs each, never straddling models
-    size_t o_ops, o_exps, o_prefix, o_llpre, o_suffix, o_lsuf, o_loglik, o_ckpt, o_phi, o_need, o_elig, o_nex, o_ll2;
-    size_t o_risk, o_upi, total;      // the dense reduce's per-chain mark; hmm_backward's uniform start distribution
-};
-
-static int make_plan32(int op, int k, int b, int L, int q, Plan32 *pp, int T_fixed = 0) {
-    if (k < 1 || b < 1 || L < 1 || q < 1) return HMM_ERR_BAD_SHAPE;
-    if ((long long)k * b > (1ll << 30) / 64) return HMM_ERR_BAD_SHAPE;
-    Plan &p = pp->p;
-    p.k = k; p.b = b; p.L = L; p.q = q; p.NB = k * b;
-    p.T = T_fixed ? T_fixed : choose_T(p.NB, L);
-    p.C = (L + p.T - 1) / p.T;
-    p.nsub = p.T / SUB32;
-    p.nchains = (long long)p.NB * p.C;
-    p.cpw = 16; p.seq_start = 1; p.G = 0; p.gsize = 0;
-    pp->nwaves = (long long)k * (((long long)b * p.C + 15) / 16);
-    size_t off = 0;
-    pp->o_ops = off;    off = align_up(off + (size_t)p.nchains * Q32 * Q32 * sizeof(float));
-    pp->o_exps = off;   off = align_up(off + (size_t)p.nchains * Q32 * sizeof(int));
-    pp->o_prefix = off; off = align_up(off + (size_t)p.nchains * Q32 * sizeof(float));
-    pp->o_llpre = off;  off = align_up(off + (size_t)p.nchains * sizeof(double));
-    pp->o_suffix = off; off = align_up(off + (size_t)p.nchains * Q32 * sizeof(float));
-    pp->o_lsuf = off;   off = align_up(off + (size_t)p.nchains * sizeof(double));
-    pp->o_loglik = off; off = align_up(off + (size_t)p.NB * sizeof(double));
-    pp->o_ll2 = off;    off = align_up(off + (size_t)p.NB * sizeof(double));
-    pp->o_phi = off;    off = align_up(off + (size_t)p.nchains * sizeof(float));
-    pp->o_need = off;   off = align_up(off + (size_t)p.NB * sizeof(int));
-    pp->o_elig = off;   off = align_up(off + (size_t)k * sizeof(int));
-    pp->o_nex = off;    off = align_up(off + sizeof(int));
-    pp->o_risk = off;   off = align_up(off + (size_t)p.nchains * sizeof(int));
-    pp->o_upi = off;    off = align_up(off + (size_t)k * q * sizeof(float));
-    pp->o_ckpt = off;
-    if (op == HMM_OP_POSTERIOR)
-        off = align_up(off + (size_t)pp->nwaves * p.nsub * 16 * Q32 * sizeof(float));
-    pp->total = off;
-    return HMM_OK;
-}
 
 // elig[m]: 0 = the serial kernels serve this model (support not primitive, or the routing is forced);
 // TopoGene29::ID (| TOPO_UNIT) = the chunked scan with the compiled sparse reduce; ID_DENSE32 = the chunked scan
@@ -811,108 +772,4 @@ __global__ __launch_bounds__(256) void k32_reduce_dense(const float *__restrict_
         const bool mark = __builtin_amdgcn_ballot_w64(risk) != 0ull;
         if (lane == 0) riskv[chain] = mark ? 1 : 0;
     }
-}
-
-// ---- host side
-
-static void scan32_reduce_scan(const float *A, const float *pi, const float *E, const Plan32 &pp, float eps, char *ws,
-                               hipStream_t st) {
-    const Plan &p = pp.p;
-    int *elig = (int *)(ws + pp.o_elig);
-    hipLaunchKernelGGL(k32_check, dim3(p.k), dim3(64), 0, st, A, elig, p.q, opt(HMM_OPT_EXACT), eps, (int *)(ws + pp.o_nex),
-                       opt(HMM_OPT_FORCE_DENSE) == 1 ? 1 : 0);
-    float *ops = (float *)(ws + pp.o_ops);
-    int *exps = (int *)(ws + pp.o_exps);
-    const unsigned nb = (unsigned)((p.nchains + 4 * RsCfg<TopoGene29>::CPW - 1) / (4 * RsCfg<TopoGene29>::CPW));
-    hipLaunchKernelGGL(k_reduce_sparse_wide<TopoGene29>, dim3(nb), dim3(256), 0, st, A, E, ops, exps, (const int *)elig, p, eps);
-    if (p.k > 1 || !HMM_RS_UNI)                // waves that straddle two models
-        hipLaunchKernelGGL((k_reduce_sparse_wide<TopoGene29, true>), dim3(nb), dim3(256), 0, st, A, E, ops, exps, (const int *)elig, p, eps);
-    {   // models outside the compiled topology: every chain its own wave (grid stride; exits at once otherwise)
-        const long long nbd = (p.nchains + 3) / 4;
-        hipLaunchKernelGGL(k32_reduce_dense, dim3((unsigned)(nbd < 8192 ? nbd : 8192)), dim3(256), 0, st, A, E, ops, exps,
-                           (int *)(ws + pp.o_risk), (const int *)elig, p, eps);
-    }
-    hipLaunchKernelGGL(k32_scan, dim3(p.NB), dim3(128), 0, st, pi, (const float *)ops, (const int *)exps,
-                       (float *)(ws + pp.o_prefix), (double *)(ws + pp.o_llpre), (float *)(ws + pp.o_suffix),
-                       (double *)(ws + pp.o_lsuf), (double *)(ws + pp.o_loglik), (const int *)elig, p, eps);
-}
-
-// need[] from the certificate sums phi (or null: the reduces' marks only)
-static void scan32_select(const Plan32 &pp, const float *phi, char *ws, hipStream_t st) {
-    const Plan &p = pp.p;
-    hipLaunchKernelGGL(k32_select, dim3((p.NB + 255) / 256), dim3(256), 0, st, (const int *)(ws + pp.o_elig), phi,
-                       (int *)(ws + pp.o_need), (int *)(ws + pp.o_nex), p, 0.f, opt(HMM_OPT_EXACT),
-                       (const int *)(ws + pp.o_exps), (const int *)(ws + pp.o_risk), Q32);
-}
-
-// log-likelihoods of the models the chunked path serves -> ws loglik; need[] for the others.  The log-likelihood comes
-// out of the chunk scan; the forward apply kernel runs for the certificate only (k32_forward<false, true>), as
-// hmm_forward's scan plan does for 16 states.
-static void scan32_loglik(const float *A, const float *pi, const float *E, const Plan32 &pp, float eps, char *ws,
-                          hipStream_t st) {
-    const Plan &p = pp.p;
-    scan32_reduce_scan(A, pi, E, pp, eps, ws, st);
-    const bool cert = opt(HMM_OPT_EXACT) == HMM_EXACT_AUTO;
-    float *phi = (float *)(ws + pp.o_phi);
-    if (cert)
-        hipLaunchKernelGGL((k32_forward<false, true>), dim3((unsigned)((pp.nwaves + 3) / 4)), dim3(256), 0, st, A, E,
-                           (const float *)(ws + pp.o_prefix), (const double *)nullptr, (float *)nullptr, (float *)nullptr,
-                           (const int *)(ws + pp.o_elig), p, eps, pp.nwaves, (const float *)(ws + pp.o_suffix), phi);
-    scan32_select(pp, cert ? phi : nullptr, ws, st);
-}
-
-static void scan32_posterior(const float *A, const float *pi, const float *E, const Plan32 &pp, float eps, int mode,
-                             float *out, char *ws, hipStream_t st) {
-    const Plan &p = pp.p;
-    scan32_reduce_scan(A, pi, E, pp, eps, ws, st);
-    const int *elig = (const int *)(ws + pp.o_elig);
-    float *ckpt = (float *)(ws + pp.o_ckpt);
-    const dim3 grid((unsigned)((pp.nwaves + 3) / 4));
-    hipLaunchKernelGGL(k32_forward<false>, grid, dim3(256), 0, st, A, E, (const float *)(ws + pp.o_prefix),
-                       (const double *)nullptr, ckpt, (float *)nullptr, elig, p, eps, pp.nwaves,
-                       (const float *)nullptr, (float *)nullptr);
-    const float *sx = (const float *)(ws + pp.o_suffix);
-    const double *ls = (const double *)(ws + pp.o_lsuf);
-    const double *ll = (const double *)(ws + pp.o_loglik);
-    float *phi = (float *)(ws + pp.o_phi);
-    if (mode == HMM_POST_PROB)
-        hipLaunchKernelGGL((k32_backward<0>), grid, dim3(256), 0, st, A, E, (const float *)ckpt, sx, ls, ll, out, phi, elig, p, eps, pp.nwaves,
-                           (const float *)nullptr);
-    else if (mode == HMM_POST_LOG)
-        hipLaunchKernelGGL((k32_backward<1>), grid, dim3(256), 0, st, A, E, (const float *)ckpt, sx, ls, ll, out, phi, elig, p, eps, pp.nwaves,
-                           (const float *)nullptr);
-    else
-        hipLaunchKernelGGL((k32_backward<2>), grid, dim3(256), 0, st, A, E, (const float *)ckpt, sx, ls, ll, out, phi, elig, p, eps, pp.nwaves,
-                           (const float *)nullptr);
-    scan32_select(pp, phi, ws, st);
-}
-
-// log alpha (and the log-likelihoods) of the models the chunked path serves; need[] for the others.  The certificate
-// variant runs whatever the routing mode, so that EXACT_OFF and the automatic routing compute an unflagged sequence
-// with the same kernel.
-static void scan32_forward(const float *A, const float *pi, const float *E, const Plan32 &pp, float eps, float *log_alpha,
-                           char *ws, hipStream_t st) {
-    const Plan &p = pp.p;
-    scan32_reduce_scan(A, pi, E, pp, eps, ws, st);
-    float *phi = (float *)(ws + pp.o_phi);
-    hipLaunchKernelGGL((k32_forward<true, true>), dim3((unsigned)((pp.nwaves + 3) / 4)), dim3(256), 0, st, A, E,
-                       (const float *)(ws + pp.o_prefix), (const double *)(ws + pp.o_llpre), (float *)nullptr, log_alpha,
-                       (const int *)(ws + pp.o_elig), p, eps, pp.nwaves, (const float *)(ws + pp.o_suffix), phi);
-    scan32_select(pp, phi, ws, st);
-}
-
-// log beta of the models the chunked path serves; need[] for the others.  hmm_backward has no start distribution: the
-// chunk scan's forward half, whose vectors weigh the certificate (k32_backward's CERT3), starts from the uniform one.
-static void scan32_backward(const float *A, const float *E, const Plan32 &pp, float eps, float *log_beta, char *ws,
-                            hipStream_t st) {
-    const Plan &p = pp.p;
-    float *upi = (float *)(ws + pp.o_upi);
-    (void)hipMemsetD32Async((hipDeviceptr_t)upi, __builtin_bit_cast(int, 1.0f / (float)p.q), (size_t)p.k * p.q, st);
-    scan32_reduce_scan(A, upi, E, pp, eps, ws, st);
-    float *phi = (float *)(ws + pp.o_phi);
-    hipLaunchKernelGGL((k32_backward<3, true>), dim3((unsigned)((pp.nwaves + 3) / 4)), dim3(256), 0, st, A, E,
-                       (const float *)nullptr, (const float *)(ws + pp.o_suffix), (const double *)(ws + pp.o_lsuf),
-                       (const double *)nullptr, log_beta, phi, (const int *)(ws + pp.o_elig), p, eps, pp.nwaves,
-                       (const float *)(ws + pp.o_prefix));
-    scan32_select(pp, phi, ws, st);
 }

@@ -19,7 +19,8 @@
 // (scan64_wanted) and only for models whose support is primitive (k64_check, B^4096 > 0: Wielandt's (q-1)^2 + 1 =
 // 3970 for q = 64); everything else — larger batches, reducible models, sequences whose psi is above EXACT_DELTA —
 // is served by the one-wave-per-sequence kernels, which take a per-sequence mask.  hmm_posterior (all modes),
-// hmm_forward and hmm_backward; gradients and Viterbi stay on hmm_midq.inc.
+// hmm_forward and hmm_backward; gradients and Viterbi stay on hmm_midq.inc.  This file holds the kernels; the plan
+// (MidPlan) and the host drivers (scan_*<Scan64>) are shared with the 32-state rows: hmm_scan_mid.inc.
 
 #define Q64 64
 #define SUB64 2                       // steps per apply block = checkpoint spacing
@@ -32,44 +33,6 @@
 
 static bool scan64_wanted(int k, int b, int L, int q) {
     return q > Q32 && q <= Q64 && (long long)k * b <= SCAN64_MAX_SEQ && L >= SCAN64_MIN_LEN;
-}
-
-struct Plan64 {
-    Plan p;                           // shape and chunking (nsub = T / SUB64)
-    long long nwaves;                 // apply waves: 16 (sequence, chunk) pairs each, never straddling models
-    size_t o_ops, o_exps, o_prefix, o_llpre, o_suffix, o_lsuf, o_loglik, o_ckpt, o_phi, o_need, o_elig, o_nex;
-    size_t o_risk, o_upi, total;      // the dense reduce's per-chain mark; hmm_backward's uniform start distribution
-};
-
-static int make_plan64(int op, int k, int b, int L, int q, Plan64 *pp) {
-    if (k < 1 || b < 1 || L < 1 || q < 1) return HMM_ERR_BAD_SHAPE;
-    Plan &p = pp->p;
-    p.k = k; p.b = b; p.L = L; p.q = q; p.NB = k * b;
-    p.T = choose_T(p.NB, L);
-    p.C = (L + p.T - 1) / p.T;
-    p.nsub = p.T / SUB64;
-    p.nchains = (long long)p.NB * p.C;
-    p.cpw = 16; p.seq_start = 1; p.G = 0; p.gsize = 0;
-    pp->nwaves = (long long)k * (((long long)b * p.C + 15) / 16);
-    size_t off = 0;
-    pp->o_ops = off;    off = align_up(off + (size_t)p.nchains * Q64 * Q64 * sizeof(float));
-    pp->o_exps = off;   off = align_up(off + (size_t)p.nchains * Q64 * sizeof(int));
-    pp->o_prefix = off; off = align_up(off + (size_t)p.nchains * Q64 * sizeof(float));
-    pp->o_llpre = off;  off = align_up(off + (size_t)p.nchains * sizeof(double));
-    pp->o_suffix = off; off = align_up(off + (size_t)p.nchains * Q64 * sizeof(float));
-    pp->o_lsuf = off;   off = align_up(off + (size_t)p.nchains * sizeof(double));
-    pp->o_loglik = off; off = align_up(off + (size_t)p.NB * sizeof(double));
-    pp->o_phi = off;    off = align_up(off + (size_t)p.nchains * sizeof(float));
-    pp->o_need = off;   off = align_up(off + (size_t)p.NB * sizeof(int));
-    pp->o_elig = off;   off = align_up(off + (size_t)k * sizeof(int));
-    pp->o_nex = off;    off = align_up(off + sizeof(int));
-    pp->o_risk = off;   off = align_up(off + (size_t)p.nchains * sizeof(int));
-    pp->o_upi = off;    off = align_up(off + (size_t)k * q * sizeof(float));
-    pp->o_ckpt = off;
-    if (op == HMM_OP_POSTERIOR)
-        off = align_up(off + (size_t)pp->nwaves * p.nsub * 16 * Q64 * sizeof(float));
-    pp->total = off;
-    return HMM_OK;
 }
 
 // elig[m]: ID_DENSE64 = the chunked scan serves this model (primitive support), 0 = the serial kernels do
@@ -669,95 +632,4 @@ __global__ __launch_bounds__(256) void k64_backward(const float *__restrict__ A,
         c = fmaxf(c, dn > 0.f ? dot64(ep, Gv) * __builtin_amdgcn_rcpf(dn) : 0.f);
         if (g == 0 && tl.valid) phi[tl.chain] = c;
     }
-}
-
-// ---- host side
-
-static void scan64_reduce_scan(const float *A, const float *pi, const float *E, const Plan64 &pp, float eps, char *ws,
-                               hipStream_t st) {
-    const Plan &p = pp.p;
-    int *elig = (int *)(ws + pp.o_elig);
-    hipLaunchKernelGGL(k64_check, dim3(p.k), dim3(64), 0, st, A, elig, p.q, opt(HMM_OPT_EXACT), eps, (int *)(ws + pp.o_nex),
-                       p.NB, opt(HMM_OPT_FORCE_DENSE) == 1 ? 1 : 0);
-    float *ops = (float *)(ws + pp.o_ops);
-    int *exps = (int *)(ws + pp.o_exps);
-    const long long nbd = (p.nchains + 3) / 4;
-    hipLaunchKernelGGL(k64_reduce_dense, dim3((unsigned)(nbd < 8192 ? nbd : 8192)), dim3(256), 0, st, A, E, ops, exps,
-                       (int *)(ws + pp.o_risk), (const int *)elig, p, eps);
-    hipLaunchKernelGGL(k64_scan, dim3(p.NB), dim3(128), 0, st, pi, (const float *)ops, (const int *)exps,
-                       (float *)(ws + pp.o_prefix), (double *)(ws + pp.o_llpre), (float *)(ws + pp.o_suffix),
-                       (double *)(ws + pp.o_lsuf), (double *)(ws + pp.o_loglik), (const int *)elig, p, eps);
-}
-
-static void scan64_select(const Plan64 &pp, const float *phi, char *ws, hipStream_t st) {
-    const Plan &p = pp.p;
-    hipLaunchKernelGGL(k32_select, dim3((p.NB + 255) / 256), dim3(256), 0, st, (const int *)(ws + pp.o_elig), phi,
-                       (int *)(ws + pp.o_need), (int *)(ws + pp.o_nex), p, 0.f, opt(HMM_OPT_EXACT),
-                       (const int *)(ws + pp.o_exps), (const int *)(ws + pp.o_risk), Q64);
-}
-
-// log-likelihoods of the models the chunked path serves -> ws loglik; need[] for the others (scan32_loglik)
-static void scan64_loglik(const float *A, const float *pi, const float *E, const Plan64 &pp, float eps, char *ws,
-                          hipStream_t st) {
-    const Plan &p = pp.p;
-    scan64_reduce_scan(A, pi, E, pp, eps, ws, st);
-    const bool cert = opt(HMM_OPT_EXACT) == HMM_EXACT_AUTO;
-    float *phi = (float *)(ws + pp.o_phi);
-    if (cert)
-        hipLaunchKernelGGL((k64_forward<false, true>), dim3((unsigned)((pp.nwaves + 3) / 4)), dim3(256), 0, st, A, E,
-                           (const float *)(ws + pp.o_prefix), (const double *)nullptr, (float *)nullptr, (float *)nullptr,
-                           (const int *)(ws + pp.o_elig), p, eps, pp.nwaves, (const float *)(ws + pp.o_suffix), phi);
-    scan64_select(pp, cert ? phi : nullptr, ws, st);
-}
-
-static void scan64_posterior(const float *A, const float *pi, const float *E, const Plan64 &pp, float eps, int mode,
-                             float *out, char *ws, hipStream_t st) {
-    const Plan &p = pp.p;
-    scan64_reduce_scan(A, pi, E, pp, eps, ws, st);
-    const int *elig = (const int *)(ws + pp.o_elig);
-    float *ckpt = (float *)(ws + pp.o_ckpt);
-    const dim3 grid((unsigned)((pp.nwaves + 3) / 4));
-    hipLaunchKernelGGL(k64_forward<false>, grid, dim3(256), 0, st, A, E, (const float *)(ws + pp.o_prefix),
-                       (const double *)nullptr, ckpt, (float *)nullptr, elig, p, eps, pp.nwaves,
-                       (const float *)nullptr, (float *)nullptr);
-    const float *sx = (const float *)(ws + pp.o_suffix);
-    const double *ls = (const double *)(ws + pp.o_lsuf);
-    const double *ll = (const double *)(ws + pp.o_loglik);
-    float *phi = (float *)(ws + pp.o_phi);
-    if (mode == HMM_POST_PROB)
-        hipLaunchKernelGGL((k64_backward<0>), grid, dim3(256), 0, st, A, E, (const float *)ckpt, sx, ls, ll, out, phi, elig, p, eps, pp.nwaves,
-                           (const float *)nullptr);
-    else if (mode == HMM_POST_LOG)
-        hipLaunchKernelGGL((k64_backward<1>), grid, dim3(256), 0, st, A, E, (const float *)ckpt, sx, ls, ll, out, phi, elig, p, eps, pp.nwaves,
-                           (const float *)nullptr);
-    else
-        hipLaunchKernelGGL((k64_backward<2>), grid, dim3(256), 0, st, A, E, (const float *)ckpt, sx, ls, ll, out, phi, elig, p, eps, pp.nwaves,
-                           (const float *)nullptr);
-    scan64_select(pp, phi, ws, st);
-}
-
-// (scan32_forward)
-static void scan64_forward(const float *A, const float *pi, const float *E, const Plan64 &pp, float eps, float *log_alpha,
-                           char *ws, hipStream_t st) {
-    scan64_reduce_scan(A, pi, E, pp, eps, ws, st);
-    float *phi = (float *)(ws + pp.o_phi);
-    hipLaunchKernelGGL((k64_forward<true, true>), dim3((unsigned)((pp.nwaves + 3) / 4)), dim3(256), 0, st, A, E,
-                       (const float *)(ws + pp.o_prefix), (const double *)(ws + pp.o_llpre), (float *)nullptr, log_alpha,
-                       (const int *)(ws + pp.o_elig), pp.p, eps, pp.nwaves, (const float *)(ws + pp.o_suffix), phi);
-    scan64_select(pp, phi, ws, st);
-}
-
-// (scan32_backward: the chunk scan starts from the uniform distribution)
-static void scan64_backward(const float *A, const float *E, const Plan64 &pp, float eps, float *log_beta, char *ws,
-                            hipStream_t st) {
-    const Plan &p = pp.p;
-    float *upi = (float *)(ws + pp.o_upi);
-    (void)hipMemsetD32Async((hipDeviceptr_t)upi, __builtin_bit_cast(int, 1.0f / (float)p.q), (size_t)p.k * p.q, st);
-    scan64_reduce_scan(A, upi, E, pp, eps, ws, st);
-    float *phi = (float *)(ws + pp.o_phi);
-    hipLaunchKernelGGL((k64_backward<3, true>), dim3((unsigned)((pp.nwaves + 3) / 4)), dim3(256), 0, st, A, E,
-                       (const float *)nullptr, (const float *)(ws + pp.o_suffix), (const double *)(ws + pp.o_lsuf),
-                       (const double *)nullptr, log_beta, phi, (const int *)(ws + pp.o_elig), p, eps, pp.nwaves,
-                       (const float *)(ws + pp.o_prefix));
-    scan64_select(pp, phi, ws, st);
 }

@@ -1,0 +1,199 @@
+// hmm_scan_mid.inc — host side of the chunked scan for 17..64 states, included by hmm_engine.hip after the kernels
+// of both row widths (hmm_scan32.inc, hmm_scan64.inc): one plan, one set of drivers.  What differs between the two
+// widths lives in the traits types Scan32 / Scan64 and nowhere else.
+
+struct MidPlan {
+    Plan p;                           // shape and chunking (k, b, L, q, NB, T, C, nchains; nsub = T / the width's SUB)
+    long long nwaves;                 // apply waves: 16 (sequence, chunk) pairs each, never straddling models
+    size_t o_ops, o_exps, o_prefix, o_llpre, o_suffix, o_lsuf, o_loglik, o_ckpt, o_phi, o_need, o_elig, o_nex;
+    size_t o_risk, o_upi, total;      // the dense reduce's per-chain mark; hmm_backward's uniform start distribution
+};
+
+// W: the row width, Q32 or Q64.  T_fixed: a chunk length other than choose_T's (hmm_postgrad_chunked.inc).
+static int make_midplan(int op, int k, int b, int L, int q, int W, MidPlan *pp, int T_fixed = 0) {
+    if (k < 1 || b < 1 || L < 1 || q < 1) return HMM_ERR_BAD_SHAPE;
+    if ((long long)k * b > (1ll << 30) / 64) return HMM_ERR_BAD_SHAPE;
+    Plan &p = pp->p;
+    p.k = k; p.b = b; p.L = L; p.q = q; p.NB = k * b;
+    p.T = T_fixed ? T_fixed : choose_T(p.NB, L);
+    p.C = (L + p.T - 1) / p.T;
+    p.nsub = p.T / (W == Q32 ? SUB32 : SUB64);
+    p.nchains = (long long)p.NB * p.C;
+    p.cpw = 16; p.seq_start = 1; p.G = 0; p.gsize = 0;
+    pp->nwaves = (long long)k * (((long long)b * p.C + 15) / 16);
+    size_t off = 0;
+    pp->o_ops = off;    off = align_up(off + (size_t)p.nchains * W * W * sizeof(float));
+    pp->o_exps = off;   off = align_up(off + (size_t)p.nchains * W * sizeof(int));
+    pp->o_prefix = off; off = align_up(off + (size_t)p.nchains * W * sizeof(float));
+    pp->o_llpre = off;  off = align_up(off + (size_t)p.nchains * sizeof(double));
+    pp->o_suffix = off; off = align_up(off + (size_t)p.nchains * W * sizeof(float));
+    pp->o_lsuf = off;   off = align_up(off + (size_t)p.nchains * sizeof(double));
+    pp->o_loglik = off; off = align_up(off + (size_t)p.NB * sizeof(double));
+    pp->o_phi = off;    off = align_up(off + (size_t)p.nchains * sizeof(float));
+    pp->o_need = off;   off = align_up(off + (size_t)p.NB * sizeof(int));
+    pp->o_elig = off;   off = align_up(off + (size_t)k * sizeof(int));
+    pp->o_nex = off;    off = align_up(off + sizeof(int));
+    pp->o_risk = off;   off = align_up(off + (size_t)p.nchains * sizeof(int));
+    pp->o_upi = off;    off = align_up(off + (size_t)k * q * sizeof(float));
+    pp->o_ckpt = off;
+    if (op == HMM_OP_POSTERIOR)
+        off = align_up(off + (size_t)pp->nwaves * p.nsub * 16 * W * sizeof(float));
+    pp->total = off;
+    return HMM_OK;
+}
+
+// the row width serving (k, b, L, q): Q32 for 17..32 states, Q64 for few long sequences of 33..64, 0 = no chunked scan
+static int mid_width(int k, int b, int L, int q) {
+    if (q > QP && q <= Q32) return Q32;
+    return scan64_wanted(k, b, L, q) ? Q64 : 0;
+}
+
+// ---- what differs between the widths: the constants, how the model check and the reduce stage are launched, and
+// which scan / apply kernels run
+struct Scan32 {
+    static constexpr int W = Q32;
+    static void check(const float *A, const MidPlan &pp, float eps, char *ws, hipStream_t st) {
+        hipLaunchKernelGGL(k32_check, dim3(pp.p.k), dim3(64), 0, st, A, (int *)(ws + pp.o_elig), pp.p.q, opt(HMM_OPT_EXACT),
+                           eps, (int *)(ws + pp.o_nex), opt(HMM_OPT_FORCE_DENSE) == 1 ? 1 : 0);
+    }
+    // the compiled sparse topology first, then the dense reduce for the models outside it
+    static void reduce(const float *A, const float *E, const MidPlan &pp, float eps, char *ws, hipStream_t st) {
+        const Plan &p = pp.p;
+        float *ops = (float *)(ws + pp.o_ops);
+        int *exps = (int *)(ws + pp.o_exps);
+        const int *elig = (const int *)(ws + pp.o_elig);
+        const unsigned nb = (unsigned)((p.nchains + 4 * RsCfg<TopoGene29>::CPW - 1) / (4 * RsCfg<TopoGene29>::CPW));
+        hipLaunchKernelGGL(k_reduce_sparse_wide<TopoGene29>, dim3(nb), dim3(256), 0, st, A, E, ops, exps, elig, p, eps);
+        if (p.k > 1 || !HMM_RS_UNI)                // waves that straddle two models
+            hipLaunchKernelGGL((k_reduce_sparse_wide<TopoGene29, true>), dim3(nb), dim3(256), 0, st, A, E, ops, exps, elig, p, eps);
+        // every chain its own wave (grid stride; exits at once for the models the sparse kernels served)
+        const long long nbd = (p.nchains + 3) / 4;
+        hipLaunchKernelGGL(k32_reduce_dense, dim3((unsigned)(nbd < 8192 ? nbd : 8192)), dim3(256), 0, st, A, E, ops, exps,
+                           (int *)(ws + pp.o_risk), elig, p, eps);
+    }
+    template <class... Args> static void scan(dim3 grid, hipStream_t st, Args... args) {
+        hipLaunchKernelGGL(k32_scan, grid, dim3(128), 0, st, args...);
+    }
+    template <bool LOGA, bool CERT, class... Args> static void forward(dim3 grid, hipStream_t st, Args... args) {
+        hipLaunchKernelGGL((k32_forward<LOGA, CERT>), grid, dim3(256), 0, st, args...);
+    }
+    template <int MODE, bool CERT3, class... Args> static void backward(dim3 grid, hipStream_t st, Args... args) {
+        hipLaunchKernelGGL((k32_backward<MODE, CERT3>), grid, dim3(256), 0, st, args...);
+    }
+};
+
+struct Scan64 {
+    static constexpr int W = Q64;
+    static void check(const float *A, const MidPlan &pp, float eps, char *ws, hipStream_t st) {
+        hipLaunchKernelGGL(k64_check, dim3(pp.p.k), dim3(64), 0, st, A, (int *)(ws + pp.o_elig), pp.p.q, opt(HMM_OPT_EXACT),
+                           eps, (int *)(ws + pp.o_nex), pp.p.NB, opt(HMM_OPT_FORCE_DENSE) == 1 ? 1 : 0);
+    }
+    static void reduce(const float *A, const float *E, const MidPlan &pp, float eps, char *ws, hipStream_t st) {
+        const Plan &p = pp.p;
+        const long long nbd = (p.nchains + 3) / 4;
+        hipLaunchKernelGGL(k64_reduce_dense, dim3((unsigned)(nbd < 8192 ? nbd : 8192)), dim3(256), 0, st, A, E,
+                           (float *)(ws + pp.o_ops), (int *)(ws + pp.o_exps), (int *)(ws + pp.o_risk),
+                           (const int *)(ws + pp.o_elig), p, eps);
+    }
+    template <class... Args> static void scan(dim3 grid, hipStream_t st, Args... args) {
+        hipLaunchKernelGGL(k64_scan, grid, dim3(128), 0, st, args...);
+    }
+    template <bool LOGA, bool CERT, class... Args> static void forward(dim3 grid, hipStream_t st, Args... args) {
+        hipLaunchKernelGGL((k64_forward<LOGA, CERT>), grid, dim3(256), 0, st, args...);
+    }
+    template <int MODE, bool CERT3, class... Args> static void backward(dim3 grid, hipStream_t st, Args... args) {
+        hipLaunchKernelGGL((k64_backward<MODE, CERT3>), grid, dim3(256), 0, st, args...);
+    }
+};
+
+// ---- the drivers, S = Scan32 or Scan64
+
+template <class S>
+static void scan_reduce_scan(const float *A, const float *pi, const float *E, const MidPlan &pp, float eps, char *ws,
+                             hipStream_t st) {
+    const Plan &p = pp.p;
+    S::check(A, pp, eps, ws, st);
+    S::reduce(A, E, pp, eps, ws, st);
+    S::scan(dim3(p.NB), st, pi, (const float *)(ws + pp.o_ops), (const int *)(ws + pp.o_exps), (float *)(ws + pp.o_prefix),
+            (double *)(ws + pp.o_llpre), (float *)(ws + pp.o_suffix), (double *)(ws + pp.o_lsuf),
+            (double *)(ws + pp.o_loglik), (const int *)(ws + pp.o_elig), p, eps);
+}
+
+// need[] from the certificate sums phi (or null: the reduces' marks only); k32_select serves both widths
+template <class S>
+static void scan_select(const MidPlan &pp, const float *phi, char *ws, hipStream_t st) {
+    const Plan &p = pp.p;
+    hipLaunchKernelGGL(k32_select, dim3((p.NB + 255) / 256), dim3(256), 0, st, (const int *)(ws + pp.o_elig), phi,
+                       (int *)(ws + pp.o_need), (int *)(ws + pp.o_nex), p, 0.f, opt(HMM_OPT_EXACT),
+                       (const int *)(ws + pp.o_exps), (const int *)(ws + pp.o_risk), S::W);
+}
+
+// log-likelihoods of the models the chunked path serves -> ws loglik; need[] for the others.  The log-likelihood comes
+// out of the chunk scan; the forward apply kernel runs for the certificate only (forward<false, true>), as
+// hmm_forward's scan plan does for 16 states.
+template <class S>
+static void scan_loglik(const float *A, const float *pi, const float *E, const MidPlan &pp, float eps, char *ws,
+                        hipStream_t st) {
+    scan_reduce_scan<S>(A, pi, E, pp, eps, ws, st);
+    const bool cert = opt(HMM_OPT_EXACT) == HMM_EXACT_AUTO;
+    float *phi = (float *)(ws + pp.o_phi);
+    if (cert)
+        S::template forward<false, true>(dim3((unsigned)((pp.nwaves + 3) / 4)), st, A, E, (const float *)(ws + pp.o_prefix),
+                                         nullptr, nullptr, nullptr, (const int *)(ws + pp.o_elig), pp.p, eps, pp.nwaves,
+                                         (const float *)(ws + pp.o_suffix), phi);
+    scan_select<S>(pp, cert ? phi : nullptr, ws, st);
+}
+
+template <class S>
+static void scan_posterior(const float *A, const float *pi, const float *E, const MidPlan &pp, float eps, int mode,
+                           float *out, char *ws, hipStream_t st) {
+    const Plan &p = pp.p;
+    scan_reduce_scan<S>(A, pi, E, pp, eps, ws, st);
+    const int *elig = (const int *)(ws + pp.o_elig);
+    float *ckpt = (float *)(ws + pp.o_ckpt);
+    const dim3 grid((unsigned)((pp.nwaves + 3) / 4));
+    S::template forward<false, false>(grid, st, A, E, (const float *)(ws + pp.o_prefix), nullptr, ckpt, nullptr, elig, p, eps,
+                                      pp.nwaves, nullptr, nullptr);
+    const float *sx = (const float *)(ws + pp.o_suffix);
+    const double *ls = (const double *)(ws + pp.o_lsuf);
+    const double *ll = (const double *)(ws + pp.o_loglik);
+    float *phi = (float *)(ws + pp.o_phi);
+    if (mode == HMM_POST_PROB)
+        S::template backward<0, false>(grid, st, A, E, ckpt, sx, ls, ll, out, phi, elig, p, eps, pp.nwaves, nullptr);
+    else if (mode == HMM_POST_LOG)
+        S::template backward<1, false>(grid, st, A, E, ckpt, sx, ls, ll, out, phi, elig, p, eps, pp.nwaves, nullptr);
+    else
+        S::template backward<2, false>(grid, st, A, E, ckpt, sx, ls, ll, out, phi, elig, p, eps, pp.nwaves, nullptr);
+    scan_select<S>(pp, phi, ws, st);
+}
+
+// log alpha (and the log-likelihoods) of the models the chunked path serves; need[] for the others.  The certificate
+// variant runs whatever the routing mode, so that EXACT_OFF and the automatic routing compute an unflagged sequence
+// with the same kernel.
+template <class S>
+static void scan_forward(const float *A, const float *pi, const float *E, const MidPlan &pp, float eps, float *log_alpha,
+                         char *ws, hipStream_t st) {
+    scan_reduce_scan<S>(A, pi, E, pp, eps, ws, st);
+    float *phi = (float *)(ws + pp.o_phi);
+    S::template forward<true, true>(dim3((unsigned)((pp.nwaves + 3) / 4)), st, A, E, (const float *)(ws + pp.o_prefix),
+                                    (const double *)(ws + pp.o_llpre), nullptr, log_alpha, (const int *)(ws + pp.o_elig),
+                                    pp.p, eps, pp.nwaves, (const float *)(ws + pp.o_suffix), phi);
+    scan_select<S>(pp, phi, ws, st);
+}
+
+// log beta of the models the chunked path serves; need[] for the others.  hmm_backward has no start distribution: the
+// chunk scan's forward half, whose vectors weigh the certificate (the backward kernel's CERT3), starts from the
+// uniform one.
+template <class S>
+static void scan_backward(const float *A, const float *E, const MidPlan &pp, float eps, float *log_beta, char *ws,
+                          hipStream_t st) {
+    const Plan &p = pp.p;
+    float *upi = (float *)(ws + pp.o_upi);
+    (void)hipMemsetD32Async((hipDeviceptr_t)upi, __builtin_bit_cast(int, 1.0f / (float)p.q), (size_t)p.k * p.q, st);
+    scan_reduce_scan<S>(A, upi, E, pp, eps, ws, st);
+    float *phi = (float *)(ws + pp.o_phi);
+    S::template backward<3, true>(dim3((unsigned)((pp.nwaves + 3) / 4)), st, A, E, nullptr,
+                                  (const float *)(ws + pp.o_suffix), (const double *)(ws + pp.o_lsuf), nullptr, log_beta,
+                                  phi, (const int *)(ws + pp.o_elig), p, eps, pp.nwaves, (const float *)(ws + pp.o_prefix));
+    scan_select<S>(pp, phi, ws, st);
+}

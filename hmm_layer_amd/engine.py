@@ -5,6 +5,7 @@ fallback: if the library is missing or a tensor is not on a HIP device these fun
 raise.  Shapes follow the reference (k models, b sequences, L positions, q states):
 A (k,q,q), pi (k,q) or (1,k,q), E (k,b,L,q).
 """
+import contextlib
 import ctypes
 import os
 
@@ -31,6 +32,72 @@ class EngineError(RuntimeError):
     pass
 
 
+_P, _I, _F, _SZ, _LL = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_longlong
+_FORWARD = [_P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _SZ, _P]
+_POSTERIOR = [_P, _P, _P, _I, _I, _I, _I, _F, _I, _P, _P, _P, _SZ, _P]
+_VITERBI = [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]
+_LOGLIK_GRAD = [_P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _SZ, _P]
+_POSTERIOR_GRAD = [_P, _P, _P, _I, _I, _I, _I, _F, _I, _P, _P, _P, _P, _P, _SZ, _P]
+_EMITTER = [_P, _I, _I, _I, _P, _I, _P, _P, _I, _P, _I, _F, _F, _I]
+_LAST_CALL = [_I, _I, _I, _I, _P, _SZ]          # (k, b, L, q, workspace, bytes): readers of the last call's records
+
+# Every function of include/hmm_engine.h that this module calls: symbol -> (restype, argtypes).
+_SIGNATURES = {
+    "hmm_strerror": (ctypes.c_char_p, [_I]),
+    "hmm_abi_version": (_I, []),
+    "hmm_set_option": (_I, [_I, _I]),
+    "hmm_get_option": (_I, [_I]),
+    "hmm_max_states": (_I, []),
+    "hmm_scan_max_states": (_I, []),
+    "hmm_largeq_tile_cols": (_I, [_I, _I]),
+    "hmm_chunk_len": (_I, [_I] * 4),
+    "hmm_workspace_bytes": (_SZ, [_I] * 5),
+    "hmm_forward": (_I, _FORWARD),
+    "hmm_backward": (_I, [_P, _P, _I, _I, _I, _I, _F, _P, _P, _SZ, _P]),
+    "hmm_posterior": (_I, _POSTERIOR),
+    "hmm_exact_count": (_LL, [_I] + _LAST_CALL),
+    "hmm_exact_detail_op": (_I, [_I] + _LAST_CALL + [_P]),
+    "hmm_window_table": (_I, [_I] + _LAST_CALL + [_I, _P, _P, _P, _I]),
+    "hmm_profile_create": (_P, []),
+    "hmm_profile_destroy": (None, [_P]),
+    "hmm_posterior_profiled": (_I, _POSTERIOR + [_P]),
+    "hmm_profile_read": (_I, [_P, _P, _P]),
+    "hmm_viterbi_max_states": (_I, []),
+    "hmm_viterbi_workspace_bytes": (_SZ, [_I] * 4),
+    "hmm_viterbi": (_I, _VITERBI),
+    "hmm_viterbi_scan_max_states": (_I, []),
+    "hmm_viterbi_scan_chunk_len": (_I, [_I] * 4),
+    "hmm_viterbi_scan_pays": (_I, [_I] * 4),
+    "hmm_viterbi_scan_workspace_bytes": (_SZ, [_I] * 4),
+    "hmm_viterbi_scan": (_I, _VITERBI),
+    "hmm_viterbi_large_max_states": (_I, []),
+    "hmm_viterbi_large_workspace_bytes": (_SZ, [_I] * 4),
+    "hmm_viterbi_large": (_I, _VITERBI),
+    "hmm_grad_max_states": (_I, []),
+    "hmm_loglik_grad_workspace_bytes": (_SZ, [_I] * 4),
+    "hmm_loglik_grad": (_I, _LOGLIK_GRAD),
+    "hmm_loglik_grad_serial_count": (_LL, _LAST_CALL),
+    "hmm_loglik_grad_large_max_states": (_I, []),
+    "hmm_loglik_grad_large_workspace_bytes": (_SZ, [_I] * 4),
+    "hmm_loglik_grad_large": (_I, _LOGLIK_GRAD),
+    "hmm_posterior_grad_max_states": (_I, []),
+    "hmm_posterior_grad_workspace_bytes": (_SZ, [_I] * 4),
+    "hmm_posterior_grad": (_I, _POSTERIOR_GRAD),
+    "hmm_posterior_grad_serial_count": (_LL, _LAST_CALL),
+    "hmm_posterior_grad_large_max_states": (_I, []),
+    "hmm_posterior_grad_large_workspace_bytes": (_SZ, [_I] * 4),
+    "hmm_posterior_grad_large": (_I, _POSTERIOR_GRAD),
+    "hmm_gene_emissions": (_I, _EMITTER + [_P, _P]),
+    "hmm_gene_emissions_grad_workspace_bytes": (_SZ, [_I] * 5),
+    "hmm_gene_emissions_grad": (_I, _EMITTER + [_P, _P, _P, _P, _SZ, _P]),
+    "hmm_loglik_partials": (_I, [_P, _P, _I, _I, _P, _P]),
+    "hmm_loglik_allreduce": (_I, [_P, _P, _I, _P]),
+    "hmm_seqshard_workspace_bytes": (_SZ, [_I] * 5),
+    "hmm_seqshard_reduce": (_I, [_P, _P, _I, _I, _I, _I, _F, _I, _I, _P, _P, _P, _SZ, _P]),
+    "hmm_seqshard_posterior": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _SZ, _P]),
+}
+
+
 def lib():
     """The loaded shared library (loaded once).  Raises if it has not been built."""
     global _lib
@@ -41,109 +108,12 @@ def lib():
             "HIP engine library %s is missing: build it with `python -m hmm_layer_amd.build` "
             "(there is no CPU fallback)" % LIB_PATH)
     L = ctypes.CDLL(LIB_PATH)
-    c_p, c_i, c_f, c_sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
-    L.hmm_strerror.restype = ctypes.c_char_p
-    L.hmm_strerror.argtypes = [c_i]
-    L.hmm_abi_version.restype = c_i
-    L.hmm_set_option.restype = c_i
-    L.hmm_set_option.argtypes = [c_i, c_i]
-    L.hmm_get_option.restype = c_i
-    L.hmm_get_option.argtypes = [c_i]
-    L.hmm_exact_count.restype = ctypes.c_longlong
-    L.hmm_exact_count.argtypes = [c_i, c_i, c_i, c_i, c_i, c_p, c_sz]
-    L.hmm_exact_detail.restype = c_i
-    L.hmm_exact_detail.argtypes = [c_i, c_i, c_i, c_i, c_p, c_sz, c_p]
-    if hasattr(L, "hmm_exact_detail_op"):           # (diagnostics added within ABI version 3: an older build lacks them)
-        L.hmm_exact_detail_op.restype = c_i
-        L.hmm_exact_detail_op.argtypes = [c_i, c_i, c_i, c_i, c_i, c_p, c_sz, c_p]
-        L.hmm_window_table.restype = c_i
-        L.hmm_window_table.argtypes = [c_i, c_i, c_i, c_i, c_i, c_p, c_sz, c_i, c_p, c_p, c_p, c_i]
-    L.hmm_max_states.restype = c_i
-    L.hmm_scan_max_states.restype = c_i
-    L.hmm_viterbi_max_states.restype = c_i
-    L.hmm_grad_max_states.restype = c_i
-    L.hmm_posterior_grad_max_states.restype = c_i
-    L.hmm_posterior_grad_workspace_bytes.restype = c_sz
-    L.hmm_posterior_grad_workspace_bytes.argtypes = [c_i] * 4
-    L.hmm_loglik_grad_serial_count.restype = ctypes.c_longlong
-    L.hmm_loglik_grad_serial_count.argtypes = [c_i, c_i, c_i, c_i, c_p, c_sz]
-    L.hmm_posterior_grad_serial_count.restype = ctypes.c_longlong
-    L.hmm_posterior_grad_serial_count.argtypes = [c_i, c_i, c_i, c_i, c_p, c_sz]
-    L.hmm_posterior_grad.restype = c_i
-    L.hmm_posterior_grad.argtypes = [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]
-    L.hmm_largeq_tile_cols.restype = c_i
-    L.hmm_largeq_tile_cols.argtypes = [c_i, c_i]
-    L.hmm_chunk_len.restype = c_i
-    L.hmm_chunk_len.argtypes = [c_i] * 4
-    L.hmm_workspace_bytes.restype = c_sz
-    L.hmm_workspace_bytes.argtypes = [c_i] * 5
-    L.hmm_forward.restype = c_i
-    L.hmm_forward.argtypes = [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_sz, c_p]
-    L.hmm_backward.restype = c_i
-    L.hmm_backward.argtypes = [c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_sz, c_p]
-    L.hmm_posterior.restype = c_i
-    L.hmm_posterior.argtypes = [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_p, c_p, c_p, c_sz, c_p]
-    L.hmm_viterbi_workspace_bytes.restype = c_sz
-    L.hmm_viterbi_workspace_bytes.argtypes = [c_i] * 4
-    L.hmm_viterbi.restype = c_i
-    L.hmm_viterbi.argtypes = [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_sz, c_p]
-    if hasattr(L, "hmm_viterbi_large"):
-        L.hmm_viterbi_large_max_states.restype = c_i
-        L.hmm_viterbi_large_workspace_bytes.restype = c_sz
-        L.hmm_viterbi_large_workspace_bytes.argtypes = [c_i] * 4
-        L.hmm_viterbi_large.restype = c_i
-        L.hmm_viterbi_large.argtypes = L.hmm_viterbi.argtypes
-    if hasattr(L, "hmm_viterbi_scan"):
-        L.hmm_viterbi_scan_max_states.restype = c_i
-        L.hmm_viterbi_scan_chunk_len.restype = c_i
-        L.hmm_viterbi_scan_chunk_len.argtypes = [c_i] * 4
-        L.hmm_viterbi_scan_pays.restype = c_i
-        L.hmm_viterbi_scan_pays.argtypes = [c_i] * 4
-        L.hmm_viterbi_scan_workspace_bytes.restype = c_sz
-        L.hmm_viterbi_scan_workspace_bytes.argtypes = [c_i] * 4
-        L.hmm_viterbi_scan.restype = c_i
-        L.hmm_viterbi_scan.argtypes = L.hmm_viterbi.argtypes
-    if hasattr(L, "hmm_loglik_grad_large"):
-        L.hmm_loglik_grad_large_max_states.restype = c_i
-        L.hmm_loglik_grad_large_workspace_bytes.restype = c_sz
-        L.hmm_loglik_grad_large_workspace_bytes.argtypes = [c_i] * 4
-        L.hmm_loglik_grad_large.restype = c_i
-        L.hmm_loglik_grad_large.argtypes = [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]
-    if hasattr(L, "hmm_posterior_grad_large"):
-        L.hmm_posterior_grad_large_max_states.restype = c_i
-        L.hmm_posterior_grad_large_workspace_bytes.restype = c_sz
-        L.hmm_posterior_grad_large_workspace_bytes.argtypes = [c_i] * 4
-        L.hmm_posterior_grad_large.restype = c_i
-        L.hmm_posterior_grad_large.argtypes = L.hmm_posterior_grad.argtypes
-    L.hmm_gene_emissions.restype = c_i
-    L.hmm_gene_emissions.argtypes = [c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_f, c_f, c_i, c_p, c_p]
-    if hasattr(L, "hmm_gene_emissions_grad"):
-        L.hmm_gene_emissions_grad_workspace_bytes.restype = c_sz
-        L.hmm_gene_emissions_grad_workspace_bytes.argtypes = [c_i] * 5
-        L.hmm_gene_emissions_grad.restype = c_i
-        L.hmm_gene_emissions_grad.argtypes = [c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_f, c_f, c_i,
-                                              c_p, c_p, c_p, c_p, c_sz, c_p]
-    L.hmm_profile_create.restype = c_p
-    L.hmm_profile_destroy.argtypes = [c_p]
-    L.hmm_posterior_profiled.restype = c_i
-    L.hmm_posterior_profiled.argtypes = L.hmm_posterior.argtypes + [c_p]
-    L.hmm_profile_read.restype = c_i
-    L.hmm_profile_read.argtypes = [c_p, c_p, c_p]
-    L.hmm_loglik_partials.restype = c_i
-    L.hmm_loglik_partials.argtypes = [c_p, c_p, c_i, c_i, c_p, c_p]
-    L.hmm_loglik_allreduce.restype = c_i
-    L.hmm_loglik_allreduce.argtypes = [c_p, c_p, c_i, c_p]
-    L.hmm_seqshard_workspace_bytes.restype = c_sz
-    L.hmm_seqshard_workspace_bytes.argtypes = [c_i] * 5
-    L.hmm_seqshard_reduce.restype = c_i
-    L.hmm_seqshard_reduce.argtypes = [c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_p, c_p, c_p, c_sz, c_p]
-    L.hmm_seqshard_posterior.restype = c_i
-    L.hmm_seqshard_posterior.argtypes = [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_p, c_p, c_i, c_i, c_i,
-                                         c_p, c_p, c_p, c_p, c_sz, c_p]
-    L.hmm_loglik_grad_workspace_bytes.restype = c_sz
-    L.hmm_loglik_grad_workspace_bytes.argtypes = [c_i] * 4
-    L.hmm_loglik_grad.restype = c_i
-    L.hmm_loglik_grad.argtypes = [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]
+    for name, (restype, argtypes) in _SIGNATURES.items():
+        if not hasattr(L, name):
+            raise EngineError("the engine library %s does not export %s: rebuild it with "
+                              "`python -m hmm_layer_amd.build`" % (LIB_PATH, name))
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -182,15 +152,29 @@ def _shapes(A, E, pi=None):
     return A, pi, (k, b, L, q)
 
 
-def _workspace(op, dims, device, need=None):
-    if need is None:
-        need = lib().hmm_workspace_bytes(op, *dims)
-    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
+def _workspace(device, need, tag=None, floor=1 << 20):
+    """The cached workspace of (device, current stream[, tag]), grown to at least `need` bytes.  The recursions'
+    workspace has no tag; calls that must not overwrite its routing records (exact_count and its kin read
+    them) keep theirs under a tag of their own."""
+    key = (device.index, torch.cuda.current_stream(device).cuda_stream) + ((tag,) if tag else ())
     ws = _workspaces.get(key)
     if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=device)
+        ws = torch.empty(max(need, floor), dtype=torch.uint8, device=device)
         _workspaces[key] = ws
     return ws
+
+
+@contextlib.contextmanager
+def _last_workspace(device):
+    """For the readers of the last call's records: on `device` (default: the current one), the recursions'
+    workspace of the current stream, with the stream synchronised."""
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    with torch.cuda.device(device):
+        ws = _workspaces.get((device.index, torch.cuda.current_stream(device).cuda_stream))
+        if ws is None:
+            raise EngineError("no call has run on this device / stream yet")
+        torch.cuda.current_stream(device).synchronize()
+        yield ws
 
 
 def release_workspaces():
@@ -239,13 +223,7 @@ class option:
 def exact_count(op, dims, device=None):
     """How many of the k*b sequences of the LAST q <= 16 call of kind `op` with shape `dims` on this
     device and stream were served by the serial exact-clamp kernels (synchronises)."""
-    device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
-    with torch.cuda.device(device):
-        key = (device.index, torch.cuda.current_stream(device).cuda_stream)
-        ws = _workspaces.get(key)
-        if ws is None:
-            raise EngineError("no call has run on this device / stream yet")
-        torch.cuda.current_stream(device).synchronize()
+    with _last_workspace(device) as ws:
         n = lib().hmm_exact_count(int(op), *dims, ws.data_ptr(), ws.numel())
     if n < 0:
         _check(int(n))
@@ -257,13 +235,7 @@ def exact_detail(dims, device=None, op=OP_POSTERIOR):
     dict(routed=sequences that left the scan, window_sequences=..., windows=..., whole=sequences redone whole,
     window_chunks=chunks the windows walked).  Synchronises.  op: OP_LOGLIK / OP_FORWARD (forward() without / with
     log alpha) or OP_BACKWARD for the last call of those entry points instead."""
-    device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
-    with torch.cuda.device(device):
-        key = (device.index, torch.cuda.current_stream(device).cuda_stream)
-        ws = _workspaces.get(key)
-        if ws is None:
-            raise EngineError("no call has run on this device / stream yet")
-        torch.cuda.current_stream(device).synchronize()
+    with _last_workspace(device) as ws:
         d = (ctypes.c_longlong * 5)()
         _check(lib().hmm_exact_detail_op(int(op), *[int(x) for x in dims], ws.data_ptr(), ws.numel(), d))
     return dict(routed=int(d[0]), window_sequences=int(d[1]), windows=int(d[2]), whole=int(d[3]), window_chunks=int(d[4]))
@@ -275,13 +247,7 @@ def window_table(dims, seq, op=OP_POSTERIOR, device=None):
     (OP_FORWARD / OP_BACKWARD), psi=numpy array of the per-chunk certificate sums; chunks the reduce marked for having
     gone through the denormal range read 1.0).  Synchronises."""
     import numpy as np
-    device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
-    with torch.cuda.device(device):
-        key = (device.index, torch.cuda.current_stream(device).cuda_stream)
-        ws = _workspaces.get(key)
-        if ws is None:
-            raise EngineError("no call has run on this device / stream yet")
-        torch.cuda.current_stream(device).synchronize()
+    with _last_workspace(device) as ws:
         k, b, L, q = (int(x) for x in dims)
         C = (L + chunk_len(k, b, L, q) - 1) // chunk_len(k, b, L, q)
         tab = (ctypes.c_int * 34)()
@@ -303,13 +269,7 @@ def loglik_grad_serial_count(dims, device=None):
 def posterior_grad_serial_count(dims, device=None, _fn="hmm_posterior_grad_serial_count"):
     """How many of the k*b sequences of the LAST posterior_grad call with shape `dims` on this device and
     stream were served by the whole-sequence sweeps rather than per chunk (synchronises)."""
-    device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
-    with torch.cuda.device(device):
-        key = (device.index, torch.cuda.current_stream(device).cuda_stream)
-        ws = _workspaces.get(key)
-        if ws is None:
-            raise EngineError("no call has run on this device / stream yet")
-        torch.cuda.current_stream(device).synchronize()
+    with _last_workspace(device) as ws:
         n = getattr(lib(), _fn)(*[int(d) for d in dims], ws.data_ptr(), ws.numel())
     if n < 0:
         _check(int(n))
@@ -321,7 +281,7 @@ def forward(A, pi, E, want_log_alpha=True, eps=EPS):
     A, pi, E = _dev(A, "A"), _dev(pi, "pi"), _dev(E, "E")
     A, pi, dims = _shapes(A, E, pi)
     with torch.cuda.device(E.device):
-        ws = _workspace(OP_FORWARD if want_log_alpha else OP_LOGLIK, dims, E.device)
+        ws = _workspace(E.device, lib().hmm_workspace_bytes(OP_FORWARD if want_log_alpha else OP_LOGLIK, *dims))
         la = torch.empty_like(E) if want_log_alpha else None
         ll = torch.empty(dims[:2], dtype=torch.float64, device=E.device)
         _check(lib().hmm_forward(A.data_ptr(), pi.data_ptr(), E.data_ptr(), *dims, eps,
@@ -335,7 +295,7 @@ def backward(A, E, eps=EPS):
     A, E = _dev(A, "A"), _dev(E, "E")
     A, _, dims = _shapes(A, E)
     with torch.cuda.device(E.device):
-        ws = _workspace(OP_BACKWARD, dims, E.device)
+        ws = _workspace(E.device, lib().hmm_workspace_bytes(OP_BACKWARD, *dims))
         lb = torch.empty_like(E)
         _check(lib().hmm_backward(A.data_ptr(), E.data_ptr(), *dims, eps, lb.data_ptr(),
                                   ws.data_ptr(), ws.numel(), _stream(E.device)))
@@ -375,7 +335,7 @@ def posterior(A, pi, E, mode=POST_PROB, eps=EPS, out=None, profile=None):
     A, pi, E = _dev(A, "A"), _dev(pi, "pi"), _dev(E, "E")
     A, pi, dims = _shapes(A, E, pi)
     with torch.cuda.device(E.device):
-        ws = _workspace(OP_POSTERIOR, dims, E.device)
+        ws = _workspace(E.device, lib().hmm_workspace_bytes(OP_POSTERIOR, *dims))
         if out is None:
             out = torch.empty_like(E)
         elif (out.shape != E.shape or out.dtype != torch.float32 or not out.is_contiguous()
@@ -391,9 +351,8 @@ def posterior(A, pi, E, mode=POST_PROB, eps=EPS, out=None, profile=None):
     return out, ll
 
 
-def gene_emissions(x, B, state_row, codon, state_codon, free_value=1.0 / 4096.0, add=0.0, n_mass=1):
-    """Fused GenePredHMMEmitter.forward for one model: x (b,L,s+5) -> E (b,L,q) fp32.
-    B (rows,s) fp32, state_row (q) int32, codon (2,nc,64) fp32, state_codon (q) int32."""
+def _emitter_args(x, B, state_row, codon, state_codon):
+    """Validation shared by gene_emissions and gene_emissions_grad -> (the five tensors, (b, L, s, rows, q, nc))."""
     x, B, codon = _dev(x, "x"), _dev(B, "B"), _dev(codon, "codon")
     state_row = _dev(state_row, "state_row", torch.int32)
     state_codon = _dev(state_codon, "state_codon", torch.int32)
@@ -404,6 +363,13 @@ def gene_emissions(x, B, state_row, codon, state_codon, free_value=1.0 / 4096.0,
     rows, q, nc = B.shape[0], state_row.numel(), codon.shape[1]
     if B.shape[1] != s or tuple(codon.shape) != (2, nc, 64) or state_codon.numel() != q:
         raise ValueError("inconsistent emitter tables")
+    return x, B, state_row, codon, state_codon, (b, L, s, rows, q, nc)
+
+
+def gene_emissions(x, B, state_row, codon, state_codon, free_value=1.0 / 4096.0, add=0.0, n_mass=1):
+    """Fused GenePredHMMEmitter.forward for one model: x (b,L,s+5) -> E (b,L,q) fp32.
+    B (rows,s) fp32, state_row (q) int32, codon (2,nc,64) fp32, state_codon (q) int32."""
+    x, B, state_row, codon, state_codon, (b, L, s, rows, q, nc) = _emitter_args(x, B, state_row, codon, state_codon)
     with torch.cuda.device(x.device):
         E = torch.empty((b, L, q), dtype=torch.float32, device=x.device)
         _check(lib().hmm_gene_emissions(x.data_ptr(), b, L, s, B.data_ptr(), rows, state_row.data_ptr(),
@@ -420,29 +386,15 @@ def gene_emissions_grad(x, B, state_row, codon, state_codon, dE, free_value=1.0 
     (one (rows,s) partial per workgroup, at most 1024 of them) comes from the engine's cache under a key of its
     own per device and stream, so it never overwrites the routing records that exact_count() and its kin read
     from the recursions' workspace."""
-    x, B, codon, dE = _dev(x, "x"), _dev(B, "B"), _dev(codon, "codon"), _dev(dE, "dE")
-    state_row = _dev(state_row, "state_row", torch.int32)
-    state_codon = _dev(state_codon, "state_codon", torch.int32)
-    if not hasattr(lib(), "hmm_gene_emissions_grad"):
-        raise EngineError("the engine library predates hmm_gene_emissions_grad: rebuild it")
-    if x.dim() != 3:
-        raise ValueError("x must have shape (b, L, s+5), got %s" % (tuple(x.shape),))
-    b, L, w = x.shape
-    s = w - 5
-    rows, q, nc = B.shape[0], state_row.numel(), codon.shape[1]
-    if B.shape[1] != s or tuple(codon.shape) != (2, nc, 64) or state_codon.numel() != q:
-        raise ValueError("inconsistent emitter tables")
+    x, B, state_row, codon, state_codon, (b, L, s, rows, q, nc) = _emitter_args(x, B, state_row, codon, state_codon)
+    dE = _dev(dE, "dE")
     if tuple(dE.shape) != (b, L, q):
         raise ValueError("dE must have shape %s, got %s" % ((b, L, q), tuple(dE.shape)))
     if not (want_dx or want_dB):
         return None, None
     with torch.cuda.device(x.device):
-        need = lib().hmm_gene_emissions_grad_workspace_bytes(b, L, s, rows, q)
-        key = (x.device.index, torch.cuda.current_stream(x.device).cuda_stream, "emitter_grad")
-        ws = _workspaces.get(key)
-        if ws is None or ws.numel() < need:
-            ws = torch.empty(need, dtype=torch.uint8, device=x.device)      # at most 1024 x rows x s floats
-            _workspaces[key] = ws
+        # at most 1024 x rows x s floats: no floor
+        ws = _workspace(x.device, lib().hmm_gene_emissions_grad_workspace_bytes(b, L, s, rows, q), "emitter_grad", floor=0)
         dx = torch.empty_like(x) if want_dx else None
         dB = torch.empty_like(B) if want_dB else None
         _check(lib().hmm_gene_emissions_grad(x.data_ptr(), b, L, s, B.data_ptr(), rows, state_row.data_ptr(),
@@ -453,6 +405,29 @@ def gene_emissions_grad(x, B, state_row, codon, state_codon, dE, free_value=1.0 
     return dx, dB
 
 
+def _viterbi(name, logA, logpi, logE):
+    """The body of viterbi / viterbi_scan / viterbi_large: hmm_<name> with the workspace cached under `name`."""
+    logA, logpi, logE = _dev(logA, "logA"), _dev(logpi, "logpi"), _dev(logE, "logE")
+    logA, logpi, dims = _shapes(logA, logE, logpi)
+    k, b, L, q = dims
+    if name == "viterbi":
+        if q > lib().hmm_viterbi_max_states():
+            name = "viterbi_large"
+        elif q > lib().hmm_scan_max_states() and lib().hmm_viterbi_scan_pays(*dims):
+            name = "viterbi_scan"
+    limit = getattr(lib(), "hmm_%s_max_states" % name)()
+    if q > limit:
+        raise ValueError("%s covers q <= %d states, got %d" % (name, limit, q))
+    with torch.cuda.device(logE.device):
+        ws = _workspace(logE.device, getattr(lib(), "hmm_%s_workspace_bytes" % name)(*dims), name)
+        path = torch.empty((k, b, L), dtype=torch.int32, device=logE.device)
+        score = torch.empty((k, b), dtype=torch.float64, device=logE.device)
+        _check(getattr(lib(), "hmm_" + name)(logA.data_ptr(), logpi.data_ptr(), logE.data_ptr(), *dims,
+                                             path.data_ptr(), score.data_ptr(), ws.data_ptr(), ws.numel(),
+                                             _stream(logE.device)))
+    return path, score
+
+
 def viterbi(logA, logpi, logE):
     """Most probable state paths.  logA (k,q,q), logpi (k,q), logE (k,b,L,q) fp32 log-probabilities
     (-inf allowed: anything below -1024 counts as -1024).  -> (path (k,b,L) int32, score (k,b) fp64).
@@ -460,77 +435,20 @@ def viterbi(logA, logpi, logE):
     (oracle/viterbi.py); ties take the lowest state index.  q <= 64 runs hmm_viterbi — or, for 17..64 states
     and the few long sequences where hmm_viterbi_scan_pays says so, viterbi_scan: bit-identical results, only
     faster —, larger models viterbi_large (hmm_viterbi_large)."""
-    logA, logpi, logE = _dev(logA, "logA"), _dev(logpi, "logpi"), _dev(logE, "logE")
-    logA, logpi, dims = _shapes(logA, logE, logpi)
-    k, b, L, q = dims
-    if q > lib().hmm_viterbi_max_states():
-        return viterbi_large(logA, logpi, logE)
-    if q > lib().hmm_scan_max_states() and hasattr(lib(), "hmm_viterbi_scan") and lib().hmm_viterbi_scan_pays(*dims):
-        return viterbi_scan(logA, logpi, logE)
-    with torch.cuda.device(logE.device):
-        need = lib().hmm_viterbi_workspace_bytes(*dims)
-        key = (logE.device.index, torch.cuda.current_stream(logE.device).cuda_stream, "viterbi")
-        ws = _workspaces.get(key)
-        if ws is None or ws.numel() < need:
-            ws = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=logE.device)
-            _workspaces[key] = ws
-        path = torch.empty((k, b, L), dtype=torch.int32, device=logE.device)
-        score = torch.empty((k, b), dtype=torch.float64, device=logE.device)
-        _check(lib().hmm_viterbi(logA.data_ptr(), logpi.data_ptr(), logE.data_ptr(), *dims,
-                                 path.data_ptr(), score.data_ptr(), ws.data_ptr(), ws.numel(),
-                                 _stream(logE.device)))
-    return path, score
+    return _viterbi("viterbi", logA, logpi, logE)
 
 
 def viterbi_scan(logA, logpi, logE):
     """viterbi() through hmm_viterbi_scan, the time-parallel chunk scan for 1 <= q <= 64 (same arguments, results
     and semantics): what few, long sequences of the 17..64-state models want.  OPT_CHUNK forces the chunk length,
     OPT_SCAN2 = 0 the single-level chunk scans, OPT_FORCE_DENSE = 1 the all-candidates reduce."""
-    logA, logpi, logE = _dev(logA, "logA"), _dev(logpi, "logpi"), _dev(logE, "logE")
-    logA, logpi, dims = _shapes(logA, logE, logpi)
-    k, b, L, q = dims
-    if not hasattr(lib(), "hmm_viterbi_scan"):
-        raise EngineError("the engine library predates hmm_viterbi_scan: rebuild it")
-    if q > lib().hmm_viterbi_scan_max_states():
-        raise ValueError("viterbi_scan covers q <= %d states, got %d" % (lib().hmm_viterbi_scan_max_states(), q))
-    with torch.cuda.device(logE.device):
-        need = lib().hmm_viterbi_scan_workspace_bytes(*dims)
-        key = (logE.device.index, torch.cuda.current_stream(logE.device).cuda_stream, "viterbi_scan")
-        ws = _workspaces.get(key)
-        if ws is None or ws.numel() < need:
-            ws = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=logE.device)
-            _workspaces[key] = ws
-        path = torch.empty((k, b, L), dtype=torch.int32, device=logE.device)
-        score = torch.empty((k, b), dtype=torch.float64, device=logE.device)
-        _check(lib().hmm_viterbi_scan(logA.data_ptr(), logpi.data_ptr(), logE.data_ptr(), *dims,
-                                      path.data_ptr(), score.data_ptr(), ws.data_ptr(), ws.numel(),
-                                      _stream(logE.device)))
-    return path, score
+    return _viterbi("viterbi_scan", logA, logpi, logE)
 
 
 def viterbi_large(logA, logpi, logE):
     """viterbi() through hmm_viterbi_large, for any 1 <= q <= 4096 (same arguments, results and semantics;
     the walk / tile evaluation is chosen by q or by OPT_VLARGE)."""
-    logA, logpi, logE = _dev(logA, "logA"), _dev(logpi, "logpi"), _dev(logE, "logE")
-    logA, logpi, dims = _shapes(logA, logE, logpi)
-    k, b, L, q = dims
-    if not hasattr(lib(), "hmm_viterbi_large"):
-        raise EngineError("the engine library predates hmm_viterbi_large: rebuild it")
-    if q > lib().hmm_viterbi_large_max_states():
-        raise ValueError("viterbi_large covers q <= %d states, got %d" % (lib().hmm_viterbi_large_max_states(), q))
-    with torch.cuda.device(logE.device):
-        need = lib().hmm_viterbi_large_workspace_bytes(*dims)
-        key = (logE.device.index, torch.cuda.current_stream(logE.device).cuda_stream, "viterbi_large")
-        ws = _workspaces.get(key)
-        if ws is None or ws.numel() < need:
-            ws = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=logE.device)
-            _workspaces[key] = ws
-        path = torch.empty((k, b, L), dtype=torch.int32, device=logE.device)
-        score = torch.empty((k, b), dtype=torch.float64, device=logE.device)
-        _check(lib().hmm_viterbi_large(logA.data_ptr(), logpi.data_ptr(), logE.data_ptr(), *dims,
-                                       path.data_ptr(), score.data_ptr(), ws.data_ptr(), ws.numel(),
-                                       _stream(logE.device)))
-    return path, score
+    return _viterbi("viterbi_large", logA, logpi, logE)
 
 
 def loglik_partials(loglik, weights=None):
@@ -553,12 +471,7 @@ def _seqshard_ws(dims, R, device):
     need = lib().hmm_seqshard_workspace_bytes(*dims, int(R))
     if need == 0:
         raise ValueError("sequence-sharded calls cover q <= %d states" % lib().hmm_scan_max_states())
-    key = (device.index, torch.cuda.current_stream(device).cuda_stream, "seqshard")
-    ws = _workspaces.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=device)
-        _workspaces[key] = ws
-    return ws
+    return _workspace(device, need, "seqshard")
 
 
 def seqshard_reduce(A, E_slab, seq_start, R, eps=EPS):
@@ -613,59 +526,66 @@ def loglik_allreduce(comm, partial):
     return partial
 
 
+def _loglik_grad(name, limit, A, pi, E, grad_loglik, eps):
+    """The body of loglik_grad / loglik_grad_large: hmm_<name>, covering q <= hmm_<limit>()."""
+    A, pi, E = _dev(A, "A"), _dev(pi, "pi"), _dev(E, "E")
+    A, pi, dims = _shapes(A, E, pi)
+    k, b, L, q = dims
+    limit = getattr(lib(), limit)()
+    if q > limit:
+        raise ValueError("%s covers q <= %d states, got %d" % (name, limit, q))
+    if grad_loglik is not None:
+        grad_loglik = _dev(grad_loglik, "grad_loglik")
+        if tuple(grad_loglik.shape) != (k, b):
+            raise ValueError("grad_loglik must have shape %s" % ((k, b),))
+    with torch.cuda.device(E.device):
+        ws = _workspace(E.device, getattr(lib(), "hmm_%s_workspace_bytes" % name)(*dims))
+        dA = torch.empty((k, q, q), dtype=torch.float32, device=E.device)
+        dpi = torch.empty((k, q), dtype=torch.float32, device=E.device)
+        dE = torch.empty_like(E)
+        ll = torch.empty((k, b), dtype=torch.float64, device=E.device)
+        _check(getattr(lib(), "hmm_" + name)(A.data_ptr(), pi.data_ptr(), E.data_ptr(), *dims, eps,
+                                             grad_loglik.data_ptr() if grad_loglik is not None else None,
+                                             dA.data_ptr(), dpi.data_ptr(), dE.data_ptr(), ll.data_ptr(),
+                                             ws.data_ptr(), ws.numel(), _stream(E.device)))
+    return dA, dpi, dE, ll
+
+
 def loglik_grad(A, pi, E, grad_loglik=None, eps=EPS):
     """Gradients of sum_{m,s} grad_loglik[m,s] * loglik[m,s] -> (dA (k,q,q), dpi (k,q), dE (k,b,L,q), loglik (k,b) fp64).
 
     What autograd through the reference's time loop (hmm_layer/BaseRNN.py:217-227) computes, from
     one forward-backward pass."""
-    A, pi, E = _dev(A, "A"), _dev(pi, "pi"), _dev(E, "E")
-    A, pi, dims = _shapes(A, E, pi)
-    k, b, L, q = dims
-    if q > lib().hmm_grad_max_states():
-        raise ValueError("loglik_grad covers q <= %d states" % lib().hmm_grad_max_states())
-    if grad_loglik is not None:
-        grad_loglik = _dev(grad_loglik, "grad_loglik")
-        if tuple(grad_loglik.shape) != (k, b):
-            raise ValueError("grad_loglik must have shape %s" % ((k, b),))
-    with torch.cuda.device(E.device):
-        ws = _workspace(None, dims, E.device, need=lib().hmm_loglik_grad_workspace_bytes(*dims))
-        dA = torch.empty((k, q, q), dtype=torch.float32, device=E.device)
-        dpi = torch.empty((k, q), dtype=torch.float32, device=E.device)
-        dE = torch.empty_like(E)
-        ll = torch.empty((k, b), dtype=torch.float64, device=E.device)
-        _check(lib().hmm_loglik_grad(A.data_ptr(), pi.data_ptr(), E.data_ptr(), *dims, eps,
-                                     grad_loglik.data_ptr() if grad_loglik is not None else None,
-                                     dA.data_ptr(), dpi.data_ptr(), dE.data_ptr(), ll.data_ptr(),
-                                     ws.data_ptr(), ws.numel(), _stream(E.device)))
-    return dA, dpi, dE, ll
+    return _loglik_grad("loglik_grad", "hmm_grad_max_states", A, pi, E, grad_loglik, eps)
 
 
 def loglik_grad_large(A, pi, E, grad_loglik=None, eps=EPS):
     """loglik_grad() through hmm_loglik_grad_large, for any 1 <= q <= 4096 (same arguments, results and
     semantics; the walk / GEMM evaluation is chosen by q or by OPT_GLARGE)."""
-    A, pi, E = _dev(A, "A"), _dev(pi, "pi"), _dev(E, "E")
+    return _loglik_grad("loglik_grad_large", "hmm_loglik_grad_large_max_states", A, pi, E, grad_loglik, eps)
+
+
+def _posterior_grad(name, A, pi, E, grad_out, mode, eps):
+    """The body of posterior_grad / posterior_grad_large: hmm_<name>, covering q <= hmm_<name>_max_states()."""
+    if int(mode) not in (POST_PROB, POST_LOG):
+        raise ValueError("%s supports mode POST_PROB or POST_LOG" % name)
+    A, pi, E, grad_out = _dev(A, "A"), _dev(pi, "pi"), _dev(E, "E"), _dev(grad_out, "grad_out")
     A, pi, dims = _shapes(A, E, pi)
     k, b, L, q = dims
-    if not hasattr(lib(), "hmm_loglik_grad_large"):
-        raise EngineError("the engine library predates hmm_loglik_grad_large: rebuild it")
-    if q > lib().hmm_loglik_grad_large_max_states():
-        raise ValueError("loglik_grad_large covers q <= %d states, got %d"
-                         % (lib().hmm_loglik_grad_large_max_states(), q))
-    if grad_loglik is not None:
-        grad_loglik = _dev(grad_loglik, "grad_loglik")
-        if tuple(grad_loglik.shape) != (k, b):
-            raise ValueError("grad_loglik must have shape %s" % ((k, b),))
+    limit = getattr(lib(), "hmm_%s_max_states" % name)()
+    if q > limit:
+        raise ValueError("%s covers q <= %d states, got %d" % (name, limit, q))
+    if grad_out.shape != E.shape:
+        raise ValueError("grad_out must be shaped like E")
     with torch.cuda.device(E.device):
-        ws = _workspace(None, dims, E.device, need=lib().hmm_loglik_grad_large_workspace_bytes(*dims))
+        ws = _workspace(E.device, getattr(lib(), "hmm_%s_workspace_bytes" % name)(*dims))
         dA = torch.empty((k, q, q), dtype=torch.float32, device=E.device)
         dpi = torch.empty((k, q), dtype=torch.float32, device=E.device)
         dE = torch.empty_like(E)
-        ll = torch.empty((k, b), dtype=torch.float64, device=E.device)
-        _check(lib().hmm_loglik_grad_large(A.data_ptr(), pi.data_ptr(), E.data_ptr(), *dims, eps,
-                                           grad_loglik.data_ptr() if grad_loglik is not None else None,
-                                           dA.data_ptr(), dpi.data_ptr(), dE.data_ptr(), ll.data_ptr(),
-                                           ws.data_ptr(), ws.numel(), _stream(E.device)))
-    return dA, dpi, dE, ll
+        _check(getattr(lib(), "hmm_" + name)(A.data_ptr(), pi.data_ptr(), E.data_ptr(), *dims, eps, int(mode),
+                                             grad_out.data_ptr(), dA.data_ptr(), dpi.data_ptr(), dE.data_ptr(),
+                                             ws.data_ptr(), ws.numel(), _stream(E.device)))
+    return dA, dpi, dE
 
 
 def posterior_grad(A, pi, E, grad_out, mode=POST_LOG, eps=EPS):
@@ -673,48 +593,11 @@ def posterior_grad(A, pi, E, grad_out, mode=POST_LOG, eps=EPS):
 
     What autograd through the reference's _state_posterior_log_probs_impl loops computes
     (hmm_layer/MsaHMMLayer.py:422-521); mode POST_PROB or POST_LOG."""
-    A, pi, E, grad_out = _dev(A, "A"), _dev(pi, "pi"), _dev(E, "E"), _dev(grad_out, "grad_out")
-    A, pi, dims = _shapes(A, E, pi)
-    k, b, L, q = dims
-    if q > lib().hmm_posterior_grad_max_states():
-        raise ValueError("posterior_grad covers q <= %d states" % lib().hmm_posterior_grad_max_states())
-    if grad_out.shape != E.shape:
-        raise ValueError("grad_out must be shaped like E")
-    if int(mode) not in (POST_PROB, POST_LOG):
-        raise ValueError("posterior_grad supports mode POST_PROB or POST_LOG")
-    with torch.cuda.device(E.device):
-        ws = _workspace(None, dims, E.device, need=lib().hmm_posterior_grad_workspace_bytes(*dims))
-        dA = torch.empty((k, q, q), dtype=torch.float32, device=E.device)
-        dpi = torch.empty((k, q), dtype=torch.float32, device=E.device)
-        dE = torch.empty_like(E)
-        _check(lib().hmm_posterior_grad(A.data_ptr(), pi.data_ptr(), E.data_ptr(), *dims, eps, int(mode),
-                                        grad_out.data_ptr(), dA.data_ptr(), dpi.data_ptr(), dE.data_ptr(),
-                                        ws.data_ptr(), ws.numel(), _stream(E.device)))
-    return dA, dpi, dE
+    return _posterior_grad("posterior_grad", A, pi, E, grad_out, mode, eps)
 
 
 def posterior_grad_large(A, pi, E, grad_out, mode=POST_LOG, eps=EPS):
     """posterior_grad() through hmm_posterior_grad_large, for any 1 <= q <= 4096 (same arguments, results and
     semantics; the walk / GEMM evaluation is chosen by q or by OPT_GLARGE).  POST_LOG_NO_LL is not a mode of
     this call: the autograd node composes it with loglik_grad_large."""
-    if int(mode) not in (POST_PROB, POST_LOG):
-        raise ValueError("posterior_grad_large supports mode POST_PROB or POST_LOG")
-    A, pi, E, grad_out = _dev(A, "A"), _dev(pi, "pi"), _dev(E, "E"), _dev(grad_out, "grad_out")
-    A, pi, dims = _shapes(A, E, pi)
-    k, b, L, q = dims
-    if not hasattr(lib(), "hmm_posterior_grad_large"):
-        raise EngineError("the engine library predates hmm_posterior_grad_large: rebuild it")
-    if q > lib().hmm_posterior_grad_large_max_states():
-        raise ValueError("posterior_grad_large covers q <= %d states, got %d"
-                         % (lib().hmm_posterior_grad_large_max_states(), q))
-    if grad_out.shape != E.shape:
-        raise ValueError("grad_out must be shaped like E")
-    with torch.cuda.device(E.device):
-        ws = _workspace(None, dims, E.device, need=lib().hmm_posterior_grad_large_workspace_bytes(*dims))
-        dA = torch.empty((k, q, q), dtype=torch.float32, device=E.device)
-        dpi = torch.empty((k, q), dtype=torch.float32, device=E.device)
-        dE = torch.empty_like(E)
-        _check(lib().hmm_posterior_grad_large(A.data_ptr(), pi.data_ptr(), E.data_ptr(), *dims, eps, int(mode),
-                                              grad_out.data_ptr(), dA.data_ptr(), dpi.data_ptr(), dE.data_ptr(),
-                                              ws.data_ptr(), ws.numel(), _stream(E.device)))
-    return dA, dpi, dE
+    return _posterior_grad("posterior_grad_large", A, pi, E, grad_out, mode, eps)

@@ -80,3 +80,36 @@ def test_missing_library_fails_loudly(monkeypatch):
     monkeypatch.setattr(engine, "LIB_PATH", "/nonexistent/libhmm_engine.so")
     with pytest.raises(engine.EngineError, match="no CPU fallback"):
         engine.lib()
+
+
+def test_midq_validation_order_without_device(lib):
+    # 17..64 states: shape / q range, then null pointers, then the mode, then the workspace (null, size, alignment:
+    # first against the serial plan, then with the chunked scan's region); nothing here reaches a HIP call
+    p = 0x10000                                                                 # never dereferenced
+    assert lib.hmm_forward(None, None, None, 1, 1, 300, 20, 1e-16, None, None, None, 0, None) == -3
+    assert lib.hmm_forward(None, None, None, 1, 1, 0, 20, 1e-16, None, None, None, 0, None) == -1
+    assert lib.hmm_backward(None, None, 1, 1, 300, 48, 1e-16, None, None, 0, None) == -3
+    assert lib.hmm_posterior(None, None, None, 1, 1, 300, 48, 1e-16, 7, None, None, None, 0, None) == -3
+    assert lib.hmm_posterior(p, p, p, 1, 1, 300, 48, 1e-16, 7, p, None, None, 0, None) == -6
+    assert lib.hmm_posterior(p, p, p, 1, 1, 300, 48, 1e-16, 0, p, None, None, 0, None) == -3
+    assert lib.hmm_posterior(p, p, p, 1, 1, 300, 48, 1e-16, 0, p, None, 0x10000, 256, None) == -4
+    assert lib.hmm_posterior(p, p, p, 1, 1, 300, 20, 1e-16, 0, p, None, 0x10001, 1 << 30, None) == -4
+    for q in (20, 48):
+        assert lib.hmm_exact_count(engine.OP_POSTERIOR, 1, 1, 300, q, None, 0) == -3
+    assert lib.hmm_exact_count(engine.OP_POSTERIOR, 1, 1, 100, 48, None, 0) == 0   # below the chunked path's minimum
+
+
+def test_midq_workspace_follows_the_chunked_path(lib):
+    # 48 states, L = 300: up to 96 sequences take the chunked scan (the posterior adds its checkpoints), 97 do not
+    w = {(op, b): lib.hmm_workspace_bytes(op, 1, b, 300, 48)
+         for op in (engine.OP_LOGLIK, engine.OP_POSTERIOR) for b in (96, 97)}
+    assert w[engine.OP_POSTERIOR, 96] > w[engine.OP_LOGLIK, 96]
+    assert w[engine.OP_POSTERIOR, 97] == w[engine.OP_LOGLIK, 97]
+    assert w[engine.OP_LOGLIK, 97] < w[engine.OP_LOGLIK, 96]
+
+
+def test_missing_symbol_names_it(lib, monkeypatch):
+    monkeypatch.setattr(engine, "_lib", None)
+    monkeypatch.setitem(engine._SIGNATURES, "hmm_no_such_function", (ctypes.c_int, []))
+    with pytest.raises(engine.EngineError, match="hmm_no_such_function"):
+        engine.lib()
