@@ -47,9 +47,9 @@
 //     exceeds PC_LOG_EXPOSED of sum w.
 
 struct PcPlan {
-    int W;                                   // states per row: 16 (main pipeline's scan plan) or 32 (hmm_scan_mid.inc's)
+    int W;                                   // states per row: 16 (main pipeline's scan plan), 32 or 64 (hmm_scan_mid.inc's)
     Plan p;                                  // shape and chunks
-    MidPlan p32;                             // W = 32: the 32-state scan plan (its p is copied into `p`)
+    MidPlan mid;                             // W = 32, 64: the scan plan of that width (its p is copied into `p`)
     PgPlan pg;                               // AH, RB, dEa, S, per-sequence partials (shared with the serial sweeps)
     size_t o_ops, o_exps, o_prefix, o_suffix, o_route;       // inside the scan plan's part of the workspace
     size_t o_pg, o_c, o_lam, o_gpart, o_side, o_need, o_sp, total;
@@ -94,8 +94,9 @@ static bool pc_wanted(int k, int b, int L, int q) {
     return (long long)k * b <= (W == QP ? 4096 : 512) && C >= 4;
 }
 
-static int make_pcplan(int k, int b, int L, int q, PcPlan *pc) {
-    const int W = pc_width(q);
+// W: the row width; 0 = pc_width's (hmm_grad_scan.inc asks for Q32 / Q64 for any model of 17..64 states)
+static int make_pcplan(int k, int b, int L, int q, PcPlan *pc, int W = 0) {
+    if (W == 0) W = pc_width(q);
     if (W == 0) return HMM_ERR_Q_UNSUPPORTED;
     pc->W = W;
     size_t off;
@@ -106,12 +107,12 @@ static int make_pcplan(int k, int b, int L, int q, PcPlan *pc) {
         pc->o_route = pc->p.o_topo;
         off = pc->p.total;
     } else {
-        int rc = make_midplan(HMM_OP_BACKWARD, k, b, L, q, Q32, &pc->p32, pc_chunk_len(k, b, L));
+        int rc = make_midplan(HMM_OP_BACKWARD, k, b, L, q, W, &pc->mid, pc_chunk_len(k, b, L));
         if (rc) return rc;
-        pc->p = pc->p32.p;
-        pc->o_ops = pc->p32.o_ops; pc->o_exps = pc->p32.o_exps; pc->o_prefix = pc->p32.o_prefix;
-        pc->o_suffix = pc->p32.o_suffix; pc->o_route = pc->p32.o_elig;
-        off = pc->p32.total;
+        pc->p = pc->mid.p;
+        pc->o_ops = pc->mid.o_ops; pc->o_exps = pc->mid.o_exps; pc->o_prefix = pc->mid.o_prefix;
+        pc->o_suffix = pc->mid.o_suffix; pc->o_route = pc->mid.o_elig;
+        off = pc->mid.total;
     }
     make_pgplan(k, b, L, q, &pc->pg);
     const Plan &p = pc->p;
@@ -164,6 +165,15 @@ template <> struct PcW<32> {
     }
     template <int K> static __device__ __forceinline__ void fmac_bc(float &acc, float v, float c) { acc = fmaf(bc<K>(v), c, acc); }
     // k32_check's verdict (elig[m] = 0: not the compiled topology, or not primitive)
+    static __device__ __forceinline__ bool model_serial(const int *route, int m) { return route[m] == 0; }
+};
+// one chunk per wave, lane = state: the row sum is the wave sum, and a state's value reaches the row as a readlane,
+// which the fma takes as its scalar operand
+template <> struct PcW<64> {
+    static __device__ __forceinline__ float sum(float v) { return mq_wave_sum(v); }
+    template <int K> static __device__ __forceinline__ float bc(float v) { return lane_bcast(v, K); }
+    template <int K> static __device__ __forceinline__ void fmac_bc(float &acc, float v, float c) { acc = fmaf(bc<K>(v), c, acc); }
+    // k64_check's verdict (elig[m] = ID_DENSE64, or 0: not primitive)
     static __device__ __forceinline__ bool model_serial(const int *route, int m) { return route[m] == 0; }
 };
 template <int W, int K> struct PcLoop {
@@ -714,7 +724,7 @@ static int pc_launch(const float *A, const float *pi, const float *E, int k, int
         if (rc) return rc;
         return pc_launch_w<QP>(A, pi, E, k, b, L, q, eps, mode, G, dA, dpi, dE, ws, pc, st);
     }
-    scan_reduce_scan<Scan32>(A, pi, E, pc.p32, eps, ws, st);
+    scan_reduce_scan<Scan32>(A, pi, E, pc.mid, eps, ws, st);
     return pc_launch_w<Q32>(A, pi, E, k, b, L, q, eps, mode, G, dA, dpi, dE, ws, pc, st);
 }
 
@@ -772,17 +782,28 @@ __global__ __launch_bounds__(64) void k_pc_llgrad(const float *__restrict__ A, c
     if (x == 0) inv_sg[r.chain] = phis;
 }
 
-// need[seq]: the whole-sequence sweeps redo it.  One wave per sequence.
+// need[seq]: the whole-sequence sweeps redo it.  One wave per sequence.  exps / risk (or null): the reduces' marks
+// as k32_select reads them — a chain whose operator went through the denormal range, or survives an observation at
+// the emission floor only, flags its sequence.
 template <int W>
 __global__ __launch_bounds__(64) void k_pc_llselect(const float *__restrict__ inv_sg, const int *__restrict__ route, Plan p,
-                                                    float eps, int exact_mode, int force, int *__restrict__ need) {
+                                                    float eps, int exact_mode, int force, int *__restrict__ need,
+                                                    const int *__restrict__ exps = nullptr,
+                                                    const int *__restrict__ risk = nullptr) {
     const int seq = blockIdx.x;
+    const int el = route[seq / p.b];
     const bool model_serial = PcW<W>::model_serial(route, seq / p.b);
     float s = 0.f;
+    bool mark = false;
     if (!model_serial)
-        for (int c = threadIdx.x; c < p.C; c += 64) s += inv_sg[(size_t)seq * p.C + c];
+        for (int c = threadIdx.x; c < p.C; c += 64) {
+            const size_t chain = (size_t)seq * p.C + c;
+            s += inv_sg[chain];
+            if (risk) mark = mark || ((el == ID_DENSE32 || el == ID_DENSE64) ? risk[chain] != 0 : exps[chain * W + W - 1] != 0);
+        }
     const float F = mq_wave_sum(s) * eps;
-    const bool flagged = !(F <= EXACT_DELTA) && !force && exact_mode == HMM_EXACT_AUTO;
+    mark = __builtin_amdgcn_ballot_w64(mark) != 0ull;
+    const bool flagged = (!(F <= EXACT_DELTA) || mark) && !force && exact_mode == HMM_EXACT_AUTO;
     if (threadIdx.x == 0) need[seq] = (model_serial || flagged) ? 1 : 0;
 }
 
@@ -803,29 +824,30 @@ static size_t pc_llgrad_workspace(int k, int b, int L, int q) {
     PcPlan pc;
     return make_pcplan(k, b, L, q, &pc) ? 0 : pc.total;
 }
-static int pc_loglik_grad(const float *A, const float *pi, const float *E, int k, int b, int L, int q, float eps,
-                          const float *gw, float *dA, float *dpi, float *dE, double *loglik, char *ws, size_t ws_bytes,
-                          hipStream_t st) {
-    PcPlan pc;
-    int rc = make_pcplan(k, b, L, q, &pc);
-    if (rc) return rc;
-    if (ws_bytes < pc.total || ((uintptr_t)ws & 255)) return HMM_ERR_WORKSPACE;
+// S: Scan32 / Scan64 (hmm_scan_mid.inc), or a type with their interface; pc: make_pcplan's for S::W.  marks: the
+// reduces' risk marks flag a sequence as well (hmm_grad_scan.inc; the 29-state path of hmm_loglik_grad runs without).
+template <class S>
+static int pc_loglik_grad_on(const float *A, const float *pi, const float *E, int k, int b, int L, int q, float eps,
+                             const float *gw, float *dA, float *dpi, float *dE, double *loglik, char *ws, const PcPlan &pc,
+                             bool marks, hipStream_t st) {
+    constexpr int W = S::W;
     const Plan &p = pc.p;
     const PgPlan &pp = pc.pg;
-    scan_reduce_scan<Scan32>(A, pi, E, pc.p32, eps, ws, st);
+    scan_reduce_scan<S>(A, pi, E, pc.mid, eps, ws, st);
     char *wp = ws + pc.o_pg;
-    float *AH = (float *)(wp + pp.o_ah), *RB = (float *)(wp + pp.o_rb), *S = (float *)(wp + pp.o_s);
+    float *AH = (float *)(wp + pp.o_ah), *RB = (float *)(wp + pp.o_rb), *S_ = (float *)(wp + pp.o_s);
     float *gseq = (float *)(wp + pp.o_gpart), *gpart = (float *)(ws + pc.o_gpart), *inv_sg = (float *)(ws + pc.o_c);
-    double *ll = (double *)(ws + pc.p32.o_loglik);
+    double *ll = (double *)(ws + pc.mid.o_loglik);
     int *need = (int *)(ws + pc.o_need);
     const int *route = (const int *)(ws + pc.o_route);
-    const unsigned nb = (unsigned)((p.nchains + 64 / Q32 - 1) / (64 / Q32));
-    hipLaunchKernelGGL(k_pc_values<Q32>, dim3(nb, 2), dim3(64), 0, st, A, E, (const float *)(ws + pc.o_prefix),
-                       (const float *)(ws + pc.o_suffix), route, p, eps, AH, S, RB);
-    hipLaunchKernelGGL(k_pc_llgrad<Q32>, dim3(nb), dim3(64), 0, st, A, E, (const float *)AH, (const float *)RB, gw, route,
+    const unsigned nb = (unsigned)((p.nchains + 64 / W - 1) / (64 / W));
+    hipLaunchKernelGGL(k_pc_values<W>, dim3(nb, 2), dim3(64), 0, st, A, E, (const float *)(ws + pc.o_prefix),
+                       (const float *)(ws + pc.o_suffix), route, p, eps, AH, S_, RB);
+    hipLaunchKernelGGL(k_pc_llgrad<W>, dim3(nb), dim3(64), 0, st, A, E, (const float *)AH, (const float *)RB, gw, route,
                        p, eps, dE, gpart, inv_sg);
-    hipLaunchKernelGGL(k_pc_llselect<Q32>, dim3(p.NB), dim3(64), 0, st, (const float *)inv_sg, route, p, eps,
-                       opt(HMM_OPT_EXACT), opt(HMM_OPT_PGCHUNK) == 2 ? 1 : 0, need);
+    hipLaunchKernelGGL(k_pc_llselect<W>, dim3(p.NB), dim3(64), 0, st, (const float *)inv_sg, route, p, eps,
+                       opt(HMM_OPT_EXACT), opt(HMM_OPT_PGCHUNK) == 2 ? 1 : 0, need,
+                       marks ? (const int *)(ws + pc.o_exps) : nullptr, marks ? (const int *)(ws + pc.mid.o_risk) : nullptr);
     if (p.NB <= PC_FOLD_WAVES_MAX_SEQS)
         hipLaunchKernelGGL(k_pc_llfold, dim3(q * q, p.NB), dim3(64), 0, st, (const float *)gpart, (const int *)need, p, gseq);
     else
@@ -834,9 +856,19 @@ static int pc_loglik_grad(const float *A, const float *pi, const float *E, int k
     // the whole-sequence sweeps for what is flagged (their waves exit at once otherwise), then the sums
     return mq_loglik_grad_run(A, pi, E, k, b, L, q, eps, gw, dA, dpi, dE, loglik, ll, gseq, st, need, (MqSp *)(ws + pc.o_sp));
 }
-static long long pc_llgrad_serial_count(int k, int b, int L, int q, const void *ws, size_t ws_bytes) {
+static int pc_loglik_grad(const float *A, const float *pi, const float *E, int k, int b, int L, int q, float eps,
+                          const float *gw, float *dA, float *dpi, float *dE, double *loglik, char *ws, size_t ws_bytes,
+                          hipStream_t st) {
     PcPlan pc;
     int rc = make_pcplan(k, b, L, q, &pc);
+    if (rc) return rc;
+    if (ws_bytes < pc.total || ((uintptr_t)ws & 255)) return HMM_ERR_WORKSPACE;
+    return pc_loglik_grad_on<Scan32>(A, pi, E, k, b, L, q, eps, gw, dA, dpi, dE, loglik, ws, pc, false, st);
+}
+// W: make_pcplan's
+static long long pc_llgrad_serial_count_w(int k, int b, int L, int q, const void *ws, size_t ws_bytes, int W) {
+    PcPlan pc;
+    int rc = make_pcplan(k, b, L, q, &pc, W);
     if (rc) return rc;
     if (!ws) return HMM_ERR_NULL_POINTER;
     if (ws_bytes < pc.total) return HMM_ERR_WORKSPACE;
@@ -846,4 +878,7 @@ static long long pc_llgrad_serial_count(int k, int b, int L, int q, const void *
     long long n = 0;
     for (int v : need) n += v != 0;
     return n;
+}
+static long long pc_llgrad_serial_count(int k, int b, int L, int q, const void *ws, size_t ws_bytes) {
+    return pc_llgrad_serial_count_w(k, b, L, q, ws, ws_bytes, 0);
 }

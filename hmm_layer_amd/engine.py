@@ -77,6 +77,12 @@ _SIGNATURES = {
     "hmm_loglik_grad_workspace_bytes": (_SZ, [_I] * 4),
     "hmm_loglik_grad": (_I, _LOGLIK_GRAD),
     "hmm_loglik_grad_serial_count": (_LL, _LAST_CALL),
+    "hmm_loglik_grad_scan_max_states": (_I, []),
+    "hmm_loglik_grad_scan_chunk_len": (_I, [_I] * 4),
+    "hmm_loglik_grad_scan_pays": (_I, [_I] * 4),
+    "hmm_loglik_grad_scan_workspace_bytes": (_SZ, [_I] * 4),
+    "hmm_loglik_grad_scan_serial_count": (_LL, _LAST_CALL),
+    "hmm_loglik_grad_scan": (_I, _LOGLIK_GRAD),
     "hmm_loglik_grad_large_max_states": (_I, []),
     "hmm_loglik_grad_large_workspace_bytes": (_SZ, [_I] * 4),
     "hmm_loglik_grad_large": (_I, _LOGLIK_GRAD),
@@ -165,12 +171,12 @@ def _workspace(device, need, tag=None, floor=1 << 20):
 
 
 @contextlib.contextmanager
-def _last_workspace(device):
+def _last_workspace(device, tag=None):
     """For the readers of the last call's records: on `device` (default: the current one), the recursions'
-    workspace of the current stream, with the stream synchronised."""
+    workspace of the current stream (or the one kept under `tag`), with the stream synchronised."""
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
     with torch.cuda.device(device):
-        ws = _workspaces.get((device.index, torch.cuda.current_stream(device).cuda_stream))
+        ws = _workspaces.get((device.index, torch.cuda.current_stream(device).cuda_stream) + ((tag,) if tag else ()))
         if ws is None:
             raise EngineError("no call has run on this device / stream yet")
         torch.cuda.current_stream(device).synchronize()
@@ -262,14 +268,19 @@ def window_table(dims, seq, op=OP_POSTERIOR, device=None):
 
 
 def loglik_grad_serial_count(dims, device=None):
-    """The same for the LAST loglik_grad call (17..64 states)."""
+    """The same for the LAST loglik_grad call (17..64 states) that hmm_loglik_grad itself served."""
     return posterior_grad_serial_count(dims, device, _fn="hmm_loglik_grad_serial_count")
 
 
-def posterior_grad_serial_count(dims, device=None, _fn="hmm_posterior_grad_serial_count"):
+def loglik_grad_scan_serial_count(dims, device=None):
+    """The same for the LAST loglik_grad_scan call (also one that loglik_grad routed there)."""
+    return posterior_grad_serial_count(dims, device, _fn="hmm_loglik_grad_scan_serial_count", _tag="loglik_grad_scan")
+
+
+def posterior_grad_serial_count(dims, device=None, _fn="hmm_posterior_grad_serial_count", _tag=None):
     """How many of the k*b sequences of the LAST posterior_grad call with shape `dims` on this device and
     stream were served by the whole-sequence sweeps rather than per chunk (synchronises)."""
-    with _last_workspace(device) as ws:
+    with _last_workspace(device, _tag) as ws:
         n = getattr(lib(), _fn)(*[int(d) for d in dims], ws.data_ptr(), ws.numel())
     if n < 0:
         _check(int(n))
@@ -527,10 +538,14 @@ def loglik_allreduce(comm, partial):
 
 
 def _loglik_grad(name, limit, A, pi, E, grad_loglik, eps):
-    """The body of loglik_grad / loglik_grad_large: hmm_<name>, covering q <= hmm_<limit>()."""
+    """The body of loglik_grad / loglik_grad_scan / loglik_grad_large: hmm_<name>, covering q <= hmm_<limit>().
+    loglik_grad_scan keeps its workspace under a tag of its own."""
     A, pi, E = _dev(A, "A"), _dev(pi, "pi"), _dev(E, "E")
     A, pi, dims = _shapes(A, E, pi)
     k, b, L, q = dims
+    if name == "loglik_grad" and lib().hmm_scan_max_states() < q <= lib().hmm_loglik_grad_scan_max_states() \
+            and lib().hmm_loglik_grad_scan_pays(*dims):
+        name, limit = "loglik_grad_scan", "hmm_loglik_grad_scan_max_states"
     limit = getattr(lib(), limit)()
     if q > limit:
         raise ValueError("%s covers q <= %d states, got %d" % (name, limit, q))
@@ -539,7 +554,10 @@ def _loglik_grad(name, limit, A, pi, E, grad_loglik, eps):
         if tuple(grad_loglik.shape) != (k, b):
             raise ValueError("grad_loglik must have shape %s" % ((k, b),))
     with torch.cuda.device(E.device):
-        ws = _workspace(E.device, getattr(lib(), "hmm_%s_workspace_bytes" % name)(*dims))
+        need = getattr(lib(), "hmm_%s_workspace_bytes" % name)(*dims)
+        if name == "loglik_grad_scan" and need == 0:
+            raise ValueError("loglik_grad_scan does not support the shape (k, b, L, q) = %s" % (dims,))
+        ws = _workspace(E.device, need, "loglik_grad_scan" if name == "loglik_grad_scan" else None)
         dA = torch.empty((k, q, q), dtype=torch.float32, device=E.device)
         dpi = torch.empty((k, q), dtype=torch.float32, device=E.device)
         dE = torch.empty_like(E)
@@ -555,8 +573,16 @@ def loglik_grad(A, pi, E, grad_loglik=None, eps=EPS):
     """Gradients of sum_{m,s} grad_loglik[m,s] * loglik[m,s] -> (dA (k,q,q), dpi (k,q), dE (k,b,L,q), loglik (k,b) fp64).
 
     What autograd through the reference's time loop (hmm_layer/BaseRNN.py:217-227) computes, from
-    one forward-backward pass."""
+    one forward-backward pass.  17..64 states: through loglik_grad_scan where hmm_loglik_grad_scan_pays says so."""
     return _loglik_grad("loglik_grad", "hmm_grad_max_states", A, pi, E, grad_loglik, eps)
+
+
+def loglik_grad_scan(A, pi, E, grad_loglik=None, eps=EPS):
+    """loglik_grad() through hmm_loglik_grad_scan, per chunk of the scan plan for 1 <= q <= 64 (same arguments,
+    results and semantics): what few, long sequences of the 17..64-state models want.  OPT_CHUNK forces the chunk
+    length, OPT_PGCHUNK = 2 serves every sequence per chunk (tests); loglik_grad_scan_serial_count() tells how many
+    sequences the whole-sequence sweeps redid."""
+    return _loglik_grad("loglik_grad_scan", "hmm_loglik_grad_scan_max_states", A, pi, E, grad_loglik, eps)
 
 
 def loglik_grad_large(A, pi, E, grad_loglik=None, eps=EPS):

@@ -408,6 +408,44 @@ int hmm_loglik_grad(const float *A, const float *pi, const float *E,
                     void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * The same gradient, per chunk of the scan plan, for 1 <= q <= hmm_loglik_grad_scan_max_states() (64): arguments,
+ * outputs, clamp semantics and NULL-ability exactly those of hmm_loglik_grad (grad_loglik and loglik may be NULL).
+ * hmm_loglik_grad itself evaluates 17..64 states per chunk only for the compiled 29-state topology; every other
+ * model of that range walks two whole-sequence sweeps, one wave per sequence.  This entry point is the explicit
+ * request to run ANY primitive model of 17..64 states per chunk: the dense reduce and chunk scan of its row width
+ * (32 lanes for 17..32 states, 64 for 33..64), the value sweeps, then every chunk sums its own share of dE, dA and
+ * the certificate.  Models whose support is not primitive, sequences over the floor-transition certificate
+ * (F = eps * sum_t 1 / Sg_t > 2e-6) and sequences a reduce marked are redone by the masked whole-sequence sweeps
+ * inside the same call, bit-identical to hmm_loglik_grad's sweeps.  q <= 16 forwards to hmm_loglik_grad (call,
+ * workspace query and serial count alike).
+ *   hmm_loglik_grad_scan_chunk_len        the chunk length the call would use (a multiple of 16, <= 512; HMM_OPT_CHUNK
+ *                                         forces it); 0 for an unsupported shape
+ *   hmm_loglik_grad_scan_pays             1 where the measured rule prefers this call to
+ *                                         hmm_loglik_grad; 0 for q <= 16, where hmm_loglik_grad already runs per
+ *                                         chunk, below 4 chunks, and for every shape the call would refuse
+ *   hmm_loglik_grad_scan_workspace_bytes  exactly what the call uses, in 64-bit sizes (the two value arrays of
+ *                                         k*b*L*q floats and more); 0 for an unsupported shape
+ *   hmm_loglik_grad_scan_serial_count     how many sequences of the LAST call with this shape the whole-sequence
+ *                                         sweeps served (synchronous copy from the workspace)
+ * Unsupported: L * q * 4 >= 2^31 - 4096 (the kernels' 32-bit row offsets) and k * b > 2^24: HMM_ERR_BAD_SHAPE.
+ * Options: HMM_OPT_CHUNK, HMM_OPT_EXACT and HMM_OPT_FORCE_DENSE act as for hmm_posterior's 17..64-state plans;
+ * HMM_OPT_PGCHUNK = 2 serves every sequence of an eligible model per chunk, without certificate and marks (tests).
+ * Runs on `stream` only, no host synchronisation, capturable into a HIP graph; fixed summation orders (fp32
+ * inside a chunk, fp64 across chunks and sequences): repeated calls are bit-identical.
+ * Argument checks, before any HIP call and in this order: bad shape -1, q > 64 -2, a NULL A / pi / E / dA / dpi /
+ * dE / workspace -3, a small or misaligned (256 bytes) workspace -4.
+ */
+int hmm_loglik_grad_scan_max_states(void);
+int hmm_loglik_grad_scan_chunk_len(int k, int b, int L, int q);
+int hmm_loglik_grad_scan_pays(int k, int b, int L, int q);
+size_t hmm_loglik_grad_scan_workspace_bytes(int k, int b, int L, int q);
+long long hmm_loglik_grad_scan_serial_count(int k, int b, int L, int q, const void *workspace, size_t workspace_bytes);
+int hmm_loglik_grad_scan(const float *A, const float *pi, const float *E,
+                         int k, int b, int L, int q, float eps, const float *grad_loglik,
+                         float *dA, float *dpi, float *dE, double *loglik,
+                         void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * The same gradient for any 1 <= q <= hmm_loglik_grad_large_max_states() (4096): arguments, outputs and
  * clamp semantics exactly those of hmm_loglik_grad (grad_loglik and loglik may be NULL).  Two evaluations,
  * picked by HMM_OPT_GLARGE (0: by q — the walk up to 128 states, the GEMMs above; 1: walk; 2: GEMMs):
