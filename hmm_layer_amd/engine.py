@@ -96,6 +96,8 @@ _SIGNATURES = {
     "hmm_gene_emissions": (_I, _EMITTER + [_P, _P]),
     "hmm_gene_emissions_grad_workspace_bytes": (_SZ, [_I] * 5),
     "hmm_gene_emissions_grad": (_I, _EMITTER + [_P, _P, _P, _P, _SZ, _P]),
+    "hmm_embedding_emissions_max_dim": (_I, []),
+    "hmm_embedding_emissions": (_I, [_P, _LL, _I, _I, _I, _P, _P, _P, _I, _P, _I, _F, _F, _I, _P, _P]),
     "hmm_loglik_partials": (_I, [_P, _P, _I, _I, _P, _P]),
     "hmm_loglik_allreduce": (_I, [_P, _P, _I, _P]),
     "hmm_seqshard_workspace_bytes": (_SZ, [_I] * 5),
@@ -414,6 +416,37 @@ def gene_emissions_grad(x, B, state_row, codon, state_codon, dE, free_value=1.0 
                                              dx.data_ptr() if want_dx else None, dB.data_ptr() if want_dB else None,
                                              ws.data_ptr(), ws.numel(), _stream(x.device)))
     return dx, dB
+
+
+def embedding_emissions(x, col0, d, mean, inv_std, log_norm, state_row, E=None, inv_temperature=1.0, add=0.0):
+    """Embedding-emission factor (hmm_embedding_emissions): x (b,L,w) fp32 holds every position's embedding in
+    columns col0 .. col0+d-1, read in place (no copy of the columns is made).  mean, inv_std (rows,d) fp32,
+    log_norm (rows) fp32, state_row (q) int32.  f = exp(inv_temperature * log N(x; mean, 1/inv_std)) + add.
+    With E (b,L,q) given, E *= f in place; otherwise a new E = f.  Returns E."""
+    x, mean, inv_std, log_norm = _dev(x, "x"), _dev(mean, "mean"), _dev(inv_std, "inv_std"), _dev(log_norm, "log_norm")
+    state_row = _dev(state_row, "state_row", torch.int32)
+    if x.dim() != 3:
+        raise ValueError("x must have shape (b, L, w), got %s" % (tuple(x.shape),))
+    b, L, w = x.shape
+    col0, d = int(col0), int(d)
+    rows, q = mean.shape[0], state_row.numel()
+    if col0 < 0 or d < 1 or col0 + d > w:
+        raise ValueError("columns %d .. %d lie outside x's %d columns" % (col0, col0 + d - 1, w))
+    if tuple(mean.shape) != (rows, d) or tuple(inv_std.shape) != (rows, d) or log_norm.numel() != rows:
+        raise ValueError("inconsistent embedding tables")
+    multiply = E is not None
+    if multiply:
+        if not (torch.is_tensor(E) and E.is_cuda and E.dtype == torch.float32 and E.is_contiguous()
+                and tuple(E.shape) == (b, L, q)):
+            raise ValueError("E must be a contiguous fp32 device tensor of shape %s" % ((b, L, q),))
+    with torch.cuda.device(x.device):
+        if not multiply:
+            E = torch.empty((b, L, q), dtype=torch.float32, device=x.device)
+        _check(lib().hmm_embedding_emissions(x.data_ptr() + 4 * col0, w, b, L, d, mean.data_ptr(), inv_std.data_ptr(),
+                                             log_norm.data_ptr(), rows, state_row.data_ptr(), q,
+                                             float(inv_temperature), float(add), int(multiply), E.data_ptr(),
+                                             _stream(x.device)))
+    return E
 
 
 def _viterbi(name, logA, logpi, logE):

@@ -9,9 +9,27 @@ Interface kept (gene_pred_hmm_emitter.py:61-128, 231-277): ``build(input_shape)`
 
 Differences, on purpose: everything is created on / follows the parameters' device; the k-mer
 helper does not mutate its input (defect D5 — ``n_mass_compat=True`` reproduces the as-shipped
-doubling of N mass in the right-pivot 3-mers); embedding emissions (``emit_embeddings``) are
-not provided (they depend on the reference's MvnMixture, upstream of the hot path).
+doubling of N mass in the right-pivot 3-mers).
+
+Embedding emissions (``emit_embeddings=True``, inputs (k, b, L, s + d [+ 5])): one model, diagonal
+covariance, one mixture component — the reference's MvnMixture(diag_only=True) with
+DefaultDiagBijector(initial_variance), written out in torch ops here (``embedding_log_pdf``) and fused
+for inference (``forward_fused``: hmm_gene_emissions, then hmm_embedding_emissions multiplying into E
+with the embedding columns read in place).  ``full_covariance=True`` raises NotImplementedError.
+Three more differences from the as-shipped reference, on purpose:
+  * MvnMixture.__init__ copies the parameter with ``torch.tensor(kernel)`` (MvnMixture.py:40), so the
+    reference never trains ``embedding_emission_kernel``; here the graph is kept and mu / sigma receive
+    gradients.
+  * the reference's class_emit einsum omits ``inputs[0]`` with embeddings on
+    (gene_pred_hmm_emitter.py:104) and returns an extra leading axis; here the result is (k, b, L, q)
+    like every other emitter output.
+  * as shipped, MvnMixture.component_log_pdf adds log_det (k1, 1, k2, c) to the transposed distances
+    (k1, batch, c, k2) (MvnMixture.py:138-148): with one component this broadcasts to (k1, batch, k2, k2) and
+    log_pdf's ``[..., 0]`` gives every row the distance to row 0's mean.  Here row r gets its own distance
+    (the diagonal of that tensor); tests/golden/mvn_diag.npz records both.
 """
+import math
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -27,28 +45,34 @@ class SimpleGenePredHMMEmitter(nn.Module):
                  initial_variance=1.0, temperature=1.0, share_intron_parameters=True, **kwargs):
         super().__init__(**kwargs)
         if emit_embeddings:
-            raise NotImplementedError("embedding emissions (MvnMixture) are outside the engine's scope")
-        assert embedding_dim is None, "embedding_dim requires emit_embeddings=True"
+            if full_covariance:
+                raise NotImplementedError("embedding emissions cover diagonal covariance only (full_covariance=False)")
+            assert embedding_dim is not None and int(embedding_dim) >= 1, "emit_embeddings=True requires embedding_dim"
+        else:
+            assert embedding_dim is None, "embedding_dim requires emit_embeddings=True"
         self.num_models = num_models
         self.num_copies = num_copies
         self.num_states = 1 + 6 * num_copies
         self.init = init
         self.trainable_emissions = trainable_emissions
-        self.emit_embeddings = False
-        self.embedding_dim = None
+        self.emit_embeddings = bool(emit_embeddings)
+        self.embedding_dim = int(embedding_dim) if emit_embeddings else None
         self.full_covariance = full_covariance
         self.embedding_kernel_init = embedding_kernel_init
         self.initial_variance = initial_variance
         self.temperature = temperature
         self.share_intron_parameters = share_intron_parameters
         self.emission_kernel = None
+        self.embedding_emission_kernel = None
         self.B = None
+        self.embedding_mu = self.embedding_sigma = None
         self.built = False
 
     def kernel_rows(self):
         return self.num_states - 2 * self.num_copies * int(self.share_intron_parameters)
 
     def build(self, input_shape):
+        """input_shape[-1] = s, the number of classes (the embedding columns are not counted)."""
         if self.built:
             return
         s = input_shape[-1]
@@ -57,19 +81,67 @@ class SimpleGenePredHMMEmitter(nn.Module):
         else:
             start = torch.full((self.num_models, self.kernel_rows(), s), float(self.init))
         self.emission_kernel = nn.Parameter(start, requires_grad=self.trainable_emissions)
+        if self.emit_embeddings:
+            assert self.num_models == 1, "embedding emissions support one model"
+            shape = (1, self.kernel_rows(), 1, 2 * self.embedding_dim)
+            if torch.is_tensor(self.embedding_kernel_init):
+                ker = self.embedding_kernel_init.detach().clone().to(torch.float32).reshape(shape)
+            elif self.embedding_kernel_init == "random_normal":
+                ker = torch.randn(shape)
+            else:
+                raise ValueError("embedding_kernel_init '%s' not supported" % (self.embedding_kernel_init,))
+            self.embedding_emission_kernel = nn.Parameter(ker, requires_grad=True)
         self.built = True
 
     def recurrent_init(self):
         self.B = self.make_B()
+        if self.emit_embeddings:
+            self.embedding_mu, self.embedding_sigma = self.make_mvn()
 
     def make_B(self):
         return F.softmax(self.emission_kernel, dim=-1)
 
-    def class_emissions(self, inputs):
-        """(k, b, L, s) class probabilities -> (k, b, L, q)."""
-        if self.B is None:
+    def make_mvn(self, dtype=None):
+        """(mu, sigma), (rows, d) each, with their graph: mu = ker[..., :d], sigma = softplus(ker[..., d:] +
+        inverse_softplus(sqrt(initial_variance))) + 1e-5 + 1e-8 (Utility.py:31-42, MvnMixture.py:98-99)."""
+        d = self.embedding_dim
+        ker = self.embedding_emission_kernel[0, :, 0, :]
+        if dtype is not None:
+            ker = ker.to(dtype)
+        shift = math.log(math.expm1(math.sqrt(float(self.initial_variance))))
+        return ker[:, :d], F.softplus(ker[:, d:] + shift) + 1e-5 + 1e-8
+
+    def embedding_log_pdf(self, emb):
+        """(..., d) embeddings -> (..., rows) log densities (MvnMixture.component_log_pdf, diag_only)."""
+        if self.embedding_mu is None:
             self.recurrent_init()
-        emit = torch.einsum("...s,kqs->k...q", inputs[0], self.B)
+        mu, sigma = self.embedding_mu, self.embedding_sigma
+        diff = emb.unsqueeze(-2) - mu
+        md = torch.sum(torch.square(diff) * torch.square(1.0 / sigma), dim=-1)
+        log_det = 2 * torch.sum(torch.log(sigma), dim=-1)
+        return -0.5 * (self.embedding_dim * math.log(2 * math.pi) + log_det + md)
+
+    def embedding_tables(self, device):
+        """(mean, inv_std (rows, d), log_norm (rows)) fp32 for hmm_embedding_emissions: computed from the
+        parameter in fp64 and rounded once."""
+        with torch.no_grad():
+            mu, sigma = self.make_mvn(torch.float64)
+            log_norm = -0.5 * self.embedding_dim * math.log(2 * math.pi) - torch.sum(torch.log(sigma), dim=-1)
+            return tuple(t.to(device, torch.float32).contiguous() for t in (mu, 1.0 / sigma, log_norm))
+
+    def class_emissions(self, inputs, training=False):
+        """(k, b, L, s) class probabilities [then d embedding columns] -> (k, b, L, q)."""
+        if self.B is None or (self.emit_embeddings and self.embedding_mu is None):
+            self.recurrent_init()
+        if self.emit_embeddings:
+            d = self.embedding_dim
+            emit = torch.einsum("...s,kqs->k...q", inputs[0][..., :-d], self.B)
+            factor = torch.exp(self.embedding_log_pdf(inputs[0][..., -d:]) / self.temperature).unsqueeze(0)
+            if training:
+                emit, factor = emit + 1e-10, factor + 1e-10
+            emit = emit * factor
+        else:
+            emit = torch.einsum("...s,kqs->k...q", inputs[0], self.B)
         if self.share_intron_parameters:
             c = self.num_copies
             emit = torch.cat([emit[..., :1 + c], emit[..., 1:1 + c], emit[..., 1:1 + c], emit[..., 1 + c:]], dim=-1)
@@ -83,7 +155,7 @@ class SimpleGenePredHMMEmitter(nn.Module):
         return torch.cat([left, emit[..., 1:-1, :], right], dim=-2)
 
     def forward(self, inputs, end_hints=None, training=False):
-        return self.apply_end_hints(self.class_emissions(inputs), end_hints)
+        return self.apply_end_hints(self.class_emissions(inputs, training=training), end_hints)
 
     def get_prior_log_density(self):
         dev = self.emission_kernel.device if self.emission_kernel is not None else None
@@ -161,6 +233,14 @@ class GenePredHMMEmitter(SimpleGenePredHMMEmitter):
     def get_nucleotide_probs(self):
         return torch.softmax(self.nuc_emission_kernel, dim=-1)
 
+    def get_aux_loss(self):
+        """l2_lambda * mean over rows of sum_c (scale kernel)^2 with embeddings on
+        (gene_pred_hmm_emitter.py:274-275, MvnMixture.py:177-181), else 0."""
+        if not self.emit_embeddings:
+            return 0.0
+        scale_kernel = self.embedding_emission_kernel[..., self.embedding_dim:]
+        return self.l2_lambda * torch.mean(torch.sum(torch.square(scale_kernel), dim=-1))
+
     def codon_emissions(self, nucleotides):
         """(k, b, L, 5) one-hot nucleotides -> (k, b, L, q) factor: 1/4096 for the first
         1 + 5*copies states, left x right 3-mer compatibility for the constrained ones."""
@@ -176,7 +256,7 @@ class GenePredHMMEmitter(SimpleGenePredHMMEmitter):
         return torch.cat([free, cod], dim=-1)
 
     def forward(self, inputs, end_hints=None, training=False):
-        """(k, b, L, s + 5): class probabilities then one-hot nucleotides -> E (k, b, L, q)."""
+        """(k, b, L, s [+ d] + 5): class probabilities, [embedding,] one-hot nucleotides -> E (k, b, L, q)."""
         nucleotides, classes = inputs[..., -5:], inputs[..., :-5]
         emit = super().forward(classes, end_hints=end_hints, training=training)
         cod = self.codon_emissions(nucleotides)
@@ -198,7 +278,7 @@ class GenePredHMMEmitter(SimpleGenePredHMMEmitter):
         # (the fused kernel serves up to 64 states; larger models, e.g. five or more copies, take forward())
         return (inputs.is_cuda and inputs.shape[0] == 1 and self.num_models == 1
                 and not self.trainable_nucleotides_at_exons and self.built
-                and self.num_states <= 64)
+                and self.num_states <= 64 and (not self.emit_embeddings or self.kernel_rows() <= 32))
 
     def state_tables(self, device):
         """(state -> kernel row, state -> codon-table row or -1) as int32 tensors."""
@@ -214,15 +294,33 @@ class GenePredHMMEmitter(SimpleGenePredHMMEmitter):
 
     def forward_fused(self, inputs, end_hints=None, training=False):
         """Same values as forward() (inference, one model) without the (b,L,64) 3-mer tensors:
-        one HIP kernel from class probabilities + nucleotides to E."""
+        one HIP kernel from class probabilities + nucleotides to E.
+
+        With embeddings, a second kernel (hmm_embedding_emissions) multiplies the normal-density factor into E,
+        reading the d embedding columns in place from `inputs`; the class kernel takes a compact (b, L, s + 5)
+        copy of the other columns.  With training=True the reference adds 1e-10 to the class term before the
+        product, which the class kernel cannot express: that case takes forward()."""
         from . import engine
         with torch.no_grad():
+            if self.emit_embeddings and training:
+                return self.forward(inputs, end_hints=end_hints, training=True)
             if self.B is None:
                 self.recurrent_init()
             row, cod = self.state_tables(inputs.device)
-            E = engine.gene_emissions(inputs[0].to(torch.float32).contiguous(), self.B[0].to(torch.float32).contiguous(),
+            x = inputs[0].to(torch.float32).contiguous()
+            if self.emit_embeddings:
+                d = self.embedding_dim
+                s = x.shape[-1] - d - 5
+                classes = torch.cat([x[..., :s], x[..., s + d:]], dim=-1)
+            else:
+                classes = x
+            E = engine.gene_emissions(classes, self.B[0].to(torch.float32).contiguous(),
                                       row, self.codon_probs.to(inputs.device, torch.float32).contiguous(), cod,
                                       add=1e-7 if training else 0.0, n_mass=2 if self.n_mass_compat else 1)
+            if self.emit_embeddings:
+                mean, inv_std, log_norm = self.embedding_tables(inputs.device)
+                engine.embedding_emissions(x, s, d, mean, inv_std, log_norm, row, E=E,
+                                           inv_temperature=1.0 / float(self.temperature))
             return self.apply_end_hints(E.unsqueeze(0), end_hints)
 
     def forward_fused_trainable(self, inputs, end_hints=None, training=False):
@@ -233,8 +331,12 @@ class GenePredHMMEmitter(SimpleGenePredHMMEmitter):
         Difference from forward(): the gradient of the five nucleotide columns of the input is exactly zero.
         One-hot nucleotides are data, and the ``== 1`` test on the N flag is not differentiable anyway; autograd
         through forward() returns small non-zero values there (up to about 3e-2 in fp64 on test-sized inputs).
-        A caller who concatenates network output with one-hot nucleotides never sees them.  Needs can_fuse(inputs)."""
+        A caller who concatenates network output with one-hot nucleotides never sees them.  Needs can_fuse(inputs).
+
+        With embeddings this is forward(): the embedding factor has no analytic backward yet."""
         from . import autograd
+        if self.emit_embeddings:
+            return self.forward(inputs, end_hints=end_hints, training=training)
         B = self.make_B()
         row, cod = self.state_tables(inputs.device)
         E = autograd.gene_emissions(inputs[0].to(torch.float32), B[0].to(torch.float32), row,

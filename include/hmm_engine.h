@@ -291,6 +291,35 @@ int hmm_gene_emissions(const float *x, int b, int L, int s, const float *B, int 
                        float free_value, float add, int n_mass, float *E, void *stream);
 
 /*
+ * Embedding-emission factor of the gene-prediction models (emit_embeddings=True): one diagonal multivariate
+ * normal per emission-kernel row, evaluated at every position's embedding and multiplied into (or written as)
+ * the emission tensor.  Replaces MvnMixture.log_pdf (hmm_layer/MvnMixture.py:125-149, diag_only, one component)
+ * and the exp / product of SimpleGenePredHMMEmitter.forward (hmm_layer/gene_pred_hmm_emitter.py:101-112) for
+ * inference with one model:
+ *   emb         first embedding float of position 0; position p's d floats start at emb + p * ld (ld >= d).
+ *               Read in place: the layer passes x + s with ld = s + d + 5.  Needs 4-byte alignment only.
+ *   mean, inv_std (rows,d)  mu and 1 / sigma of every row
+ *   log_norm    (rows)      -0.5 d log(2 pi) - sum_c log sigma[r][c]
+ *   state_row   (q) int     kernel row feeding state j (entries outside 0..rows-1 are clamped)
+ *   f[p][j] = exp(inv_temperature * (log_norm[r] - 0.5 sum_c ((x[p][c] - mean[r][c]) * inv_std[r][c])^2)) + add,
+ *             r = state_row[j]
+ *   E           (b,L,q)     multiply = 1: E[p][j] *= f[p][j] (read and written once); multiply = 0: E[p][j] = f[p][j]
+ * The caller computes inv_std and log_norm from the parameter (in fp64, rounded once).
+ * Limits: q <= 64, rows <= 32, d <= hmm_embedding_emissions_max_dim() (every d from 1 up).  Checked before any
+ * HIP call, in this order: shape (HMM_ERR_BAD_SHAPE, includes ld < d), limits (HMM_ERR_Q_UNSUPPORTED), any NULL
+ * pointer (HMM_ERR_NULL_POINTER), multiply not 0 or 1 (HMM_ERR_BAD_ARGUMENT).
+ * Runs on `stream` only, no host synchronisation, no workspace, capturable into a HIP graph; deterministic
+ * (no atomics, nothing depends on the grid); every offset into emb and E is 64-bit.
+ */
+int hmm_embedding_emissions_max_dim(void);
+int hmm_embedding_emissions(const float *emb, long long ld, int b, int L, int d,
+                            const float *mean, const float *inv_std /* (rows,d) each */,
+                            const float *log_norm /* (rows) */,
+                            int rows, const int *state_row, int q,
+                            float inv_temperature, float add, int multiply,
+                            float *E /* (b,L,q) */, void *stream);
+
+/*
  * Backward of hmm_gene_emissions: what autograd through GenePredHMMEmitter.forward
  * (hmm_layer/gene_pred_hmm_emitter.py:231-277, class part :93-121, kmer.make_k_mers hmm_layer/kmer.py:3-47)
  * computes for the class probabilities and for B, from x, the tables and the upstream gradient alone
