@@ -99,3 +99,40 @@ class GeneEmissions(torch.autograd.Function):
 def gene_emissions(x, B, state_row, codon, state_codon, add=0.0, n_mass=1):
     """Differentiable fused emitter: E (b,L,q) with gradients for x's class columns and B."""
     return GeneEmissions.apply(x, B, state_row, codon, state_codon, add, n_mass)
+
+
+class EmbeddingEmissions(torch.autograd.Function):
+    """E_out (b,L,q) = E_in * (exp(inv_temperature * log N(x[..., col0:col0+d]; mean, 1/inv_std)) + add)[..., state_row]
+    (E_in None: the factor alone).  Forward = hmm_embedding_emissions on a fresh output (E_in survives for the
+    backward), backward = hmm_embedding_emissions_grad.  Differentiable in E_in, x (embedding columns; every other
+    column of its gradient is exactly 0), mean, inv_std and log_norm.  Saved: E_in, x, the three tables and
+    state_row — not the factor, and nothing of size b L rows d."""
+
+    @staticmethod
+    def forward(ctx, E_in, x, mean, inv_std, log_norm, state_row, col0, d, inv_temperature, add):
+        x, mean, inv_std, log_norm = x.contiguous(), mean.contiguous(), inv_std.contiguous(), log_norm.contiguous()
+        if E_in is not None:
+            E_in = E_in.contiguous()
+        ctx.save_for_backward(E_in, x, mean, inv_std, log_norm, state_row)
+        ctx.args = (int(col0), int(d), float(inv_temperature), float(add))
+        return engine.embedding_emissions(x, col0, d, mean, inv_std, log_norm, state_row,
+                                          E=None if E_in is None else E_in.clone(),
+                                          inv_temperature=inv_temperature, add=add)
+
+    @staticmethod
+    def backward(ctx, dE):
+        E_in, x, mean, inv_std, log_norm, state_row = ctx.saved_tensors
+        col0, d, inv_temperature, add = ctx.args
+        need = ctx.needs_input_grad
+        tables = any(need[2:5])
+        dE_in, dx, dmean, dinv_std, dlog_norm = engine.embedding_emissions_grad(
+            x, col0, d, mean, inv_std, log_norm, state_row, dE.to(torch.float32).contiguous(), E_in=E_in,
+            inv_temperature=inv_temperature, add=add, want_dE_in=need[0], want_demb=need[1], want_tables=tables,
+            dx_out=torch.zeros_like(x) if need[1] else None)
+        return (dE_in, dx, dmean if need[2] else None, dinv_std if need[3] else None,
+                dlog_norm if need[4] else None, None, None, None, None, None)
+
+
+def embedding_emissions(E_in, x, mean, inv_std, log_norm, state_row, col0, d, inv_temperature=1.0, add=0.0):
+    """Differentiable embedding-emission factor multiplied into E_in (b,L,q) (None: the factor alone)."""
+    return EmbeddingEmissions.apply(E_in, x, mean, inv_std, log_norm, state_row, col0, d, inv_temperature, add)

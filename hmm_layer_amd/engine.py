@@ -98,6 +98,10 @@ _SIGNATURES = {
     "hmm_gene_emissions_grad": (_I, _EMITTER + [_P, _P, _P, _P, _SZ, _P]),
     "hmm_embedding_emissions_max_dim": (_I, []),
     "hmm_embedding_emissions": (_I, [_P, _LL, _I, _I, _I, _P, _P, _P, _I, _P, _I, _F, _F, _I, _P, _P]),
+    "hmm_embedding_emissions_grad_max_dim": (_I, []),
+    "hmm_embedding_emissions_grad_workspace_bytes": (_SZ, [_I] * 5),
+    "hmm_embedding_emissions_grad": (_I, [_P, _LL, _I, _I, _I, _P, _P, _P, _I, _P, _I, _F, _F, _P, _P, _P, _P, _LL,
+                                          _P, _P, _P, _P, _SZ, _P]),
     "hmm_loglik_partials": (_I, [_P, _P, _I, _I, _P, _P]),
     "hmm_loglik_allreduce": (_I, [_P, _P, _I, _P]),
     "hmm_seqshard_workspace_bytes": (_SZ, [_I] * 5),
@@ -418,11 +422,9 @@ def gene_emissions_grad(x, B, state_row, codon, state_codon, dE, free_value=1.0 
     return dx, dB
 
 
-def embedding_emissions(x, col0, d, mean, inv_std, log_norm, state_row, E=None, inv_temperature=1.0, add=0.0):
-    """Embedding-emission factor (hmm_embedding_emissions): x (b,L,w) fp32 holds every position's embedding in
-    columns col0 .. col0+d-1, read in place (no copy of the columns is made).  mean, inv_std (rows,d) fp32,
-    log_norm (rows) fp32, state_row (q) int32.  f = exp(inv_temperature * log N(x; mean, 1/inv_std)) + add.
-    With E (b,L,q) given, E *= f in place; otherwise a new E = f.  Returns E."""
+def _embedding_args(x, col0, d, mean, inv_std, log_norm, state_row):
+    """Validation shared by embedding_emissions and embedding_emissions_grad -> (the five tensors, col0, d,
+    (b, L, w, rows, q))."""
     x, mean, inv_std, log_norm = _dev(x, "x"), _dev(mean, "mean"), _dev(inv_std, "inv_std"), _dev(log_norm, "log_norm")
     state_row = _dev(state_row, "state_row", torch.int32)
     if x.dim() != 3:
@@ -434,10 +436,24 @@ def embedding_emissions(x, col0, d, mean, inv_std, log_norm, state_row, E=None, 
         raise ValueError("columns %d .. %d lie outside x's %d columns" % (col0, col0 + d - 1, w))
     if tuple(mean.shape) != (rows, d) or tuple(inv_std.shape) != (rows, d) or log_norm.numel() != rows:
         raise ValueError("inconsistent embedding tables")
+    return x, mean, inv_std, log_norm, state_row, col0, d, (b, L, w, rows, q)
+
+
+def _is_E(t, shape):
+    return (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+            and tuple(t.shape) == shape)
+
+
+def embedding_emissions(x, col0, d, mean, inv_std, log_norm, state_row, E=None, inv_temperature=1.0, add=0.0):
+    """Embedding-emission factor (hmm_embedding_emissions): x (b,L,w) fp32 holds every position's embedding in
+    columns col0 .. col0+d-1, read in place (no copy of the columns is made).  mean, inv_std (rows,d) fp32,
+    log_norm (rows) fp32, state_row (q) int32.  f = exp(inv_temperature * log N(x; mean, 1/inv_std)) + add.
+    With E (b,L,q) given, E *= f in place; otherwise a new E = f.  Returns E."""
+    x, mean, inv_std, log_norm, state_row, col0, d, (b, L, w, rows, q) = _embedding_args(
+        x, col0, d, mean, inv_std, log_norm, state_row)
     multiply = E is not None
     if multiply:
-        if not (torch.is_tensor(E) and E.is_cuda and E.dtype == torch.float32 and E.is_contiguous()
-                and tuple(E.shape) == (b, L, q)):
+        if not _is_E(E, (b, L, q)):
             raise ValueError("E must be a contiguous fp32 device tensor of shape %s" % ((b, L, q),))
     with torch.cuda.device(x.device):
         if not multiply:
@@ -447,6 +463,53 @@ def embedding_emissions(x, col0, d, mean, inv_std, log_norm, state_row, E=None, 
                                              float(inv_temperature), float(add), int(multiply), E.data_ptr(),
                                              _stream(x.device)))
     return E
+
+
+def embedding_emissions_grad(x, col0, d, mean, inv_std, log_norm, state_row, dE, E_in=None, inv_temperature=1.0,
+                             add=0.0, want_dE_in=True, want_demb=True, want_tables=True, dx_out=None):
+    """Backward of embedding_emissions (hmm_embedding_emissions_grad): dE (b,L,q) = dL/dE_out ->
+    (dE_in (b,L,q) | None, demb | None, dmean (rows,d) | None, dinv_std (rows,d) | None, dlog_norm (rows) | None).
+    x, col0, d and the tables as for embedding_emissions; E_in (b,L,q) is the tensor the forward multiplied
+    into (None: the forward wrote E = f, and there is no dE_in).  demb is a new (b,L,d) tensor, or, with dx_out
+    (a contiguous fp32 tensor of x's shape) given, dx_out itself with its columns col0 .. col0+d-1 overwritten
+    in place and every other column left as it was.  The three table gradients are written whole and summed in
+    a fixed order: repeated calls, and calls for a subset of the outputs, are bit-identical.  The workspace
+    (W (b L, rows) and at most 16 MiB of workgroup partials) comes from the engine's cache under a key of its
+    own per device and stream."""
+    x, mean, inv_std, log_norm, state_row, col0, d, (b, L, w, rows, q) = _embedding_args(
+        x, col0, d, mean, inv_std, log_norm, state_row)
+    if not _is_E(dE, (b, L, q)):
+        raise ValueError("dE must be a contiguous fp32 device tensor of shape %s" % ((b, L, q),))
+    if E_in is not None and not _is_E(E_in, (b, L, q)):
+        raise ValueError("E_in must be a contiguous fp32 device tensor of shape %s" % ((b, L, q),))
+    if dx_out is not None and not _is_E(dx_out, (b, L, w)):
+        raise ValueError("dx_out must be a contiguous fp32 device tensor of shape %s" % ((b, L, w),))
+    want_dE_in = bool(want_dE_in) and E_in is not None
+    if not (want_dE_in or want_demb or want_tables):
+        return None, None, None, None, None
+    need = lib().hmm_embedding_emissions_grad_workspace_bytes(b, L, d, rows, q)
+    if need == 0:
+        raise ValueError("hmm_embedding_emissions_grad covers q <= 64, rows <= 32, d <= %d (got q = %d, rows = %d, "
+                         "d = %d)" % (lib().hmm_embedding_emissions_grad_max_dim(), q, rows, d))
+    with torch.cuda.device(x.device):
+        ws = _workspace(x.device, need, "embedding_grad", floor=0)
+        dE_in = torch.empty_like(dE) if want_dE_in else None
+        demb, demb_ptr, ldd = None, None, 0
+        if want_demb and dx_out is not None:
+            demb, demb_ptr, ldd = dx_out, dx_out.data_ptr() + 4 * col0, w
+        elif want_demb:
+            demb = torch.empty((b, L, d), dtype=torch.float32, device=x.device)
+            demb_ptr, ldd = demb.data_ptr(), d
+        dmean = torch.empty_like(mean) if want_tables else None
+        dinv_std = torch.empty_like(inv_std) if want_tables else None
+        dlog_norm = torch.empty_like(log_norm) if want_tables else None
+        _check(lib().hmm_embedding_emissions_grad(
+            x.data_ptr() + 4 * col0, w, b, L, d, mean.data_ptr(), inv_std.data_ptr(), log_norm.data_ptr(), rows,
+            state_row.data_ptr(), q, float(inv_temperature), float(add),
+            E_in.data_ptr() if E_in is not None else None, dE.data_ptr(), dE_in.data_ptr() if want_dE_in else None,
+            demb_ptr, ldd, dmean.data_ptr() if want_tables else None, dinv_std.data_ptr() if want_tables else None,
+            dlog_norm.data_ptr() if want_tables else None, ws.data_ptr(), ws.numel(), _stream(x.device)))
+    return dE_in, demb, dmean, dinv_std, dlog_norm
 
 
 def _viterbi(name, logA, logpi, logE):

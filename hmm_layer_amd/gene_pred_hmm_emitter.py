@@ -15,7 +15,9 @@ Embedding emissions (``emit_embeddings=True``, inputs (k, b, L, s + d [+ 5])): o
 covariance, one mixture component — the reference's MvnMixture(diag_only=True) with
 DefaultDiagBijector(initial_variance), written out in torch ops here (``embedding_log_pdf``) and fused
 for inference (``forward_fused``: hmm_gene_emissions, then hmm_embedding_emissions multiplying into E
-with the embedding columns read in place).  ``full_covariance=True`` raises NotImplementedError.
+with the embedding columns read in place) and for training with ``fused_training=True``
+(``forward_fused_trainable``: autograd.EmbeddingEmissions, backward hmm_embedding_emissions_grad).
+``full_covariance=True`` raises NotImplementedError.
 Three more differences from the as-shipped reference, on purpose:
   * MvnMixture.__init__ copies the parameter with ``torch.tensor(kernel)`` (MvnMixture.py:40), so the
     reference never trains ``embedding_emission_kernel``; here the graph is kept and mu / sigma receive
@@ -128,6 +130,14 @@ class SimpleGenePredHMMEmitter(nn.Module):
             mu, sigma = self.make_mvn(torch.float64)
             log_norm = -0.5 * self.embedding_dim * math.log(2 * math.pi) - torch.sum(torch.log(sigma), dim=-1)
             return tuple(t.to(device, torch.float32).contiguous() for t in (mu, 1.0 / sigma, log_norm))
+
+    def embedding_tables_with_graph(self, device):
+        """embedding_tables with its autograd graph, for training through hmm_embedding_emissions_grad: the same
+        fp64 chain from the parameter (softplus, reciprocal, log), cast to fp32 once.  The kernel's three table
+        gradients flow back to embedding_emission_kernel through these (rows, d)-sized torch ops."""
+        mu, sigma = self.make_mvn(torch.float64)
+        log_norm = -0.5 * self.embedding_dim * math.log(2 * math.pi) - torch.sum(torch.log(sigma), dim=-1)
+        return tuple(t.to(device, torch.float32).contiguous() for t in (mu, 1.0 / sigma, log_norm))
 
     def class_emissions(self, inputs, training=False):
         """(k, b, L, s) class probabilities [then d embedding columns] -> (k, b, L, q)."""
@@ -333,15 +343,36 @@ class GenePredHMMEmitter(SimpleGenePredHMMEmitter):
         through forward() returns small non-zero values there (up to about 3e-2 in fp64 on test-sized inputs).
         A caller who concatenates network output with one-hot nucleotides never sees them.  Needs can_fuse(inputs).
 
-        With embeddings this is forward(): the embedding factor has no analytic backward yet."""
+        With embeddings a second node follows (autograd.EmbeddingEmissions: hmm_embedding_emissions forward,
+        hmm_embedding_emissions_grad backward) that multiplies the normal-density factor into E, reading the d
+        embedding columns of the input in place; the class node takes the compact (b, L, s + 5) copy of the other
+        columns.  The tables come from embedding_tables_with_graph, so embedding_emission_kernel trains.  With
+        training=True the reference adds 1e-10 to the class term before the product ((C + 1e-10) (f + 1e-10)
+        (cod + 1e-7)): the compact tensor gets one more class column of value 1e-10 and B a column of ones, so
+        that C + 1e-10 comes out of the unchanged class kernel (torch.cat's backward drops the column again).
+        That needs s + 1 <= 32 classes; above that, and where can_fuse(inputs) does not hold, this is forward()."""
         from . import autograd
-        if self.emit_embeddings:
-            return self.forward(inputs, end_hints=end_hints, training=training)
-        B = self.make_B()
+        B = self.make_B()[0].to(torch.float32)
         row, cod = self.state_tables(inputs.device)
-        E = autograd.gene_emissions(inputs[0].to(torch.float32), B[0].to(torch.float32), row,
-                                    self.codon_probs.to(inputs.device, torch.float32).contiguous(), cod,
-                                    add=1e-7 if training else 0.0, n_mass=2 if self.n_mass_compat else 1)
+        x = inputs[0].to(torch.float32)
+        kw = dict(add=1e-7 if training else 0.0, n_mass=2 if self.n_mass_compat else 1)
+        codon = self.codon_probs.to(inputs.device, torch.float32).contiguous()
+        if not self.emit_embeddings:
+            E = autograd.gene_emissions(x, B, row, codon, cod, **kw)
+            return self.apply_end_hints(E.unsqueeze(0), end_hints)
+        d = self.embedding_dim
+        s = x.shape[-1] - d - 5
+        if (training and s + 1 > 32) or not self.can_fuse(inputs):
+            return self.forward(inputs, end_hints=end_hints, training=training)
+        parts = [x[..., :s], x[..., s + d:]]
+        if training:
+            parts.insert(1, torch.full_like(x[..., :1], 1e-10))
+            B = torch.cat([B, torch.ones_like(B[:, :1])], dim=-1)
+        E = autograd.gene_emissions(torch.cat(parts, dim=-1), B, row, codon, cod, **kw)
+        mean, inv_std, log_norm = self.embedding_tables_with_graph(inputs.device)
+        E = autograd.embedding_emissions(E, x, mean, inv_std, log_norm, row, s, d,
+                                         inv_temperature=1.0 / float(self.temperature),
+                                         add=1e-10 if training else 0.0)
         return self.apply_end_hints(E.unsqueeze(0), end_hints)
 
     def get_config(self):

@@ -320,6 +320,48 @@ int hmm_embedding_emissions(const float *emb, long long ld, int b, int L, int d,
                             float *E /* (b,L,q) */, void *stream);
 
 /*
+ * Backward of hmm_embedding_emissions: what autograd through the reference's ops (MvnMixture.log_pdf, exp, the
+ * product with E) computes, from the inputs, the tables and the upstream gradient alone; nothing of size
+ * b*L*rows*d is formed.  Arguments as for hmm_embedding_emissions, with g = f - add, r = row(j) = state_row[j]
+ * clamped, and
+ *   E_in        (b,L,q)     the tensor the forward multiplied into, or NULL for the multiply = 0 forward (E_in = 1)
+ *   dE          (b,L,q)     upstream gradient dL/dE_out
+ *   dE_in       (b,L,q)     or NULL: dE[p][j] * f[p][r].  Needs E_in; must not alias dE.
+ *   demb                    or NULL: position p's d floats at demb + p * ldd (ldd >= d), so the caller can point it
+ *                           at the embedding columns of an input-gradient tensor:
+ *                           demb[p][c] = -sum_r W[p][r] (x[p][c] - mean[r][c]) inv_std[r][c]^2
+ *   dmean, dinv_std (rows,d), dlog_norm (rows)   all three or none; written whole (the caller zeroes nothing):
+ *                           dlog_norm[r]   = sum_p W[p][r]
+ *                           dmean[r][c]    = sum_p W[p][r] (x[p][c] - mean[r][c]) inv_std[r][c]^2
+ *                           dinv_std[r][c] = -sum_p W[p][r] (x[p][c] - mean[r][c])^2 inv_std[r][c]
+ *   W[p][r] = inv_temperature * g[p][r] * sum_{j: row(j) = r} dE[p][j] E_in[p][j]   (ascending j; add has no gradient)
+ * Everything is evaluated in the difference form ((x - mean) first), like the forward.  Reduction order of the
+ * three table gradients: fp32 inside a workgroup (its positions in ascending order per position group, the
+ * groups in group order), one partial per workgroup in the workspace, then the partials in workgroup order in
+ * fp64, times inv_std^2 / -inv_std in fp64, rounded to fp32 once.  No atomics: repeated calls, and calls for any
+ * subset of the outputs, are bit-identical.
+ * Limits: q <= 64, rows <= 32, d <= hmm_embedding_emissions_grad_max_dim() (4096; every d from 1 up).  Checked
+ * before any HIP call, in this order: shape (HMM_ERR_BAD_SHAPE, includes ld < d, and ldd < d with demb given),
+ * limits (HMM_ERR_Q_UNSUPPORTED), pointers (HMM_ERR_NULL_POINTER: any input, the workspace, no output at all,
+ * one or two of the three table gradients, dE_in without E_in), workspace (HMM_ERR_WORKSPACE: fewer than
+ * hmm_embedding_emissions_grad_workspace_bytes bytes, or not 256-byte aligned).  The workspace holds W
+ * (b*L x rows rounded up to 4 floats, passed between the two kernels) and at most 1024 workgroup partials of
+ * rows * (2 d + 1) floats, at most 16 MiB of them (the grid shrinks as rows * d grows): the partials stop growing
+ * with b*L.  The query returns 0 for an unsupported shape.  Runs on `stream` only, no host synchronisation,
+ * capturable into a HIP graph; every offset into emb, demb, E_in, dE and dE_in is 64-bit.
+ */
+int hmm_embedding_emissions_grad_max_dim(void);
+size_t hmm_embedding_emissions_grad_workspace_bytes(int b, int L, int d, int rows, int q);
+int hmm_embedding_emissions_grad(const float *emb, long long ld, int b, int L, int d,
+                                 const float *mean, const float *inv_std, const float *log_norm, int rows,
+                                 const int *state_row, int q, float inv_temperature, float add,
+                                 const float *E_in /* (b,L,q) or NULL */, const float *dE /* (b,L,q) */,
+                                 float *dE_in /* (b,L,q) or NULL */,
+                                 float *demb, long long ldd /* or NULL */,
+                                 float *dmean, float *dinv_std /* (rows,d) */, float *dlog_norm /* (rows) */,
+                                 void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Backward of hmm_gene_emissions: what autograd through GenePredHMMEmitter.forward
  * (hmm_layer/gene_pred_hmm_emitter.py:231-277, class part :93-121, kmer.make_k_mers hmm_layer/kmer.py:3-47)
  * computes for the class probabilities and for B, from x, the tables and the upstream gradient alone
