@@ -742,7 +742,7 @@ __device__ __forceinline__ void reduce_sparse_wave(const float *__restrict__ A, 
         if (SUM) {
             // (32-lane rows — the 29-state model: a column that loses more than 2^-45 between two sums has met an
             // observation that everything survives at the emission floor only; such sequences go to the serial kernels,
-            // k32_select, on top of the certificates of the 32-state apply kernels)
+            // k_scan_select, on top of the certificates of the 32-state apply kernels)
             if (W >= 32) {                      // ... EVERY column of the chain, whatever the start state
                 const unsigned long long keep = __builtin_amdgcn_ballot_w64(kc < Q && !(s < cs * 0x1p-45f));
                 const unsigned long long mine = W == 64 ? ~0ull : (((1ull << (W & 63)) - 1ull) << (W * cl));
@@ -2700,8 +2700,7 @@ static int check_ws(size_t total, void *ws, size_t bytes) {
 
 #include "hmm_largeq.inc"
 #include "hmm_midq.inc"
-#include "hmm_scan32.inc"
-#include "hmm_scan64.inc"
+#include "hmm_scan_rows.inc"
 #include "hmm_scan_mid.inc"
 
 extern "C" {

@@ -2,7 +2,7 @@
 // model of up to 64 states (included by hmm_engine.hip after hmm_postgrad.inc).
 //
 // hmm_loglik_grad runs per chunk for q <= 16 (hmm_grad.inc) and for the compiled 29-state topology
-// (hmm_postgrad_chunked.inc: k_pc_values + k_pc_llgrad on hmm_scan32.inc's plan); every other model of 17..64 states
+// (hmm_postgrad_chunked.inc: k_pc_values + k_pc_llgrad on hmm_scan_rows.inc's plan); every other model of 17..64 states
 // walks two whole-sequence sweeps, one wave per sequence (hmm_midq.inc): 32 waves at b = 32 x L = 9 999.  This entry
 // point runs the per-chunk kernels on the scan plan of EITHER row width — rows of 32 lanes, two chunks per wave, for
 // 17..32 states; rows of 64, a chunk per wave, for 33..64 — behind the dense reduces and chunk scans of

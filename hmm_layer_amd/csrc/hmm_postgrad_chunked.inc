@@ -1,5 +1,5 @@
 // hmm_postgrad_chunked.inc — the sweeps of hmm_postgrad.inc cut into the chunks of the scan plan (q <= 16, and
-// the compiled 29-state topology on hmm_scan32.inc's plan; included by hmm_postgrad.inc).  At the end of the
+// the compiled 29-state topology on hmm_scan_rows.inc's plan; included by hmm_postgrad.inc).  At the end of the
 // file: the log-likelihood gradient of the 29-state topology on the same value sweeps.
 //
 // hmm_postgrad.inc walks four dependent chains over the whole sequence: 12 ms at the reference's own
@@ -173,7 +173,7 @@ template <> struct PcW<64> {
     static __device__ __forceinline__ float sum(float v) { return mq_wave_sum(v); }
     template <int K> static __device__ __forceinline__ float bc(float v) { return lane_bcast(v, K); }
     template <int K> static __device__ __forceinline__ void fmac_bc(float &acc, float v, float c) { acc = fmaf(bc<K>(v), c, acc); }
-    // k64_check's verdict (elig[m] = ID_DENSE64, or 0: not primitive)
+    // k64_check's verdict (elig[m] = Rows<4>::ID_DENSE, or 0: not primitive)
     static __device__ __forceinline__ bool model_serial(const int *route, int m) { return route[m] == 0; }
 };
 template <int W, int K> struct PcLoop {
@@ -783,7 +783,7 @@ __global__ __launch_bounds__(64) void k_pc_llgrad(const float *__restrict__ A, c
 }
 
 // need[seq]: the whole-sequence sweeps redo it.  One wave per sequence.  exps / risk (or null): the reduces' marks
-// as k32_select reads them — a chain whose operator went through the denormal range, or survives an observation at
+// as k_scan_select reads them — a chain whose operator went through the denormal range, or survives an observation at
 // the emission floor only, flags its sequence.
 template <int W>
 __global__ __launch_bounds__(64) void k_pc_llselect(const float *__restrict__ inv_sg, const int *__restrict__ route, Plan p,
@@ -799,7 +799,7 @@ __global__ __launch_bounds__(64) void k_pc_llselect(const float *__restrict__ in
         for (int c = threadIdx.x; c < p.C; c += 64) {
             const size_t chain = (size_t)seq * p.C + c;
             s += inv_sg[chain];
-            if (risk) mark = mark || ((el == ID_DENSE32 || el == ID_DENSE64) ? risk[chain] != 0 : exps[chain * W + W - 1] != 0);
+            if (risk) mark = mark || (elig_dense(el) ? risk[chain] != 0 : exps[chain * W + W - 1] != 0);
         }
     const float F = mq_wave_sum(s) * eps;
     mark = __builtin_amdgcn_ballot_w64(mark) != 0ull;

@@ -1,6 +1,7 @@
 // hmm_scan_mid.inc — host side of the chunked scan for 17..64 states, included by hmm_engine.hip after the kernels
-// of both row widths (hmm_scan32.inc, hmm_scan64.inc): one plan, one set of drivers.  What differs between the two
-// widths lives in the traits types Scan32 / Scan64 and nowhere else.
+// (hmm_scan_rows.inc): one plan, one set of drivers.  The kernels are templates over the row width (NT tile rows);
+// what else differs between the two widths — the model check and how the reduce stage is launched — lives in the
+// traits types Scan32 / Scan64.
 
 struct MidPlan {
     Plan p;                           // shape and chunking (k, b, L, q, NB, T, C, nchains; nsub = T / the width's SUB)
@@ -17,7 +18,7 @@ static int make_midplan(int op, int k, int b, int L, int q, int W, MidPlan *pp, 
     p.k = k; p.b = b; p.L = L; p.q = q; p.NB = k * b;
     p.T = T_fixed ? T_fixed : choose_T(p.NB, L);
     p.C = (L + p.T - 1) / p.T;
-    p.nsub = p.T / (W == Q32 ? SUB32 : SUB64);
+    p.nsub = p.T / (W == Q32 ? Rows<2>::BLK : Rows<4>::BLK);
     p.nchains = (long long)p.NB * p.C;
     p.cpw = 16; p.seq_start = 1; p.G = 0; p.gsize = 0;
     pp->nwaves = (long long)k * (((long long)b * p.C + 15) / 16);
@@ -48,10 +49,9 @@ static int mid_width(int k, int b, int L, int q) {
     return scan64_wanted(k, b, L, q) ? Q64 : 0;
 }
 
-// ---- what differs between the widths: the constants, how the model check and the reduce stage are launched, and
-// which scan / apply kernels run
+// ---- what differs between the widths on the host: how the model check and the reduce stage are launched
 struct Scan32 {
-    static constexpr int W = Q32;
+    static constexpr int NT = 2, W = Rows<NT>::W;
     static void check(const float *A, const MidPlan &pp, float eps, char *ws, hipStream_t st) {
         hipLaunchKernelGGL(k32_check, dim3(pp.p.k), dim3(64), 0, st, A, (int *)(ws + pp.o_elig), pp.p.q, opt(HMM_OPT_EXACT),
                            eps, (int *)(ws + pp.o_nex), opt(HMM_OPT_FORCE_DENSE) == 1 ? 1 : 0);
@@ -68,22 +68,13 @@ struct Scan32 {
             hipLaunchKernelGGL((k_reduce_sparse_wide<TopoGene29, true>), dim3(nb), dim3(256), 0, st, A, E, ops, exps, elig, p, eps);
         // every chain its own wave (grid stride; exits at once for the models the sparse kernels served)
         const long long nbd = (p.nchains + 3) / 4;
-        hipLaunchKernelGGL(k32_reduce_dense, dim3((unsigned)(nbd < 8192 ? nbd : 8192)), dim3(256), 0, st, A, E, ops, exps,
+        hipLaunchKernelGGL(reduce_dense<NT>, dim3((unsigned)(nbd < 8192 ? nbd : 8192)), dim3(256), 0, st, A, E, ops, exps,
                            (int *)(ws + pp.o_risk), elig, p, eps);
-    }
-    template <class... Args> static void scan(dim3 grid, hipStream_t st, Args... args) {
-        hipLaunchKernelGGL(k32_scan, grid, dim3(128), 0, st, args...);
-    }
-    template <bool LOGA, bool CERT, class... Args> static void forward(dim3 grid, hipStream_t st, Args... args) {
-        hipLaunchKernelGGL((k32_forward<LOGA, CERT>), grid, dim3(256), 0, st, args...);
-    }
-    template <int MODE, bool CERT3, class... Args> static void backward(dim3 grid, hipStream_t st, Args... args) {
-        hipLaunchKernelGGL((k32_backward<MODE, CERT3>), grid, dim3(256), 0, st, args...);
     }
 };
 
 struct Scan64 {
-    static constexpr int W = Q64;
+    static constexpr int NT = 4, W = Rows<NT>::W;
     static void check(const float *A, const MidPlan &pp, float eps, char *ws, hipStream_t st) {
         hipLaunchKernelGGL(k64_check, dim3(pp.p.k), dim3(64), 0, st, A, (int *)(ws + pp.o_elig), pp.p.q, opt(HMM_OPT_EXACT),
                            eps, (int *)(ws + pp.o_nex), pp.p.NB, opt(HMM_OPT_FORCE_DENSE) == 1 ? 1 : 0);
@@ -91,18 +82,9 @@ struct Scan64 {
     static void reduce(const float *A, const float *E, const MidPlan &pp, float eps, char *ws, hipStream_t st) {
         const Plan &p = pp.p;
         const long long nbd = (p.nchains + 3) / 4;
-        hipLaunchKernelGGL(k64_reduce_dense, dim3((unsigned)(nbd < 8192 ? nbd : 8192)), dim3(256), 0, st, A, E,
+        hipLaunchKernelGGL(reduce_dense<NT>, dim3((unsigned)(nbd < 8192 ? nbd : 8192)), dim3(256), 0, st, A, E,
                            (float *)(ws + pp.o_ops), (int *)(ws + pp.o_exps), (int *)(ws + pp.o_risk),
                            (const int *)(ws + pp.o_elig), p, eps);
-    }
-    template <class... Args> static void scan(dim3 grid, hipStream_t st, Args... args) {
-        hipLaunchKernelGGL(k64_scan, grid, dim3(128), 0, st, args...);
-    }
-    template <bool LOGA, bool CERT, class... Args> static void forward(dim3 grid, hipStream_t st, Args... args) {
-        hipLaunchKernelGGL((k64_forward<LOGA, CERT>), grid, dim3(256), 0, st, args...);
-    }
-    template <int MODE, bool CERT3, class... Args> static void backward(dim3 grid, hipStream_t st, Args... args) {
-        hipLaunchKernelGGL((k64_backward<MODE, CERT3>), grid, dim3(256), 0, st, args...);
     }
 };
 
@@ -114,16 +96,17 @@ static void scan_reduce_scan(const float *A, const float *pi, const float *E, co
     const Plan &p = pp.p;
     S::check(A, pp, eps, ws, st);
     S::reduce(A, E, pp, eps, ws, st);
-    S::scan(dim3(p.NB), st, pi, (const float *)(ws + pp.o_ops), (const int *)(ws + pp.o_exps), (float *)(ws + pp.o_prefix),
-            (double *)(ws + pp.o_llpre), (float *)(ws + pp.o_suffix), (double *)(ws + pp.o_lsuf),
-            (double *)(ws + pp.o_loglik), (const int *)(ws + pp.o_elig), p, eps);
+    hipLaunchKernelGGL(scan<S::NT>, dim3(p.NB), dim3(128), 0, st, pi, (const float *)(ws + pp.o_ops),
+                       (const int *)(ws + pp.o_exps), (float *)(ws + pp.o_prefix), (double *)(ws + pp.o_llpre),
+                       (float *)(ws + pp.o_suffix), (double *)(ws + pp.o_lsuf), (double *)(ws + pp.o_loglik),
+                       (const int *)(ws + pp.o_elig), p, eps);
 }
 
-// need[] from the certificate sums phi (or null: the reduces' marks only); k32_select serves both widths
+// need[] from the certificate sums phi (or null: the reduces' marks only); one kernel for both widths
 template <class S>
 static void scan_select(const MidPlan &pp, const float *phi, char *ws, hipStream_t st) {
     const Plan &p = pp.p;
-    hipLaunchKernelGGL(k32_select, dim3((p.NB + 255) / 256), dim3(256), 0, st, (const int *)(ws + pp.o_elig), phi,
+    hipLaunchKernelGGL(k_scan_select, dim3((p.NB + 255) / 256), dim3(256), 0, st, (const int *)(ws + pp.o_elig), phi,
                        (int *)(ws + pp.o_need), (int *)(ws + pp.o_nex), p, 0.f, opt(HMM_OPT_EXACT),
                        (const int *)(ws + pp.o_exps), (const int *)(ws + pp.o_risk), S::W);
 }
@@ -138,9 +121,9 @@ static void scan_loglik(const float *A, const float *pi, const float *E, const M
     const bool cert = opt(HMM_OPT_EXACT) == HMM_EXACT_AUTO;
     float *phi = (float *)(ws + pp.o_phi);
     if (cert)
-        S::template forward<false, true>(dim3((unsigned)((pp.nwaves + 3) / 4)), st, A, E, (const float *)(ws + pp.o_prefix),
-                                         nullptr, nullptr, nullptr, (const int *)(ws + pp.o_elig), pp.p, eps, pp.nwaves,
-                                         (const float *)(ws + pp.o_suffix), phi);
+        hipLaunchKernelGGL((forward<S::NT, false, true>), dim3((unsigned)((pp.nwaves + 3) / 4)), dim3(256), 0, st, A, E,
+                           (const float *)(ws + pp.o_prefix), nullptr, nullptr, nullptr, (const int *)(ws + pp.o_elig),
+                           pp.p, eps, pp.nwaves, (const float *)(ws + pp.o_suffix), phi);
     scan_select<S>(pp, cert ? phi : nullptr, ws, st);
 }
 
@@ -152,18 +135,16 @@ static void scan_posterior(const float *A, const float *pi, const float *E, cons
     const int *elig = (const int *)(ws + pp.o_elig);
     float *ckpt = (float *)(ws + pp.o_ckpt);
     const dim3 grid((unsigned)((pp.nwaves + 3) / 4));
-    S::template forward<false, false>(grid, st, A, E, (const float *)(ws + pp.o_prefix), nullptr, ckpt, nullptr, elig, p, eps,
-                                      pp.nwaves, nullptr, nullptr);
+    hipLaunchKernelGGL((forward<S::NT, false, false>), grid, dim3(256), 0, st, A, E, (const float *)(ws + pp.o_prefix),
+                       nullptr, ckpt, nullptr, elig, p, eps, pp.nwaves, nullptr, nullptr);
     const float *sx = (const float *)(ws + pp.o_suffix);
     const double *ls = (const double *)(ws + pp.o_lsuf);
     const double *ll = (const double *)(ws + pp.o_loglik);
     float *phi = (float *)(ws + pp.o_phi);
-    if (mode == HMM_POST_PROB)
-        S::template backward<0, false>(grid, st, A, E, ckpt, sx, ls, ll, out, phi, elig, p, eps, pp.nwaves, nullptr);
-    else if (mode == HMM_POST_LOG)
-        S::template backward<1, false>(grid, st, A, E, ckpt, sx, ls, ll, out, phi, elig, p, eps, pp.nwaves, nullptr);
-    else
-        S::template backward<2, false>(grid, st, A, E, ckpt, sx, ls, ll, out, phi, elig, p, eps, pp.nwaves, nullptr);
+    auto *kern = mode == HMM_POST_PROB ? backward<S::NT, 0, false>
+                 : mode == HMM_POST_LOG ? backward<S::NT, 1, false> : backward<S::NT, 2, false>;
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, A, E, (const float *)ckpt, sx, ls, ll, out, phi, elig, p, eps,
+                       pp.nwaves, nullptr);
     scan_select<S>(pp, phi, ws, st);
 }
 
@@ -175,9 +156,9 @@ static void scan_forward(const float *A, const float *pi, const float *E, const 
                          char *ws, hipStream_t st) {
     scan_reduce_scan<S>(A, pi, E, pp, eps, ws, st);
     float *phi = (float *)(ws + pp.o_phi);
-    S::template forward<true, true>(dim3((unsigned)((pp.nwaves + 3) / 4)), st, A, E, (const float *)(ws + pp.o_prefix),
-                                    (const double *)(ws + pp.o_llpre), nullptr, log_alpha, (const int *)(ws + pp.o_elig),
-                                    pp.p, eps, pp.nwaves, (const float *)(ws + pp.o_suffix), phi);
+    hipLaunchKernelGGL((forward<S::NT, true, true>), dim3((unsigned)((pp.nwaves + 3) / 4)), dim3(256), 0, st, A, E,
+                       (const float *)(ws + pp.o_prefix), (const double *)(ws + pp.o_llpre), nullptr, log_alpha,
+                       (const int *)(ws + pp.o_elig), pp.p, eps, pp.nwaves, (const float *)(ws + pp.o_suffix), phi);
     scan_select<S>(pp, phi, ws, st);
 }
 
@@ -192,8 +173,8 @@ static void scan_backward(const float *A, const float *E, const MidPlan &pp, flo
     (void)hipMemsetD32Async((hipDeviceptr_t)upi, __builtin_bit_cast(int, 1.0f / (float)p.q), (size_t)p.k * p.q, st);
     scan_reduce_scan<S>(A, upi, E, pp, eps, ws, st);
     float *phi = (float *)(ws + pp.o_phi);
-    S::template backward<3, true>(dim3((unsigned)((pp.nwaves + 3) / 4)), st, A, E, nullptr,
-                                  (const float *)(ws + pp.o_suffix), (const double *)(ws + pp.o_lsuf), nullptr, log_beta,
-                                  phi, (const int *)(ws + pp.o_elig), p, eps, pp.nwaves, (const float *)(ws + pp.o_prefix));
+    hipLaunchKernelGGL((backward<S::NT, 3, true>), dim3((unsigned)((pp.nwaves + 3) / 4)), dim3(256), 0, st, A, E, nullptr,
+                       (const float *)(ws + pp.o_suffix), (const double *)(ws + pp.o_lsuf), nullptr, log_beta, phi,
+                       (const int *)(ws + pp.o_elig), p, eps, pp.nwaves, (const float *)(ws + pp.o_prefix));
     scan_select<S>(pp, phi, ws, st);
 }

@@ -1,6 +1,7 @@
 #!/bin/bash
 # Register / LDS / spill usage per kernel of the engine (compiles device code only, no GPU needed).
 #   bash tools/kernel_resources.sh [regex]
+# e.g. the chunked scan for 17..64 states:  bash tools/kernel_resources.sh '^(reduce_dense|scan|forward|backward)<[24]'
 R=$(cd "$(dirname "$0")/.." && pwd)
 T=$(mktemp -d)
 cd "$T" && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -mllvm -amdgpu-mfma-vgpr-form -fno-honor-nans \
