@@ -2515,193 +2515,54 @@ __global__ __launch_bounds__(256) void k_loglik_partials(const double *__restric
 
 // ------------------------------------------------------------------ host side
 
-static int check_launch() { return hipGetLastError() == hipSuccess ? HMM_OK : HMM_ERR_LAUNCH; }
-
-// Optional per-kernel timing with HIP events on the launch stream (bench.py's roofline leg).
-struct Profile {
-    struct Span { int kernel; hipEvent_t a, b; };
-    std::vector<Span> spans;
-};
-struct Timed {   // brackets one launch when a profile is attached
-    Profile *pr; hipStream_t st; Profile::Span sp;
-    Timed(Profile *pr_, int kernel, hipStream_t st_) : pr(pr_), st(st_) {
-        if (!pr) return;
-        sp.kernel = kernel;
-        (void)hipEventCreate(&sp.a); (void)hipEventCreate(&sp.b);
-        (void)hipEventRecord(sp.a, st);
-    }
-    ~Timed() {
-        if (!pr) return;
-        (void)hipEventRecord(sp.b, st);
-        pr->spans.push_back(sp);
-    }
-};
-
-// chunk operators of every (sequence, chunk): ws + o_ops / o_exps
-static void run_reduce(const float *A, const float *E, const Plan &p, float eps, char *ws, hipStream_t st,
-                       Profile *pr, int exact_mode) {
-    float *ops = (float *)(ws + p.o_ops);
-    int *exps = (int *)(ws + p.o_exps);
-    const unsigned nb = (unsigned)((p.nchains + 3) / 4);
-    int *topo = (int *)(ws + p.o_topo);
-    const int force_dense = opt(HMM_OPT_FORCE_DENSE) == 1 ? 1 : 0;
-    hipLaunchKernelGGL(k_topo_check, dim3(p.k), dim3(64), 0, st, A, topo, p.k, p.q, force_dense, exact_mode,
-                       eps, (int *)(ws + p.o_nexact), (int *)(ws + p.o_wcnt));
-    {
-        // every (sequence, chunk) is served by exactly one of the two kernels, chosen on the
-        // device from the support of its model's A; the other kernel's waves exit at once
-        Timed t(pr, HMM_KERNEL_REDUCE, st);
-        const unsigned nbs = (unsigned)((p.nchains + 15) / 16);
-        if (p.q == TopoGene15::Q) {
-            hipLaunchKernelGGL(k_reduce_sparse<TopoGene15>, dim3(nbs), dim3(256), 0, st, A, E, ops, exps, topo, p, eps);
-            if (p.k > 1 || !HMM_RS_UNI)        // waves that straddle two models
-                hipLaunchKernelGGL((k_reduce_sparse<TopoGene15, true>), dim3(nbs), dim3(256), 0, st, A, E, ops, exps, topo, p, eps);
-        } else if (p.q == TopoGene7::Q) {
-            hipLaunchKernelGGL(k_reduce_sparse<TopoGene7>, dim3(nbs), dim3(256), 0, st, A, E, ops, exps, topo, p, eps);
-            if (p.k > 1 || !HMM_RS_UNI)
-                hipLaunchKernelGGL((k_reduce_sparse<TopoGene7, true>), dim3(nbs), dim3(256), 0, st, A, E, ops, exps, topo, p, eps);
-        }
-        // the dense kernel: every chain its own wave, unless a sparse kernel may have taken the model
-        const bool maybe_sparse = p.q == TopoGene15::Q || p.q == TopoGene7::Q;
-        const unsigned nbd = (maybe_sparse && nb > 4096u) ? 4096u : nb;
-        hipLaunchKernelGGL(k_reduce, dim3(nbd), dim3(256), 0, st, A, E, ops, exps, (const int *)topo, p, eps);
-    }
-}
-
-// chunk-level prefix / suffix vectors from the chunk operators.  pre_in .. ls_in (sequence-sharded
-// calls): the vectors entering this time slab, in place of the start distribution and of ones.
-static void run_scan(const float *pi, const Plan &p, float eps, char *ws, hipStream_t st, Profile *pr,
-                     const float *pre_in = nullptr, const double *ll_in = nullptr, const float *suf_in = nullptr,
-                     const double *ls_in = nullptr) {
-    float *ops = (float *)(ws + p.o_ops);
-    int *exps = (int *)(ws + p.o_exps);
-    int *topo = (int *)(ws + p.o_topo);
-    {
-        Timed t(pr, HMM_KERNEL_SCAN, st);
-        const bool two = p.G > 0 && opt(HMM_OPT_SCAN2) != 0;
-        if (!two) {
-            hipLaunchKernelGGL(k_scan, dim3(p.NB), dim3(128), 0, st, pi, ops, exps, (float *)(ws + p.o_prefix),
-                               (double *)(ws + p.o_llpre), (float *)(ws + p.o_suffix), (double *)(ws + p.o_lsuf),
-                               (double *)(ws + p.o_loglik), (const int *)topo, p, eps, pre_in, ll_in, suf_in, ls_in);
-        } else {
-            float *gops = (float *)(ws + p.o_gops);
-            int *gexps = (int *)(ws + p.o_gexps);
-            const long long nwv = (long long)p.NB * p.G;
-            hipLaunchKernelGGL(k_scan_compose, dim3((unsigned)((nwv + 3) / 4)), dim3(256), 0, st, (const float *)ops,
-                               (const int *)exps, gops, gexps, (const int *)topo, p);
-            Plan pg = p;                  // the same scan, over the group operators
-            pg.C = p.G;
-            hipLaunchKernelGGL(k_scan, dim3(p.NB), dim3(128), 0, st, pi, (const float *)gops, (const int *)gexps,
-                               (float *)(ws + p.o_gprefix), (double *)(ws + p.o_gllpre), (float *)(ws + p.o_gsuffix),
-                               (double *)(ws + p.o_glsuf), (double *)(ws + p.o_loglik), (const int *)topo, pg, eps,
-                               pre_in, ll_in, suf_in, ls_in);
-            hipLaunchKernelGGL(k_scan_inner, dim3((unsigned)((nwv + 3) / 4)), dim3(128), 0, st, (const float *)ops, (const int *)exps,
-                               (const float *)(ws + p.o_gprefix), (const double *)(ws + p.o_gllpre),
-                               (const float *)(ws + p.o_gsuffix), (const double *)(ws + p.o_glsuf),
-                               (float *)(ws + p.o_prefix), (double *)(ws + p.o_llpre), (float *)(ws + p.o_suffix),
-                               (double *)(ws + p.o_lsuf), (const int *)topo, p, eps);
-        }
-    }
-}
-
-static int run_reduce_scan(const float *A, const float *pi, const float *E, const Plan &p, float eps,
-                           char *ws, hipStream_t st, Profile *pr = nullptr) {
-    run_reduce(A, E, p, eps, ws, st, pr, opt(HMM_OPT_EXACT));
-    run_scan(pi, p, eps, ws, st, pr);
-    return check_launch();
-}
-
-static Routing routing(const Plan &p, char *ws, bool, bool count) {
-    Routing rt;
-    rt.topo = (const int *)(ws + p.o_topo);
-    rt.exact_mode = opt(HMM_OPT_EXACT);
-    rt.nexact = count ? (int *)(ws + p.o_nexact) : nullptr;
-    rt.flags = nullptr;
-    return rt;
-}
-
-static int win_margin(const Plan &p) { return (WIN_MARGIN_STEPS + p.T - 1) / p.T; }
-
-static long long apply_waves(const Plan &p) {
-    const long long per_model = (long long)p.b * p.C;
-    return (long long)p.k * ((per_model + p.cpw - 1) / p.cpw);
-}
-
-// ---- batch groups for the posterior pipeline.  The sparse reduce kernel is VALU-bound and the
-// apply kernels are HBM-bound (measured: removing all arithmetic from them changes their time by
-// 3 %), so a large batch is cut into groups and reduce(g+1) runs on a second stream underneath
-// forward/backward(g).  Groups are independent sub-problems (sequences never interact); all use
-// the chunk length of the whole problem, so results do not depend on the grouping.
-#ifndef HMM_MAX_GROUPS
-#define HMM_MAX_GROUPS 16
-#endif
-#define MAX_GROUPS HMM_MAX_GROUPS
-#ifndef HMM_GROUP_MIN_SEQ
-#define HMM_GROUP_MIN_SEQ 64
-#endif
-struct Groups {
-    int n;                      // number of groups (1 = no pipelining)
-    int T;                      // chunk length shared by all groups
-    int b0[MAX_GROUPS + 1];     // group g owns sequences [b0[g], b0[g+1])
-    Plan plan[MAX_GROUPS];
-    size_t off[MAX_GROUPS];     // workspace offset of group g
-    size_t total;
-};
-
-static int plan_groups(int k, int b, int L, int q, Groups *G) {
-    Plan whole;
-    int rc = make_plan(HMM_OP_POSTERIOR, k, b, L, q, &whole);
-    if (rc) return rc;
-    int n = 1;
-    if (k == 1 && (long long)b * L >= (1ll << 24)) {
-        // Measured on MI355X (b=1024, L=1e5): the kernels of the two streams do overlap, but each
-        // slows down by as much as it overlaps (7.67 ms with 1 group, 7.62 / 7.80 / 7.92 with
-        // 2 / 4 / 8), so the pipeline is off by default and kept as an opt-in knob.
-        n = opt(HMM_OPT_GROUPS);
-        if (n > b / HMM_GROUP_MIN_SEQ) n = b / HMM_GROUP_MIN_SEQ;
-        if (n > MAX_GROUPS) n = MAX_GROUPS;
-        if (n < 1) n = 1;
-    }
-    G->n = n;
-    G->T = whole.T;
-    size_t off = 0;
-    for (int g = 0; g < n; ++g) {
-        G->b0[g] = (int)((long long)b * g / n);
-        G->b0[g + 1] = (int)((long long)b * (g + 1) / n);
-        if ((rc = make_plan(HMM_OP_POSTERIOR, k, G->b0[g + 1] - G->b0[g], L, q, &G->plan[g], whole.T))) return rc;
-        G->off[g] = off;
-        off += G->plan[g].total;
-    }
-    G->total = off;
-    return HMM_OK;
-}
-
-// two helper streams per device, created on first use and kept for the life of the process
-static hipStream_t *helper_streams() {
-    static hipStream_t pool[64][2];
-    static bool ready[64];
-    static std::mutex mu;                      // entry points may be called from several host threads
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-    std::lock_guard<std::mutex> lock(mu);
-    if (!ready[dev]) {
-        if (hipStreamCreateWithFlags(&pool[dev][0], hipStreamNonBlocking) != hipSuccess) return nullptr;
-        if (hipStreamCreateWithFlags(&pool[dev][1], hipStreamNonBlocking) != hipSuccess) return nullptr;
-        ready[dev] = true;
-    }
-    return pool[dev];
-}
-
-static int check_ws(size_t total, void *ws, size_t bytes) {
-    if (!ws) return HMM_ERR_NULL_POINTER;
-    if (bytes < total || ((uintptr_t)ws & 255)) return HMM_ERR_WORKSPACE;
-    return HMM_OK;
-}
+#include "hmm_scan16.inc"
 
 #include "hmm_largeq.inc"
 #include "hmm_midq.inc"
 #include "hmm_scan_rows.inc"
 #include "hmm_scan_mid.inc"
+
+// ---- the router: which path serves (op, k, b, L, q), the plans that path needs, the workspace it takes.  Every entry
+// point below and hmm_workspace_bytes go through it, so they cannot disagree.
+enum Path {
+    PATH_S16,      // up to 16 states: the chunked scan of hmm_scan16.inc
+    PATH_MID32,    // 17..32 states: the chunked scan of hmm_scan_mid.inc on 32-lane rows, one wave per sequence for the rest
+    PATH_MID64,    // few long sequences of 33..64 states: the same on 64-lane rows
+    PATH_MQ,       // up to 64 states otherwise: one wave per sequence (hmm_midq.inc)
+    PATH_LQ        // above: one GEMM per step (hmm_largeq.inc)
+};
+struct Route {
+    Path path;
+    Plan p;            // S16, every operation but the posterior
+    Groups G;          // S16, the posterior: one plan per batch group
+    LqPlan lp;         // the other paths; MID*: the chunked scan's region (mp) follows it in the workspace
+    MidPlan mp;
+    size_t total;      // workspace bytes
+};
+
+static int make_route(int op, int k, int b, int L, int q, Route *r) {
+    const int W = op != HMM_OP_VITERBI ? mid_width(k, b, L, q) : 0;
+    r->path = q <= QP ? PATH_S16 : W == Q32 ? PATH_MID32 : W == Q64 ? PATH_MID64 : q <= MQ_MAX ? PATH_MQ : PATH_LQ;
+    r->lp = LqPlan{};
+    int rc;
+    if (r->path == PATH_S16) {
+        if (op == HMM_OP_POSTERIOR) {
+            if ((rc = plan_groups(k, b, L, q, &r->G))) return rc;
+            r->total = r->G.total;
+        } else {
+            if ((rc = make_plan(op, k, b, L, q, &r->p))) return rc;
+            r->total = r->p.total;
+        }
+        return HMM_OK;
+    }
+    if ((rc = make_lqplan(k, b, L, q, &r->lp))) return rc;
+    r->total = r->lp.total;
+    if (W) {
+        if ((rc = make_midplan(op, k, b, L, q, W, &r->mp))) return rc;
+        r->total += r->mp.total;
+    }
+    return HMM_OK;
+}
 
 extern "C" {
 
@@ -2747,391 +2608,112 @@ int hmm_chunk_len(int k, int b, int L, int q) {
 }
 
 size_t hmm_workspace_bytes(int op, int k, int b, int L, int q) {
-    if (q > QP) {
-        LqPlan lp;
-        if (make_lqplan(k, b, L, q, &lp)) return 0;
-        const int W = op != HMM_OP_VITERBI ? mid_width(k, b, L, q) : 0;
-        if (W) {                                                               // + the chunked scan's region
-            MidPlan mp;
-            if (make_midplan(op, k, b, L, q, W, &mp)) return 0;
-            return lp.total + mp.total;
-        }
-        return lp.total;
-    }
-    if (op == HMM_OP_POSTERIOR) {
-        Groups G;
-        if (plan_groups(k, b, L, q, &G)) return 0;
-        return G.total;
-    }
-    Plan p;
-    if (make_plan(op, k, b, L, q, &p)) return 0;
-    return p.total;
+    Route r;
+    return make_route(op, k, b, L, q, &r) ? 0 : r.total;
 }
 
 int hmm_forward(const float *A, const float *pi, const float *E, int k, int b, int L, int q, float eps,
                 float *log_alpha, double *loglik, void *workspace, size_t workspace_bytes, void *stream) {
-    if (q > QP) {
-        LqPlan lp;
-        int rc = make_lqplan(k, b, L, q, &lp);
-        if (rc) return rc;
-        if (!A || !pi || !E || !loglik) return HMM_ERR_NULL_POINTER;
-        if ((rc = check_ws(lp.total, workspace, workspace_bytes))) return rc;
-        char *ws = (char *)workspace;
-        hipStream_t st = (hipStream_t)stream;
-        double *ll = (double *)(ws + lp.o_ll);
-        if (const int W = mid_width(k, b, L, q)) {
-            // 17..32 states, or few long sequences of 33..64: chunk operators + chunk scan (+ the forward apply kernel
-            // for log alpha) for the models the chunked path serves (decided on the device), one wave per sequence
-            // for the others
-            MidPlan mp;
-            if ((rc = make_midplan(log_alpha ? HMM_OP_FORWARD : HMM_OP_LOGLIK, k, b, L, q, W, &mp))) return rc;
-            if (workspace_bytes < lp.total + mp.total) return HMM_ERR_WORKSPACE;
-            char *wm = ws + lp.total;
-            if (log_alpha && W == Q32) scan_forward<Scan32>(A, pi, E, mp, eps, log_alpha, wm, st);
-            else if (log_alpha) scan_forward<Scan64>(A, pi, E, mp, eps, log_alpha, wm, st);
-            else if (W == Q32) scan_loglik<Scan32>(A, pi, E, mp, eps, wm, st);
-            else scan_loglik<Scan64>(A, pi, E, mp, eps, wm, st);
-            ll = (double *)(wm + mp.o_loglik);
-            mq_forward(A, pi, E, k, b, L, q, eps, nullptr, log_alpha, ll, st, (const int *)(wm + mp.o_need),
-                       (MqSp *)(ws + lp.o_sp));
-        } else if (q <= MQ_MAX) {                            // one wave per sequence, no launches per step
-            mq_forward(A, pi, E, k, b, L, q, eps, nullptr, log_alpha, ll, st, nullptr, (MqSp *)(ws + lp.o_sp));
-        } else {
-            lq_forward(A, pi, E, lp, eps, ws, log_alpha, st);
-        }
-        hipLaunchKernelGGL(k_copy_loglik, dim3((lp.NB + 255) / 256), dim3(256), 0, st, (const double *)ll, loglik, lp.NB);
-        return check_launch();
-    }
-    Plan p;
-    int rc = make_plan(log_alpha ? HMM_OP_FORWARD : HMM_OP_LOGLIK, k, b, L, q, &p);
+    Route r;
+    int rc = make_route(log_alpha ? HMM_OP_FORWARD : HMM_OP_LOGLIK, k, b, L, q, &r);
     if (rc) return rc;
     if (!A || !pi || !E || !loglik) return HMM_ERR_NULL_POINTER;
-    if ((rc = check_ws(p.total, workspace, workspace_bytes))) return rc;
+    if ((rc = check_ws(r.total, workspace, workspace_bytes))) return rc;
     char *ws = (char *)workspace;
     hipStream_t st = (hipStream_t)stream;
-    Plan px;
-    if ((rc = make_xplan(p, &px))) return rc;
-    if ((rc = run_reduce_scan(A, pi, E, p, eps, ws, st))) return rc;
-    double *wll = (double *)(ws + p.o_loglik);
-    // Routing.  Per model: k_topo_check.  Per sequence: there is no backward pass here, so the scan plan's forward
-    // kernel itself carries the clamp-born part of alpha_hat along and weighs it with the chunk scan's suffix
-    // vectors (forward_body's CERT); sequences whose sum is above EXACT_DELTA are walked whole by the serial plan.
-    // The log-likelihood alone comes out of the chunk scan, so for it the kernel runs for the verdict only.
-    const Routing rt = routing(p, ws, false, false);
-    Routing rtx = routing(p, ws, false, false);
-    const long long nw = apply_waves(p), nwx = apply_waves(px);
-    const dim3 grid((unsigned)((nw + 3) / 4)), gx((unsigned)((nwx + 3) / 4));
-    float *psi = (float *)(ws + p.o_phi);
-    int *flags = (int *)(ws + p.o_flags);
-    const float *pre = (const float *)(ws + p.o_prefix), *suf = (const float *)(ws + p.o_suffix);
-    const double *llp = (const double *)(ws + p.o_llpre);
-    const bool cert = rt.exact_mode == HMM_EXACT_AUTO;
-    if (log_alpha) {
-        if (cert)
-            hipLaunchKernelGGL((k_forward<false, true, false, true>), grid, dim3(256), 0, st, A, pi, E, pre, llp, (float *)nullptr,
-                               log_alpha, wll, (float *)(ws + p.o_xend), rt, p, eps, nw, psi, suf);
-        else
-            hipLaunchKernelGGL((k_forward<false, true, false>), grid, dim3(256), 0, st, A, pi, E, pre, llp, (float *)nullptr,
-                               log_alpha, wll, (float *)nullptr, rt, p, eps, nw);
-    } else if (cert) {
-        hipLaunchKernelGGL((k_forward<false, false, false, true>), grid, dim3(256), 0, st, A, pi, E, pre, llp, (float *)nullptr,
-                           (float *)nullptr, wll, (float *)(ws + p.o_xend), rt, p, eps, nw, psi, suf);
+    char *wm = ws + r.lp.total;                              // MID*: the chunked scan's region
+    double *ll = ws_at<double>(ws, r.lp.o_ll);
+    const int *need = nullptr;
+    MqSp *sp = ws_at<MqSp>(ws, r.lp.o_sp);
+    switch (r.path) {
+        case PATH_S16: return s16_forward(A, pi, E, r.p, eps, log_alpha, loglik, ws, st);
+        case PATH_MID32:
+        case PATH_MID64:
+            // chunk operators + chunk scan (+ the forward apply kernel for log alpha) for the models the chunked path
+            // serves (decided on the device), one wave per sequence for the others
+            if (log_alpha)
+                (r.path == PATH_MID32 ? scan_forward<Scan32> : scan_forward<Scan64>)(A, pi, E, r.mp, eps, log_alpha, wm, st);
+            else
+                (r.path == PATH_MID32 ? scan_loglik<Scan32> : scan_loglik<Scan64>)(A, pi, E, r.mp, eps, wm, st);
+            ll = WsMid(r.mp, wm).loglik;
+            need = WsMid(r.mp, wm).need;
+            [[fallthrough]];
+        case PATH_MQ:                                        // one wave per sequence, no launches per step
+            mq_forward(A, pi, E, k, b, L, q, eps, nullptr, log_alpha, ll, st, need, sp);
+            break;
+        case PATH_LQ: lq_forward(A, pi, E, r.lp, eps, ws, log_alpha, st); break;
     }
-    // Routed sequences: windows, forward half only — for the log-likelihood alone, and for log alpha, whose rows
-    // after a window then move with the window's log-likelihood (k_window_shift_loga); what the windows cannot
-    // settle is walked whole
-    hipLaunchKernelGGL(k_exact_select, dim3(p.NB), dim3(64), 0, st, rt.topo, psi, p, rt.exact_mode,
-                       win_margin(p), flags, (int *)(ws + p.o_nexact), (int *)(ws + p.o_wtab),
-                       (int *)(ws + p.o_wlist), (int *)(ws + p.o_wcnt), (const int *)(ws + p.o_exps));
-    if (log_alpha) {
-        const unsigned gw = (unsigned)((p.NB < 4096 ? p.NB : 4096) + 3) / 4;
-        double *wsh = (double *)(ws + p.o_wshift);
-        hipLaunchKernelGGL((k_window_posterior<5>), dim3(gw), dim3(256), 0, st, A, E, pre, llp, suf,
-                           (const float *)(ws + p.o_xend), (const float *)nullptr, (float *)nullptr, wll, log_alpha,
-                           (int *)(ws + p.o_wtab), (const int *)(ws + p.o_wlist), (int *)(ws + p.o_wcnt), flags,
-                           (double *)(ws + p.o_dfix), p, eps, win_margin(p), wsh);
-        hipLaunchKernelGGL(k_window_shift_loga, dim3(64, 64), dim3(256), 0, st, log_alpha, (const int *)(ws + p.o_wtab),
-                           (const int *)(ws + p.o_wlist), (const int *)(ws + p.o_wcnt), (const int *)flags,
-                           (const double *)wsh, p);
-    } else {
-        const unsigned gw = (unsigned)((p.NB < 4096 ? p.NB : 4096) + 3) / 4;
-        hipLaunchKernelGGL((k_window_posterior<4>), dim3(gw), dim3(256), 0, st, A, E, pre, llp, suf,
-                           (const float *)(ws + p.o_xend), (const float *)nullptr, (float *)nullptr, wll, (float *)nullptr,
-                           (int *)(ws + p.o_wtab), (const int *)(ws + p.o_wlist), (int *)(ws + p.o_wcnt), flags,
-                           (double *)(ws + p.o_dfix), p, eps, win_margin(p));
-    }
-    rtx.flags = flags;
-    if (log_alpha)
-        hipLaunchKernelGGL((k_forward<false, true, true>), gx, dim3(256), 0, st, A, pi, E, (const float *)nullptr,
-                           (const double *)nullptr, (float *)nullptr, log_alpha, wll, (float *)nullptr, rtx, px, eps, nwx);
-    else
-        hipLaunchKernelGGL((k_forward<false, false, true>), gx, dim3(256), 0, st, A, pi, E, (const float *)nullptr,
-                           (const double *)nullptr, (float *)nullptr, (float *)nullptr, wll, (float *)nullptr, rtx, px,
-                           eps, nwx);
-    hipLaunchKernelGGL(k_copy_loglik, dim3((p.NB + 255) / 256), dim3(256), 0, st, (const double *)wll, loglik, p.NB);
+    launch(k_copy_loglik, dim3((r.lp.NB + 255) / 256), dim3(256), 0, st, ll, loglik, r.lp.NB);
     return check_launch();
 }
 
 int hmm_backward(const float *A, const float *E, int k, int b, int L, int q, float eps, float *log_beta,
                  void *workspace, size_t workspace_bytes, void *stream) {
-    if (q > QP) {
-        LqPlan lp;
-        int rc = make_lqplan(k, b, L, q, &lp);
-        if (rc) return rc;
-        if (!A || !E || !log_beta) return HMM_ERR_NULL_POINTER;
-        if ((rc = check_ws(lp.total, workspace, workspace_bytes))) return rc;
-        if (const int W = mid_width(k, b, L, q)) {
-            MidPlan mp;
-            if ((rc = make_midplan(HMM_OP_BACKWARD, k, b, L, q, W, &mp))) return rc;
-            if (workspace_bytes < lp.total + mp.total) return HMM_ERR_WORKSPACE;
-            char *wm = (char *)workspace + lp.total;
-            if (W == Q32) scan_backward<Scan32>(A, E, mp, eps, log_beta, wm, (hipStream_t)stream);
-            else scan_backward<Scan64>(A, E, mp, eps, log_beta, wm, (hipStream_t)stream);
-            mq_backward(A, E, k, b, L, q, eps, log_beta, nullptr, 3, (hipStream_t)stream, (const int *)(wm + mp.o_need),
-                        (MqSp *)((char *)workspace + lp.o_sp));
-        } else if (q <= MQ_MAX)
-            mq_backward(A, E, k, b, L, q, eps, log_beta, nullptr, 3, (hipStream_t)stream, nullptr,
-                        (MqSp *)((char *)workspace + lp.o_sp));
-        else
-            lq_backward(A, E, lp, eps, (char *)workspace, log_beta, (hipStream_t)stream);
-        return check_launch();
-    }
-    Plan p;
-    int rc = make_plan(HMM_OP_BACKWARD, k, b, L, q, &p);
+    Route r;
+    int rc = make_route(HMM_OP_BACKWARD, k, b, L, q, &r);
     if (rc) return rc;
     if (!A || !E || !log_beta) return HMM_ERR_NULL_POINTER;
-    if ((rc = check_ws(p.total, workspace, workspace_bytes))) return rc;
+    if ((rc = check_ws(r.total, workspace, workspace_bytes))) return rc;
     char *ws = (char *)workspace;
     hipStream_t st = (hipStream_t)stream;
-    // hmm_backward has no start distribution: the chunk scan's forward half (whose vectors weigh the certificate,
-    // backward_body's CERT3) starts from the uniform one
-    Plan px;
-    if ((rc = make_xplan(p, &px))) return rc;
-    float *upi = (float *)(ws + p.o_upi);
-    {
-        const float u = 1.0f / (float)q;
-        if (hipMemsetD32Async((hipDeviceptr_t)upi, __builtin_bit_cast(int, u), (size_t)k * q, st) != hipSuccess)
-            return HMM_ERR_LAUNCH;
+    char *wm = ws + r.lp.total;                              // MID*: the chunked scan's region
+    const int *need = nullptr;
+    MqSp *sp = ws_at<MqSp>(ws, r.lp.o_sp);
+    switch (r.path) {
+        case PATH_S16: return s16_backward(A, E, r.p, eps, log_beta, ws, st);
+        case PATH_MID32:
+        case PATH_MID64:
+            (r.path == PATH_MID32 ? scan_backward<Scan32> : scan_backward<Scan64>)(A, E, r.mp, eps, log_beta, wm, st);
+            need = WsMid(r.mp, wm).need;
+            [[fallthrough]];
+        case PATH_MQ: mq_backward(A, E, k, b, L, q, eps, log_beta, nullptr, 3, st, need, sp); break;
+        case PATH_LQ: lq_backward(A, E, r.lp, eps, ws, log_beta, st); break;
     }
-    if ((rc = run_reduce_scan(A, upi, E, p, eps, ws, st))) return rc;
-    const Routing rt = routing(p, ws, false, false);
-    Routing rtx = routing(p, ws, false, false);
-    const long long nw = apply_waves(p), nwx = apply_waves(px);
-    float *psi = (float *)(ws + p.o_phi);
-    int *flags = (int *)(ws + p.o_flags);
-    if (rt.exact_mode == HMM_EXACT_AUTO)
-        hipLaunchKernelGGL((k_backward<3, false, true>), dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, st, A, E,
-                           (const float *)nullptr, (const float *)(ws + p.o_suffix), (const double *)(ws + p.o_lsuf),
-                           (const double *)(ws + p.o_loglik), log_beta, psi, (float *)(ws + p.o_rstart), rt, p, eps, nw,
-                           (const float *)(ws + p.o_prefix));
-    else
-        hipLaunchKernelGGL((k_backward<3, false>), dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, st, A, E,
-                           (const float *)nullptr, (const float *)(ws + p.o_suffix), (const double *)(ws + p.o_lsuf),
-                           (const double *)(ws + p.o_loglik), log_beta, (float *)nullptr, (float *)nullptr, rt, p, eps, nw);
-    hipLaunchKernelGGL(k_exact_select, dim3(p.NB), dim3(64), 0, st, rt.topo, psi, p, rt.exact_mode,
-                       win_margin(p), flags, (int *)(ws + p.o_nexact), (int *)(ws + p.o_wtab), (int *)(ws + p.o_wlist),
-                       (int *)(ws + p.o_wcnt), (const int *)(ws + p.o_exps));
-    if (rt.exact_mode == HMM_EXACT_AUTO) {                  // routed sequences: windows (k_window_logbeta), the rest whole
-        const unsigned gw = (unsigned)((p.NB < 4096 ? p.NB : 4096) + 3) / 4;
-        double *wsh = (double *)(ws + p.o_wshift);
-        hipLaunchKernelGGL(k_window_logbeta, dim3(gw), dim3(256), 0, st, A, E, (const float *)(ws + p.o_prefix),
-                           (const float *)(ws + p.o_suffix), (const double *)(ws + p.o_lsuf),
-                           (const float *)(ws + p.o_rstart), log_beta, (int *)(ws + p.o_wtab),
-                           (const int *)(ws + p.o_wlist), (int *)(ws + p.o_wcnt), flags, wsh, p, eps, win_margin(p));
-        hipLaunchKernelGGL(k_window_shift_logb, dim3(64, 64), dim3(256), 0, st, log_beta, (const int *)(ws + p.o_wtab),
-                           (const int *)(ws + p.o_wlist), (const int *)(ws + p.o_wcnt), (const int *)flags,
-                           (const double *)wsh, p);
-    }
-    rtx.flags = flags;
-    hipLaunchKernelGGL((k_backward<3, true>), dim3((unsigned)((nwx + 3) / 4)), dim3(256), 0, st, A, E,
-                       (const float *)nullptr, (const float *)nullptr, (const double *)nullptr,
-                       (const double *)(ws + p.o_loglik), log_beta, (float *)nullptr, (float *)nullptr, rtx, px, eps, nwx);
     return check_launch();
-}
-
-static int launch_apply(const float *A, const float *pi, const float *E, const Plan &p, float eps, int mode, char *ws,
-                        float *out, double *loglik, hipStream_t st, Profile *pr, bool allow_exact = true) {
-    Plan px;
-    int rc = make_xplan(p, &px);
-    if (rc) return rc;
-    const long long nw = apply_waves(p), nwx = apply_waves(px);
-    const dim3 grid((unsigned)((nw + 3) / 4)), gx((unsigned)((nwx + 3) / 4));
-    float *ckpt = (float *)(ws + p.o_ckpt);
-    float *psi = (float *)(ws + p.o_phi);
-    float *xend = (float *)(ws + p.o_xend), *rstart = (float *)(ws + p.o_rstart);
-    double *ll = (double *)(ws + p.o_loglik);
-    const Routing rt = routing(p, ws, false, false);
-    // The scan plan's forward / backward pair agrees on its own block length: checkpoints every HMM_POST_BLOCK
-    // steps for the probability output (half the checkpoint traffic: k_forward 1.38 -> 1.24 ms in a one-process A/B;
-    // 16 recomputed alpha_hat rows fit k_backward<0>'s register file at two waves per SIMD, the log modes' do not)
-    const bool wide = HMM_POST_BLOCK != SUB && mode == HMM_POST_PROB && p.T % HMM_POST_BLOCK == 0;
-    Plan pb = p;
-    if (wide) pb.nsub = p.T / HMM_POST_BLOCK;
-    {
-        Timed t(pr, HMM_KERNEL_FORWARD, st);
-        if (wide)
-            hipLaunchKernelGGL((k_forward<true, false, false, false, HMM_POST_BLOCK>), grid, dim3(256), 0, st, A, pi, E,
-                               (const float *)(ws + p.o_prefix), (const double *)(ws + p.o_llpre), ckpt, (float *)nullptr,
-                               ll, xend, rt, pb, eps, nw);
-        else
-            hipLaunchKernelGGL((k_forward<true, false, false>), grid, dim3(256), 0, st, A, pi, E,
-                               (const float *)(ws + p.o_prefix), (const double *)(ws + p.o_llpre), ckpt, (float *)nullptr,
-                               ll, xend, rt, p, eps, nw);
-    }
-    const float *sx = (const float *)(ws + p.o_suffix);
-    const double *ls = (const double *)(ws + p.o_lsuf);
-    {
-        Timed t(pr, HMM_KERNEL_BACKWARD, st);
-        if (mode == HMM_POST_PROB && wide)
-            hipLaunchKernelGGL((k_backward<0, false, false, HMM_POST_BLOCK>), grid, dim3(256), 0, st, A, E, (const float *)ckpt,
-                               sx, ls, (const double *)ll, out, psi, rstart, rt, pb, eps, nw);
-        else if (mode == HMM_POST_PROB)
-            hipLaunchKernelGGL((k_backward<0, false>), grid, dim3(256), 0, st, A, E, (const float *)ckpt, sx, ls,
-                               (const double *)ll, out, psi, rstart, rt, p, eps, nw);
-        else if (mode == HMM_POST_LOG)
-            hipLaunchKernelGGL((k_backward<1, false>), grid, dim3(256), 0, st, A, E, (const float *)ckpt, sx, ls,
-                               (const double *)ll, out, psi, rstart, rt, p, eps, nw);
-        else
-            hipLaunchKernelGGL((k_backward<2, false>), grid, dim3(256), 0, st, A, E, (const float *)ckpt, sx, ls,
-                               (const double *)ll, out, psi, rstart, rt, p, eps, nw);
-    }
-    if (allow_exact) {
-        // the serial kernels: per model as k_topo_check decided, per sequence from the clamp-born mass the
-        // backward kernel just summed; their waves exit at once when nothing is routed
-        Timed t(pr, HMM_KERNEL_EXACT, st);
-        Routing rtx = routing(p, ws, true, false);
-        int *flags = (int *)(ws + p.o_flags);
-        int *wtab = (int *)(ws + p.o_wtab), *wlist = (int *)(ws + p.o_wlist), *wcnt = (int *)(ws + p.o_wcnt);
-        double *dfix = (double *)(ws + p.o_dfix);
-        hipLaunchKernelGGL(k_exact_select, dim3(p.NB), dim3(64), 0, st, rtx.topo, psi, p, rtx.exact_mode,
-                           win_margin(p), flags, (int *)(ws + p.o_nexact), wtab, wlist, wcnt, (const int *)(ws + p.o_exps));
-        rtx.flags = flags;
-        const unsigned gw = (unsigned)((p.NB < 4096 ? p.NB : 4096) + 3) / 4;
-        const float *pre = (const float *)(ws + p.o_prefix);
-        const double *llp = (const double *)(ws + p.o_llpre);
-        if (mode == HMM_POST_PROB) {
-            hipLaunchKernelGGL((k_window_posterior<0>), dim3(gw), dim3(256), 0, st, A, E, pre, llp, sx, (const float *)xend,
-                               (const float *)rstart, ckpt, ll, out, wtab, (const int *)wlist, wcnt, flags, dfix, p, eps, win_margin(p));
-            hipLaunchKernelGGL((k_exact_posterior<0>), gx, dim3(256), 0, st, A, pi, E, ckpt, ll, out, rtx, px, eps, nwx);
-        } else if (mode == HMM_POST_LOG) {
-            hipLaunchKernelGGL((k_window_posterior<1>), dim3(gw), dim3(256), 0, st, A, E, pre, llp, sx, (const float *)xend,
-                               (const float *)rstart, ckpt, ll, out, wtab, (const int *)wlist, wcnt, flags, dfix, p, eps, win_margin(p));
-            hipLaunchKernelGGL((k_exact_posterior<1>), gx, dim3(256), 0, st, A, pi, E, ckpt, ll, out, rtx, px, eps, nwx);
-        } else {
-            hipLaunchKernelGGL((k_window_posterior<2>), dim3(gw), dim3(256), 0, st, A, E, pre, llp, sx, (const float *)xend,
-                               (const float *)rstart, ckpt, ll, out, wtab, (const int *)wlist, wcnt, flags, dfix, p, eps, win_margin(p));
-            hipLaunchKernelGGL(k_window_fixll, dim3(64, 64), dim3(256), 0, st, out, (const int *)wlist, (const int *)wcnt,
-                               (const int *)flags, (const double *)dfix, p);
-            hipLaunchKernelGGL((k_exact_posterior<2>), gx, dim3(256), 0, st, A, pi, E, ckpt, ll, out, rtx, px, eps, nwx);
-        }
-    }
-    if (loglik)
-        hipLaunchKernelGGL(k_copy_loglik, dim3((p.NB + 255) / 256), dim3(256), 0, st, (const double *)ll, loglik, p.NB);
-    return HMM_OK;
 }
 
 static int posterior_impl(const float *A, const float *pi, const float *E, int k, int b, int L, int q, float eps,
                           int mode, float *out, double *loglik, void *workspace, size_t workspace_bytes,
                           void *stream, Profile *pr) {
-    if (q > QP) {
-        LqPlan lp;
-        int rc = make_lqplan(k, b, L, q, &lp);
-        if (rc) return rc;
-        if (!A || !pi || !E || !out) return HMM_ERR_NULL_POINTER;
-        if (mode < HMM_POST_PROB || mode > HMM_POST_LOG_NO_LL) return HMM_ERR_BAD_ARGUMENT;
-        if ((rc = check_ws(lp.total, workspace, workspace_bytes))) return rc;
-        char *ws = (char *)workspace;
-        hipStream_t st = (hipStream_t)stream;
-        if (const int W = mid_width(k, b, L, q)) {
-            // 17..32 states, or few long sequences of 33..64: the chunked scan for the models it serves, the serial
-            // kernels for the rest and for the sequences the certificate flags (all decided on the device)
-            MidPlan mp;
-            if ((rc = make_midplan(HMM_OP_POSTERIOR, k, b, L, q, W, &mp))) return rc;
-            if (workspace_bytes < lp.total + mp.total) return HMM_ERR_WORKSPACE;
-            char *wm = ws + lp.total;
-            if (W == Q32) scan_posterior<Scan32>(A, pi, E, mp, eps, mode, out, wm, st);
-            else scan_posterior<Scan64>(A, pi, E, mp, eps, mode, out, wm, st);
-            const int *need = (const int *)(wm + mp.o_need);
-            double *ll = (double *)(wm + mp.o_loglik);
-            if (mode != HMM_POST_LOG_NO_LL && L >= 2) {
-                mq_posterior2(A, pi, E, k, b, L, q, eps, out, ll, mode, st, need, (MqSp *)(ws + lp.o_sp));
-            } else {
-                mq_forward(A, pi, E, k, b, L, q, eps, out, nullptr, ll, st, need, (MqSp *)(ws + lp.o_sp));
-                mq_backward(A, E, k, b, L, q, eps, out, (const double *)ll, mode, st, need, (MqSp *)(ws + lp.o_sp));
-            }
-            if (loglik)
-                hipLaunchKernelGGL(k_copy_loglik, dim3((lp.NB + 255) / 256), dim3(256), 0, st, (const double *)ll, loglik,
-                                   lp.NB);
-            return check_launch();
-        }
-        if (q <= MQ_MAX && mode != HMM_POST_LOG_NO_LL && L >= 2) {
-            // forward and backward waves side by side, meeting in the middle
-            mq_posterior2(A, pi, E, k, b, L, q, eps, out, (double *)(ws + lp.o_ll), mode, st, nullptr, (MqSp *)(ws + lp.o_sp));
-        } else if (q <= MQ_MAX) {
-            mq_forward(A, pi, E, k, b, L, q, eps, out, nullptr, (double *)(ws + lp.o_ll), st, nullptr, (MqSp *)(ws + lp.o_sp));   // alpha_hat parked in `out`
-            mq_backward(A, E, k, b, L, q, eps, out, (const double *)(ws + lp.o_ll), mode, st, nullptr, (MqSp *)(ws + lp.o_sp));
-        } else {
-            hipStream_t *hs = helper_streams();               // the two recursions side by side (lq_posterior)
-            lq_posterior(A, pi, E, lp, eps, ws, out, mode, st, hs ? hs[0] : nullptr);
-        }
-        if (loglik)
-            hipLaunchKernelGGL(k_copy_loglik, dim3((lp.NB + 255) / 256), dim3(256), 0, st,
-                               (const double *)(ws + lp.o_ll), loglik, lp.NB);
-        return check_launch();
-    }
-    Groups G;
-    int rc = plan_groups(k, b, L, q, &G);
+    Route r;
+    int rc = make_route(HMM_OP_POSTERIOR, k, b, L, q, &r);
     if (rc) return rc;
     if (!A || !pi || !E || !out) return HMM_ERR_NULL_POINTER;
     if (mode < HMM_POST_PROB || mode > HMM_POST_LOG_NO_LL) return HMM_ERR_BAD_ARGUMENT;
-    if ((rc = check_ws(G.total, workspace, workspace_bytes))) return rc;
+    if ((rc = check_ws(r.total, workspace, workspace_bytes))) return rc;
     char *ws = (char *)workspace;
     hipStream_t st = (hipStream_t)stream;
-#ifdef HMM_GROUPS_SERIAL
-    hipStream_t *hs = nullptr;
-#else
-    hipStream_t *hs = G.n > 1 ? helper_streams() : nullptr;
-#endif
-    if (G.n == 1 || !hs) {
-        // single group (or no helper streams available): everything in order on the caller's stream
-        for (int g = 0; g < G.n; ++g) {
-            const Plan &p = G.plan[g];
-            const size_t row = (size_t)G.b0[g] * L * q;
-            if ((rc = run_reduce_scan(A, pi, E + row, p, eps, ws + G.off[g], st, pr))) return rc;
-            if ((rc = launch_apply(A, pi, E + row, p, eps, mode, ws + G.off[g], out + row,
-                                   loglik ? loglik + G.b0[g] : nullptr, st, pr))) return rc;
+    char *wm = ws + r.lp.total;                              // MID*: the chunked scan's region
+    double *ll = ws_at<double>(ws, r.lp.o_ll);
+    const int *need = nullptr;
+    MqSp *sp = ws_at<MqSp>(ws, r.lp.o_sp);
+    switch (r.path) {
+        case PATH_S16: return s16_posterior(A, pi, E, r.G, eps, mode, out, loglik, ws, st, pr);
+        case PATH_MID32:
+        case PATH_MID64:
+            // the chunked scan for the models it serves, the serial kernels for the rest and for the sequences the
+            // certificate flags (all decided on the device)
+            (r.path == PATH_MID32 ? scan_posterior<Scan32> : scan_posterior<Scan64>)(A, pi, E, r.mp, eps, mode, out, wm,
+                                                                                     st);
+            ll = WsMid(r.mp, wm).loglik;
+            need = WsMid(r.mp, wm).need;
+            [[fallthrough]];
+        case PATH_MQ:
+            if (mode != HMM_POST_LOG_NO_LL && L >= 2) {      // forward and backward waves side by side, meeting in the middle
+                mq_posterior2(A, pi, E, k, b, L, q, eps, out, ll, mode, st, need, sp);
+            } else {
+                mq_forward(A, pi, E, k, b, L, q, eps, out, nullptr, ll, st, need, sp);   // alpha_hat parked in `out`
+                mq_backward(A, E, k, b, L, q, eps, out, ll, mode, st, need, sp);
+            }
+            break;
+        case PATH_LQ: {
+            hipStream_t *hs = helper_streams();               // the two recursions side by side (lq_posterior)
+            lq_posterior(A, pi, E, r.lp, eps, ws, out, mode, st, hs ? hs[0] : nullptr);
+            break;
         }
-        return check_launch();
     }
-    // fork: helper stream 0 runs reduce+scan of every group back to back, helper stream 1 runs
-    // forward+backward of group g as soon as its reduce+scan is done; join back into `st`
-    hipEvent_t ev_fork, ev_red[MAX_GROUPS], ev_join[2];
-    (void)hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming);
-    (void)hipEventRecord(ev_fork, st);
-    (void)hipStreamWaitEvent(hs[0], ev_fork, 0);
-    (void)hipStreamWaitEvent(hs[1], ev_fork, 0);
-    int ngroups = 0;                            // groups whose event exists (all of them unless a launch failed)
-    for (int g = 0; g < G.n && rc == HMM_OK; ++g) {
-        const Plan &p = G.plan[g];
-        const size_t row = (size_t)G.b0[g] * L * q;
-        rc = run_reduce_scan(A, pi, E + row, p, eps, ws + G.off[g], hs[0], pr);
-        (void)hipEventCreateWithFlags(&ev_red[g], hipEventDisableTiming);
-        (void)hipEventRecord(ev_red[g], hs[0]);
-        ngroups = g + 1;
-        if (rc != HMM_OK) break;                // still join the helper streams and release the events below
-        (void)hipStreamWaitEvent(hs[1], ev_red[g], 0);
-        rc = launch_apply(A, pi, E + row, p, eps, mode, ws + G.off[g], out + row, loglik ? loglik + G.b0[g] : nullptr,
-                          hs[1], pr);
-    }
-    for (int i = 0; i < 2; ++i) {
-        (void)hipEventCreateWithFlags(&ev_join[i], hipEventDisableTiming);
-        (void)hipEventRecord(ev_join[i], hs[i]);
-        (void)hipStreamWaitEvent(st, ev_join[i], 0);
-        (void)hipEventDestroy(ev_join[i]);
-    }
-    (void)hipEventDestroy(ev_fork);
-    for (int g = 0; g < ngroups; ++g) (void)hipEventDestroy(ev_red[g]);
-    return rc != HMM_OK ? rc : check_launch();
+    if (loglik) launch(k_copy_loglik, dim3((r.lp.NB + 255) / 256), dim3(256), 0, st, ll, loglik, r.lp.NB);
+    return check_launch();
 }
 
 int hmm_posterior(const float *A, const float *pi, const float *E, int k, int b, int L, int q, float eps,
@@ -3139,42 +2721,31 @@ int hmm_posterior(const float *A, const float *pi, const float *E, int k, int b,
     return posterior_impl(A, pi, E, k, b, L, q, eps, mode, out, loglik, workspace, workspace_bytes, stream, nullptr);
 }
 
+// one device counter -> the host, added to *sum
+static int read_counter(const int *src, long long *sum) {
+    int v = 0;
+    if (hipMemcpy(&v, src, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return HMM_ERR_LAUNCH;
+    *sum += v;
+    return HMM_OK;
+}
+
 long long hmm_exact_count(int op, int k, int b, int L, int q, const void *workspace, size_t workspace_bytes) {
-    if (const int W = op != HMM_OP_VITERBI ? mid_width(k, b, L, q) : 0) {
-        // sequences of the last call that the one-wave-per-sequence kernels served
-        LqPlan lp;
-        MidPlan mp;
-        if (make_lqplan(k, b, L, q, &lp) || make_midplan(op, k, b, L, q, W, &mp)) return HMM_ERR_BAD_SHAPE;
-        if (!workspace) return HMM_ERR_NULL_POINTER;
-        if (workspace_bytes < lp.total + mp.total) return HMM_ERR_WORKSPACE;
-        int v = 0;
-        if (hipMemcpy(&v, (const char *)workspace + lp.total + mp.o_nex, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
-            return HMM_ERR_LAUNCH;
-        return v;
-    }
-    if (q > QP) return 0;                                    // the serial-in-time paths are exact throughout
+    Route r;
+    int rc = make_route(op, k, b, L, q, &r);
+    if (r.path == PATH_MQ || r.path == PATH_LQ) return 0;    // the serial-in-time paths are exact throughout
+    if (rc && r.path != PATH_S16) return rc;
     if (!workspace) return HMM_ERR_NULL_POINTER;
+    if (rc) return rc;
+    if (workspace_bytes < r.total) return HMM_ERR_WORKSPACE;
     long long total = 0;
-    auto read = [&](const Plan &p, size_t off) -> int {
-        if (workspace_bytes < off + p.total) return HMM_ERR_WORKSPACE;
-        int v = 0;
-        if (hipMemcpy(&v, (const char *)workspace + off + p.o_nexact, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
-            return HMM_ERR_LAUNCH;
-        total += v;
-        return HMM_OK;
-    };
-    int rc;
-    if (op == HMM_OP_POSTERIOR) {
-        Groups G;
-        if ((rc = plan_groups(k, b, L, q, &G))) return rc;
-        for (int g = 0; g < G.n; ++g)
-            if ((rc = read(G.plan[g], G.off[g]))) return rc;
-        return total;
-    }
-    Plan p;
-    if ((rc = make_plan(op, k, b, L, q, &p))) return rc;
-    if ((rc = read(p, 0))) return rc;
-    return total;
+    if (r.path != PATH_S16)                                  // sequences of the last call that the one-wave-per-sequence kernels served
+        rc = read_counter(WsMid(r.mp, (const char *)workspace + r.lp.total).nex, &total);
+    else if (op != HMM_OP_POSTERIOR)
+        rc = read_counter(Ws16(r.p, workspace).nexact, &total);
+    else
+        for (int g = 0; g < r.G.n && rc == HMM_OK; ++g)
+            rc = read_counter(Ws16(r.G.plan[g], (const char *)workspace + r.G.off[g]).nexact, &total);
+    return rc ? rc : total;
 }
 
 int hmm_exact_detail(int k, int b, int L, int q, const void *workspace, size_t workspace_bytes, long long *detail) {
@@ -3189,9 +2760,9 @@ int hmm_exact_detail_op(int op, int k, int b, int L, int q, const void *workspac
     auto read = [&](const Plan &p, size_t off) -> int {
         if (workspace_bytes < off + p.total) return HMM_ERR_WORKSPACE;
         int nx = 0, wc[4] = {0, 0, 0, 0};
-        const char *ws = (const char *)workspace + off;
-        if (hipMemcpy(&nx, ws + p.o_nexact, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(wc, ws + p.o_wcnt, sizeof(wc), hipMemcpyDeviceToHost) != hipSuccess)
+        const Ws16 w(p, (const char *)workspace + off);
+        if (hipMemcpy(&nx, w.nexact, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(wc, w.wcnt, sizeof(wc), hipMemcpyDeviceToHost) != hipSuccess)
             return HMM_ERR_LAUNCH;
         detail[0] += nx; detail[1] += wc[0]; detail[2] += wc[2]; detail[3] += wc[1]; detail[4] += wc[3];
         return HMM_OK;
@@ -3221,15 +2792,15 @@ int hmm_window_table(int op, int k, int b, int L, int q, const void *workspace, 
     int rc = make_plan(op, k, b, L, q, &p);
     if (rc) return rc;
     if (workspace_bytes < p.total || seq < 0 || seq >= p.NB) return HMM_ERR_WORKSPACE;
-    const char *ws = (const char *)workspace;
-    if (hipMemcpy(table, ws + p.o_wtab + (size_t)seq * WIN_STRIDE * sizeof(int), WIN_STRIDE * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+    const Ws16 w(p, workspace);
+    if (hipMemcpy(table, w.wtab + (size_t)seq * WIN_STRIDE, WIN_STRIDE * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
         return HMM_ERR_LAUNCH;
     if (shifts && (op == HMM_OP_FORWARD || op == HMM_OP_BACKWARD) &&
-        hipMemcpy(shifts, ws + p.o_wshift + (size_t)seq * WSH_STRIDE * sizeof(double), WSH_STRIDE * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+        hipMemcpy(shifts, w.wshift + (size_t)seq * WSH_STRIDE, WSH_STRIDE * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
         return HMM_ERR_LAUNCH;
     if (psi && npsi > 0) {
         const int n = npsi < p.C ? npsi : p.C;
-        if (hipMemcpy(psi, ws + p.o_phi + (size_t)seq * p.C * sizeof(float), (size_t)n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+        if (hipMemcpy(psi, w.phi + (size_t)seq * p.C, (size_t)n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
             return HMM_ERR_LAUNCH;
     }
     return p.C;
@@ -3300,7 +2871,7 @@ int hmm_loglik_allreduce(void *comm, double *partial, int k, void *stream) {
 int hmm_loglik_partials(const double *loglik, const float *weights, int k, int b, double *partial, void *stream) {
     if (k < 1 || b < 1) return HMM_ERR_BAD_SHAPE;
     if (!loglik || !partial) return HMM_ERR_NULL_POINTER;
-    hipLaunchKernelGGL(k_loglik_partials, dim3(k), dim3(256), 0, (hipStream_t)stream, loglik, weights, b, partial);
+    launch(k_loglik_partials, dim3(k), dim3(256), 0, (hipStream_t)stream, loglik, weights, b, partial);
     return check_launch();
 }
 

@@ -374,7 +374,7 @@ long long hmm_loglik_grad_serial_count(int k, int b, int L, int q, const void *w
         if (!workspace) return HMM_ERR_NULL_POINTER;
         if (workspace_bytes < gp.total) return HMM_ERR_WORKSPACE;
         int v = 0;
-        if (hipMemcpy(&v, (const char *)workspace + gp.p.o_nexact, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+        if (hipMemcpy(&v, Ws16(gp.p, workspace).nexact, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
             return HMM_ERR_LAUNCH;
         return v;
     }
@@ -406,56 +406,37 @@ int hmm_loglik_grad(const float *A, const float *pi, const float *E, int k, int 
     char *ws = (char *)workspace;
     hipStream_t st = (hipStream_t)stream;
     if ((rc = run_reduce_scan(A, pi, E, p, eps, ws, st))) return rc;
+    const Ws16 w(p, ws);
     const long long nw = apply_waves(p), nwx = apply_waves(px);
-    const dim3 grid((unsigned)((nw + 3) / 4)), gx((unsigned)((nwx + 3) / 4));
-    float *ckpt = (float *)(ws + p.o_ckpt);
-    const Routing rt = routing(p, ws, false, false);
-    double *wll = (double *)(ws + p.o_loglik);
-    float *gpart = (float *)(ws + gp.o_gpart);
-    double *gred = (double *)(ws + gp.o_gred);
+    const Routing rt = routing(w), rtf = routing_flagged(rt, w);
+    float *gpart = ws_at<float>(ws, gp.o_gpart);
+    double *gred = ws_at<double>(ws, gp.o_gred);
     const long long wtot = gp.wpm + gp.wpmx + b;
-    hipLaunchKernelGGL((k_forward<true, false, false>), grid, dim3(256), 0, st, A, pi, E,
-                       (const float *)(ws + p.o_prefix), (const double *)(ws + p.o_llpre), ckpt, (float *)nullptr, wll,
-                       (float *)(ws + p.o_xend), rt, p, eps, nw);
-    float *psi = (float *)(ws + p.o_phi);
-    int *flags = (int *)(ws + p.o_flags);
-    int *wtab = (int *)(ws + p.o_wtab), *wlist = (int *)(ws + p.o_wlist), *wcnt = (int *)(ws + p.o_wcnt);
-    float *xend = (float *)(ws + p.o_xend), *rstart = (float *)(ws + p.o_rstart);
+    launch(k_forward<true, false, false>, apply_grid(p), dim3(256), 0, st, A, pi, E, w.prefix, w.llpre, w.ckpt, nullptr,
+           w.loglik, w.xend, rt, p, eps, nw, nullptr, nullptr);
     // the sequences' window slots of gpart: written only for sequences that have windows
     for (int m = 0; m < k; ++m)
         if (hipMemsetAsync(gpart + ((size_t)m * wtot + gp.wpm + gp.wpmx) * QP * QP, 0, (size_t)b * QP * QP * sizeof(float), st) !=
             hipSuccess)
             return HMM_ERR_LAUNCH;
-    hipLaunchKernelGGL(k_backward_grad<false>, grid, dim3(256), 0, st, A, E, (const float *)ckpt,
-                       (const float *)(ws + p.o_suffix), grad_loglik, dE, gpart, rt, gp.wpm, 0ll, wtot, p, eps, nw, psi,
-                       (const int *)nullptr, (const int *)nullptr, rstart);
+    launch(k_backward_grad<false>, apply_grid(p), dim3(256), 0, st, A, E, w.ckpt, w.suffix, grad_loglik, dE, gpart, rt,
+           gp.wpm, 0ll, wtot, p, eps, nw, w.phi, nullptr, nullptr, w.rstart);
     // the verdict per sequence; the flagged runs of chunks in windows; the scan plan's waves that hold routed chains
     // once more without them; the serial plan for sequences routed whole
-    hipLaunchKernelGGL(k_exact_select, dim3(p.NB), dim3(64), 0, st, rt.topo, psi, p, rt.exact_mode,
-                       win_margin(p), flags, (int *)(ws + p.o_nexact), wtab, wlist, wcnt, (const int *)(ws + p.o_exps));
-    {
-        const unsigned gwv = (unsigned)((p.NB < 4096 ? p.NB : 4096) + 3) / 4;
-        hipLaunchKernelGGL(k_window_grad, dim3(gwv), dim3(256), 0, st, A, E, (const float *)(ws + p.o_prefix),
-                           (const double *)(ws + p.o_llpre), (const float *)(ws + p.o_suffix), (const float *)xend,
-                           (const float *)rstart, (float *)(ws + gp.o_wckpt), wll, grad_loglik, dE, gpart, wtot,
-                           gp.wpm + gp.wpmx, wtab,
-                           (const int *)wlist, wcnt, flags, (double *)(ws + p.o_dfix), p, eps, win_margin(p));
-    }
-    hipLaunchKernelGGL(k_backward_grad<false>, grid, dim3(256), 0, st, A, E, (const float *)ckpt,
-                       (const float *)(ws + p.o_suffix), grad_loglik, dE, gpart, rt, gp.wpm, 0ll, wtot, p, eps, nw,
-                       (float *)nullptr, (const int *)flags, (const int *)wtab, (float *)nullptr);
-    Routing rtf = routing(p, ws, false, false);
-    rtf.flags = flags;
-    hipLaunchKernelGGL((k_forward<true, false, true>), gx, dim3(256), 0, st, A, pi, E, (const float *)nullptr,
-                       (const double *)nullptr, ckpt, (float *)nullptr, wll, (float *)nullptr, rtf, px, eps, nwx);
-    hipLaunchKernelGGL(k_backward_grad<true>, gx, dim3(256), 0, st, A, E, (const float *)ckpt, (const float *)nullptr,
-                       grad_loglik, dE, gpart, rtf, gp.wpmx, gp.wpm, wtot, px, eps, nwx);
-    hipLaunchKernelGGL(k_grad_sum1, dim3(GR_SLICES, k), dim3(256), 0, st, (const float *)gpart, gred, wtot);
-    hipLaunchKernelGGL(k_grad_sum2, dim3(k), dim3(256), 0, st, (const double *)gred, dA, q);
-    hipLaunchKernelGGL(k_grad_pi, dim3(q, k), dim3(64), 0, st, pi, E, (const float *)dE, b, L, q, eps, dpi);
-    if (loglik)
-        hipLaunchKernelGGL(k_copy_loglik, dim3((p.NB + 255) / 256), dim3(256), 0, st,
-                           (const double *)(ws + p.o_loglik), loglik, p.NB);
+    s16_select(p, w, rt, st);
+    launch(k_window_grad, win_grid(p), dim3(256), 0, st, A, E, w.prefix, w.llpre, w.suffix, w.xend, w.rstart,
+           ws_at<float>(ws, gp.o_wckpt), w.loglik, grad_loglik, dE, gpart, wtot, gp.wpm + gp.wpmx, w.wtab, w.wlist, w.wcnt,
+           w.flags, w.dfix, p, eps, win_margin(p));
+    launch(k_backward_grad<false>, apply_grid(p), dim3(256), 0, st, A, E, w.ckpt, w.suffix, grad_loglik, dE, gpart, rt,
+           gp.wpm, 0ll, wtot, p, eps, nw, nullptr, w.flags, w.wtab, nullptr);
+    launch(k_forward<true, false, true>, apply_grid(px), dim3(256), 0, st, A, pi, E, nullptr, nullptr, w.ckpt, nullptr,
+           w.loglik, nullptr, rtf, px, eps, nwx, nullptr, nullptr);
+    launch(k_backward_grad<true>, apply_grid(px), dim3(256), 0, st, A, E, w.ckpt, nullptr, grad_loglik, dE, gpart, rtf,
+           gp.wpmx, gp.wpm, wtot, px, eps, nwx, nullptr, nullptr, nullptr, nullptr);
+    launch(k_grad_sum1, dim3(GR_SLICES, k), dim3(256), 0, st, gpart, gred, wtot);
+    launch(k_grad_sum2, dim3(k), dim3(256), 0, st, gred, dA, q);
+    launch(k_grad_pi, dim3(q, k), dim3(64), 0, st, pi, E, dE, b, L, q, eps, dpi);
+    if (loglik) launch(k_copy_loglik, dim3((p.NB + 255) / 256), dim3(256), 0, st, w.loglik, loglik, p.NB);
     return check_launch();
 }
 

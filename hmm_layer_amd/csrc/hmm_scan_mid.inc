@@ -49,66 +49,75 @@ static int mid_width(int k, int b, int L, int q) {
     return scan64_wanted(k, b, L, q) ? Q64 : 0;
 }
 
+// the regions of the chunked scan's workspace (MidPlan::o_*), typed
+struct WsMid {
+    float *ops; int *exps; float *prefix; double *llpre; float *suffix; double *lsuf, *loglik; float *ckpt, *phi;
+    int *need, *elig, *nex, *risk; float *upi;
+#define WSMID(m) m(ws_at<std::remove_pointer_t<decltype(m)>>(ws, pp.o_##m))
+    WsMid(const MidPlan &pp, const void *ws)
+        : WSMID(ops), WSMID(exps), WSMID(prefix), WSMID(llpre), WSMID(suffix), WSMID(lsuf), WSMID(loglik), WSMID(ckpt),
+          WSMID(phi), WSMID(need), WSMID(elig), WSMID(nex), WSMID(risk), WSMID(upi) {}
+#undef WSMID
+};
+
 // ---- what differs between the widths on the host: how the model check and the reduce stage are launched
 struct Scan32 {
     static constexpr int NT = 2, W = Rows<NT>::W;
     static void check(const float *A, const MidPlan &pp, float eps, char *ws, hipStream_t st) {
-        hipLaunchKernelGGL(k32_check, dim3(pp.p.k), dim3(64), 0, st, A, (int *)(ws + pp.o_elig), pp.p.q, opt(HMM_OPT_EXACT),
-                           eps, (int *)(ws + pp.o_nex), opt(HMM_OPT_FORCE_DENSE) == 1 ? 1 : 0);
+        const WsMid w(pp, ws);
+        launch(k32_check, dim3(pp.p.k), dim3(64), 0, st, A, w.elig, pp.p.q, opt(HMM_OPT_EXACT), eps, w.nex,
+               opt(HMM_OPT_FORCE_DENSE) == 1 ? 1 : 0);
     }
     // the compiled sparse topology first, then the dense reduce for the models outside it
     static void reduce(const float *A, const float *E, const MidPlan &pp, float eps, char *ws, hipStream_t st) {
         const Plan &p = pp.p;
-        float *ops = (float *)(ws + pp.o_ops);
-        int *exps = (int *)(ws + pp.o_exps);
-        const int *elig = (const int *)(ws + pp.o_elig);
+        const WsMid w(pp, ws);
         const unsigned nb = (unsigned)((p.nchains + 4 * RsCfg<TopoGene29>::CPW - 1) / (4 * RsCfg<TopoGene29>::CPW));
-        hipLaunchKernelGGL(k_reduce_sparse_wide<TopoGene29>, dim3(nb), dim3(256), 0, st, A, E, ops, exps, elig, p, eps);
+        launch(k_reduce_sparse_wide<TopoGene29>, dim3(nb), dim3(256), 0, st, A, E, w.ops, w.exps, w.elig, p, eps);
         if (p.k > 1 || !HMM_RS_UNI)                // waves that straddle two models
-            hipLaunchKernelGGL((k_reduce_sparse_wide<TopoGene29, true>), dim3(nb), dim3(256), 0, st, A, E, ops, exps, elig, p, eps);
+            launch(k_reduce_sparse_wide<TopoGene29, true>, dim3(nb), dim3(256), 0, st, A, E, w.ops, w.exps, w.elig, p, eps);
         // every chain its own wave (grid stride; exits at once for the models the sparse kernels served)
         const long long nbd = (p.nchains + 3) / 4;
-        hipLaunchKernelGGL(reduce_dense<NT>, dim3((unsigned)(nbd < 8192 ? nbd : 8192)), dim3(256), 0, st, A, E, ops, exps,
-                           (int *)(ws + pp.o_risk), elig, p, eps);
+        launch(reduce_dense<NT>, dim3((unsigned)(nbd < 8192 ? nbd : 8192)), dim3(256), 0, st, A, E, w.ops, w.exps, w.risk,
+               w.elig, p, eps);
     }
 };
 
 struct Scan64 {
     static constexpr int NT = 4, W = Rows<NT>::W;
     static void check(const float *A, const MidPlan &pp, float eps, char *ws, hipStream_t st) {
-        hipLaunchKernelGGL(k64_check, dim3(pp.p.k), dim3(64), 0, st, A, (int *)(ws + pp.o_elig), pp.p.q, opt(HMM_OPT_EXACT),
-                           eps, (int *)(ws + pp.o_nex), pp.p.NB, opt(HMM_OPT_FORCE_DENSE) == 1 ? 1 : 0);
+        const WsMid w(pp, ws);
+        launch(k64_check, dim3(pp.p.k), dim3(64), 0, st, A, w.elig, pp.p.q, opt(HMM_OPT_EXACT), eps, w.nex, pp.p.NB,
+               opt(HMM_OPT_FORCE_DENSE) == 1 ? 1 : 0);
     }
     static void reduce(const float *A, const float *E, const MidPlan &pp, float eps, char *ws, hipStream_t st) {
         const Plan &p = pp.p;
+        const WsMid w(pp, ws);
         const long long nbd = (p.nchains + 3) / 4;
-        hipLaunchKernelGGL(reduce_dense<NT>, dim3((unsigned)(nbd < 8192 ? nbd : 8192)), dim3(256), 0, st, A, E,
-                           (float *)(ws + pp.o_ops), (int *)(ws + pp.o_exps), (int *)(ws + pp.o_risk),
-                           (const int *)(ws + pp.o_elig), p, eps);
+        launch(reduce_dense<NT>, dim3((unsigned)(nbd < 8192 ? nbd : 8192)), dim3(256), 0, st, A, E, w.ops, w.exps, w.risk,
+               w.elig, p, eps);
     }
 };
 
 // ---- the drivers, S = Scan32 or Scan64
 
+static dim3 mid_grid(const MidPlan &pp) { return dim3((unsigned)((pp.nwaves + 3) / 4)); }
+
 template <class S>
 static void scan_reduce_scan(const float *A, const float *pi, const float *E, const MidPlan &pp, float eps, char *ws,
                              hipStream_t st) {
-    const Plan &p = pp.p;
+    const WsMid w(pp, ws);
     S::check(A, pp, eps, ws, st);
     S::reduce(A, E, pp, eps, ws, st);
-    hipLaunchKernelGGL(scan<S::NT>, dim3(p.NB), dim3(128), 0, st, pi, (const float *)(ws + pp.o_ops),
-                       (const int *)(ws + pp.o_exps), (float *)(ws + pp.o_prefix), (double *)(ws + pp.o_llpre),
-                       (float *)(ws + pp.o_suffix), (double *)(ws + pp.o_lsuf), (double *)(ws + pp.o_loglik),
-                       (const int *)(ws + pp.o_elig), p, eps);
+    launch(scan<S::NT>, dim3(pp.p.NB), dim3(128), 0, st, pi, w.ops, w.exps, w.prefix, w.llpre, w.suffix, w.lsuf, w.loglik,
+           w.elig, pp.p, eps);
 }
 
 // need[] from the certificate sums phi (or null: the reduces' marks only); one kernel for both widths
 template <class S>
-static void scan_select(const MidPlan &pp, const float *phi, char *ws, hipStream_t st) {
-    const Plan &p = pp.p;
-    hipLaunchKernelGGL(k_scan_select, dim3((p.NB + 255) / 256), dim3(256), 0, st, (const int *)(ws + pp.o_elig), phi,
-                       (int *)(ws + pp.o_need), (int *)(ws + pp.o_nex), p, 0.f, opt(HMM_OPT_EXACT),
-                       (const int *)(ws + pp.o_exps), (const int *)(ws + pp.o_risk), S::W);
+static void scan_select(const MidPlan &pp, const WsMid &w, const float *phi, hipStream_t st) {
+    launch(k_scan_select, dim3((pp.p.NB + 255) / 256), dim3(256), 0, st, w.elig, phi, w.need, w.nex, pp.p, 0.f,
+           opt(HMM_OPT_EXACT), w.exps, w.risk, S::W);
 }
 
 // log-likelihoods of the models the chunked path serves -> ws loglik; need[] for the others.  The log-likelihood comes
@@ -117,35 +126,27 @@ static void scan_select(const MidPlan &pp, const float *phi, char *ws, hipStream
 template <class S>
 static void scan_loglik(const float *A, const float *pi, const float *E, const MidPlan &pp, float eps, char *ws,
                         hipStream_t st) {
+    const WsMid w(pp, ws);
     scan_reduce_scan<S>(A, pi, E, pp, eps, ws, st);
     const bool cert = opt(HMM_OPT_EXACT) == HMM_EXACT_AUTO;
-    float *phi = (float *)(ws + pp.o_phi);
     if (cert)
-        hipLaunchKernelGGL((forward<S::NT, false, true>), dim3((unsigned)((pp.nwaves + 3) / 4)), dim3(256), 0, st, A, E,
-                           (const float *)(ws + pp.o_prefix), nullptr, nullptr, nullptr, (const int *)(ws + pp.o_elig),
-                           pp.p, eps, pp.nwaves, (const float *)(ws + pp.o_suffix), phi);
-    scan_select<S>(pp, cert ? phi : nullptr, ws, st);
+        launch(forward<S::NT, false, true>, mid_grid(pp), dim3(256), 0, st, A, E, w.prefix, nullptr, nullptr, nullptr,
+               w.elig, pp.p, eps, pp.nwaves, w.suffix, w.phi);
+    scan_select<S>(pp, w, cert ? w.phi : nullptr, st);
 }
 
 template <class S>
 static void scan_posterior(const float *A, const float *pi, const float *E, const MidPlan &pp, float eps, int mode,
                            float *out, char *ws, hipStream_t st) {
-    const Plan &p = pp.p;
+    const WsMid w(pp, ws);
     scan_reduce_scan<S>(A, pi, E, pp, eps, ws, st);
-    const int *elig = (const int *)(ws + pp.o_elig);
-    float *ckpt = (float *)(ws + pp.o_ckpt);
-    const dim3 grid((unsigned)((pp.nwaves + 3) / 4));
-    hipLaunchKernelGGL((forward<S::NT, false, false>), grid, dim3(256), 0, st, A, E, (const float *)(ws + pp.o_prefix),
-                       nullptr, ckpt, nullptr, elig, p, eps, pp.nwaves, nullptr, nullptr);
-    const float *sx = (const float *)(ws + pp.o_suffix);
-    const double *ls = (const double *)(ws + pp.o_lsuf);
-    const double *ll = (const double *)(ws + pp.o_loglik);
-    float *phi = (float *)(ws + pp.o_phi);
+    launch(forward<S::NT, false, false>, mid_grid(pp), dim3(256), 0, st, A, E, w.prefix, nullptr, w.ckpt, nullptr, w.elig,
+           pp.p, eps, pp.nwaves, nullptr, nullptr);
     auto *kern = mode == HMM_POST_PROB ? backward<S::NT, 0, false>
                  : mode == HMM_POST_LOG ? backward<S::NT, 1, false> : backward<S::NT, 2, false>;
-    hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, A, E, (const float *)ckpt, sx, ls, ll, out, phi, elig, p, eps,
-                       pp.nwaves, nullptr);
-    scan_select<S>(pp, phi, ws, st);
+    launch(kern, mid_grid(pp), dim3(256), 0, st, A, E, w.ckpt, w.suffix, w.lsuf, w.loglik, out, w.phi, w.elig, pp.p, eps,
+           pp.nwaves, nullptr);
+    scan_select<S>(pp, w, w.phi, st);
 }
 
 // log alpha (and the log-likelihoods) of the models the chunked path serves; need[] for the others.  The certificate
@@ -154,12 +155,11 @@ static void scan_posterior(const float *A, const float *pi, const float *E, cons
 template <class S>
 static void scan_forward(const float *A, const float *pi, const float *E, const MidPlan &pp, float eps, float *log_alpha,
                          char *ws, hipStream_t st) {
+    const WsMid w(pp, ws);
     scan_reduce_scan<S>(A, pi, E, pp, eps, ws, st);
-    float *phi = (float *)(ws + pp.o_phi);
-    hipLaunchKernelGGL((forward<S::NT, true, true>), dim3((unsigned)((pp.nwaves + 3) / 4)), dim3(256), 0, st, A, E,
-                       (const float *)(ws + pp.o_prefix), (const double *)(ws + pp.o_llpre), nullptr, log_alpha,
-                       (const int *)(ws + pp.o_elig), pp.p, eps, pp.nwaves, (const float *)(ws + pp.o_suffix), phi);
-    scan_select<S>(pp, phi, ws, st);
+    launch(forward<S::NT, true, true>, mid_grid(pp), dim3(256), 0, st, A, E, w.prefix, w.llpre, nullptr, log_alpha, w.elig,
+           pp.p, eps, pp.nwaves, w.suffix, w.phi);
+    scan_select<S>(pp, w, w.phi, st);
 }
 
 // log beta of the models the chunked path serves; need[] for the others.  hmm_backward has no start distribution: the
@@ -168,13 +168,11 @@ static void scan_forward(const float *A, const float *pi, const float *E, const 
 template <class S>
 static void scan_backward(const float *A, const float *E, const MidPlan &pp, float eps, float *log_beta, char *ws,
                           hipStream_t st) {
-    const Plan &p = pp.p;
-    float *upi = (float *)(ws + pp.o_upi);
-    (void)hipMemsetD32Async((hipDeviceptr_t)upi, __builtin_bit_cast(int, 1.0f / (float)p.q), (size_t)p.k * p.q, st);
-    scan_reduce_scan<S>(A, upi, E, pp, eps, ws, st);
-    float *phi = (float *)(ws + pp.o_phi);
-    hipLaunchKernelGGL((backward<S::NT, 3, true>), dim3((unsigned)((pp.nwaves + 3) / 4)), dim3(256), 0, st, A, E, nullptr,
-                       (const float *)(ws + pp.o_suffix), (const double *)(ws + pp.o_lsuf), nullptr, log_beta, phi,
-                       (const int *)(ws + pp.o_elig), p, eps, pp.nwaves, (const float *)(ws + pp.o_prefix));
-    scan_select<S>(pp, phi, ws, st);
+    const WsMid w(pp, ws);
+    (void)hipMemsetD32Async((hipDeviceptr_t)w.upi, __builtin_bit_cast(int, 1.0f / (float)pp.p.q), (size_t)pp.p.k * pp.p.q,
+                            st);
+    scan_reduce_scan<S>(A, w.upi, E, pp, eps, ws, st);
+    launch(backward<S::NT, 3, true>, mid_grid(pp), dim3(256), 0, st, A, E, nullptr, w.suffix, w.lsuf, nullptr, log_beta,
+           w.phi, w.elig, pp.p, eps, pp.nwaves, w.prefix);
+    scan_select<S>(pp, w, w.phi, st);
 }

@@ -166,7 +166,7 @@ int hmm_seqshard_posterior(const float *A, const float *pi, const float *E, int 
     // the sequence's log-likelihood is the global scan's, not the local prefix's
     hipLaunchKernelGGL(k_copy_loglik, dim3((p.NB + 255) / 256), dim3(256), 0, st, (const double *)total,
                        (double *)(ws + p.o_loglik), p.NB);
-    if ((rc = launch_apply(A, pi, E, p, eps, mode, ws, out, loglik, st, nullptr, false))) return rc;
+    if ((rc = s16_apply(A, pi, E, p, eps, mode, ws, out, loglik, st, nullptr, false))) return rc;
     if (phi_out)
         hipLaunchKernelGGL(k_seqshard_phi, dim3((p.NB + 255) / 256), dim3(256), 0, st, (const float *)(ws + p.o_phi),
                            (const int *)(ws + sp.o_topo2), phi_out, p, eps, (const int *)(ws + p.o_exps));

@@ -99,6 +99,37 @@ def test_midq_validation_order_without_device(lib):
     assert lib.hmm_exact_count(engine.OP_POSTERIOR, 1, 1, 100, 48, None, 0) == 0   # below the chunked path's minimum
 
 
+# one shape per route: the 16-state scan plan (twice), both chunked widths, one wave per sequence (short sequences,
+# and too many of them for the 64-state rows), the GEMM path
+ROUTE_SHAPES = [(1, 1, 300, 15), (2, 3, 17, 7), (1, 1, 300, 20), (1, 1, 300, 48), (1, 1, 100, 48), (1, 2, 40, 100),
+                (1, 200, 300, 48)]
+
+
+@pytest.mark.parametrize("k,b,L,q", ROUTE_SHAPES)
+def test_validation_order_on_every_route(lib, k, b, L, q):
+    # the same precedence whichever path serves the shape: shape / q range, null pointers, the mode, then the
+    # workspace (null, size, alignment); nothing here reaches a HIP call
+    p = 0x10000                                                                 # never dereferenced
+    eps = 1e-16
+    big = 1 << 40
+    assert lib.hmm_forward(p, p, p, k, b, 0, q, eps, p, p, p, big, None) == -1
+    assert lib.hmm_forward(None, p, p, k, b, L, q, eps, p, p, p, big, None) == -3
+    assert lib.hmm_forward(p, p, p, k, b, L, q, eps, p, p, None, big, None) == -3
+    assert lib.hmm_backward(None, None, k, b, L, q, eps, None, None, 0, None) == -3
+    assert lib.hmm_posterior(None, None, None, k, b, L, q, eps, 7, None, None, None, 0, None) == -3
+    assert lib.hmm_posterior(p, p, p, k, b, L, q, eps, 7, p, None, p, big, None) == -6
+    assert lib.hmm_posterior(p, p, p, k, b, L, q, eps, 0, p, None, None, big, None) == -3
+    # 256 bytes short of what hmm_workspace_bytes asks for the same operation
+    short = {op: lib.hmm_workspace_bytes(op, k, b, L, q) - 256
+             for op in (engine.OP_LOGLIK, engine.OP_FORWARD, engine.OP_BACKWARD, engine.OP_POSTERIOR)}
+    assert min(short.values()) > 0
+    assert lib.hmm_forward(p, p, p, k, b, L, q, eps, None, p, p, short[engine.OP_LOGLIK], None) == -4
+    assert lib.hmm_forward(p, p, p, k, b, L, q, eps, p, p, p, short[engine.OP_FORWARD], None) == -4
+    assert lib.hmm_backward(p, p, k, b, L, q, eps, p, p, short[engine.OP_BACKWARD], None) == -4
+    assert lib.hmm_posterior(p, p, p, k, b, L, q, eps, 0, p, None, p, short[engine.OP_POSTERIOR], None) == -4
+    assert lib.hmm_posterior(p, p, p, k, b, L, q, eps, 0, p, None, p + 1, big, None) == -4
+
+
 def test_midq_workspace_follows_the_chunked_path(lib):
     # 48 states, L = 300: up to 96 sequences take the chunked scan (the posterior adds its checkpoints), 97 do not
     w = {(op, b): lib.hmm_workspace_bytes(op, 1, b, 300, 48)
