@@ -76,7 +76,8 @@ def posterior(A, pi, E, mode=engine.POST_LOG, eps=engine.EPS):
 
 class GeneEmissions(torch.autograd.Function):
     """E (b,L,q) = fused gene emitter of x (b,L,s+5) and B (rows,s) = softmax(emission_kernel) for one model.
-    Forward = hmm_gene_emissions, backward = hmm_gene_emissions_grad; only x, B and the small tables are saved
+    Forward = hmm_gene_emissions, backward = hmm_gene_emissions_grad, or their _wide forms above 64 states or 32
+    kernel rows (engine.gene_emissions_routes_wide); only x, B and the small tables are saved
     (not E, and none of the reference's (b,L,64) 3-mer tensors, hmm_layer/gene_pred_hmm_emitter.py:231-277).
     The gradient of the five nucleotide columns of x is zero."""
 
@@ -85,14 +86,17 @@ class GeneEmissions(torch.autograd.Function):
         x, B = x.contiguous(), B.contiguous()
         ctx.save_for_backward(x, B, state_row, codon, state_codon)
         ctx.add, ctx.n_mass = add, n_mass
-        return engine.gene_emissions(x, B, state_row, codon, state_codon, add=add, n_mass=n_mass)
+        ctx.wide = bool(engine.gene_emissions_routes_wide(state_row.numel(), B.shape[0]))
+        fwd = engine.gene_emissions_wide if ctx.wide else engine.gene_emissions
+        return fwd(x, B, state_row, codon, state_codon, add=add, n_mass=n_mass)
 
     @staticmethod
     def backward(ctx, dE):
         x, B, state_row, codon, state_codon = ctx.saved_tensors
         need = ctx.needs_input_grad
-        dx, dB = engine.gene_emissions_grad(x, B, state_row, codon, state_codon, dE.to(torch.float32).contiguous(),
-                                            add=ctx.add, n_mass=ctx.n_mass, want_dx=need[0], want_dB=need[1])
+        bwd = engine.gene_emissions_grad_wide if ctx.wide else engine.gene_emissions_grad
+        dx, dB = bwd(x, B, state_row, codon, state_codon, dE.to(torch.float32).contiguous(),
+                     add=ctx.add, n_mass=ctx.n_mass, want_dx=need[0], want_dB=need[1])
         return dx, dB, None, None, None, None, None
 
 

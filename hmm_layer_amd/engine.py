@@ -96,6 +96,10 @@ _SIGNATURES = {
     "hmm_gene_emissions": (_I, _EMITTER + [_P, _P]),
     "hmm_gene_emissions_grad_workspace_bytes": (_SZ, [_I] * 5),
     "hmm_gene_emissions_grad": (_I, _EMITTER + [_P, _P, _P, _P, _SZ, _P]),
+    "hmm_gene_emissions_wide_max_states": (_I, []),
+    "hmm_gene_emissions_wide": (_I, _EMITTER + [_P, _P]),
+    "hmm_gene_emissions_grad_wide_workspace_bytes": (_SZ, [_I] * 5),
+    "hmm_gene_emissions_grad_wide": (_I, _EMITTER + [_P, _P, _P, _P, _SZ, _P]),
     "hmm_embedding_emissions_max_dim": (_I, []),
     "hmm_embedding_emissions": (_I, [_P, _LL, _I, _I, _I, _P, _P, _P, _I, _P, _I, _F, _F, _I, _P, _P]),
     "hmm_embedding_emissions_grad_max_dim": (_I, []),
@@ -383,16 +387,55 @@ def _emitter_args(x, B, state_row, codon, state_codon):
     return x, B, state_row, codon, state_codon, (b, L, s, rows, q, nc)
 
 
-def gene_emissions(x, B, state_row, codon, state_codon, free_value=1.0 / 4096.0, add=0.0, n_mass=1):
-    """Fused GenePredHMMEmitter.forward for one model: x (b,L,s+5) -> E (b,L,q) fp32.
-    B (rows,s) fp32, state_row (q) int32, codon (2,nc,64) fp32, state_codon (q) int32."""
+def _gene_emissions(name, x, B, state_row, codon, state_codon, free_value, add, n_mass):
     x, B, state_row, codon, state_codon, (b, L, s, rows, q, nc) = _emitter_args(x, B, state_row, codon, state_codon)
     with torch.cuda.device(x.device):
         E = torch.empty((b, L, q), dtype=torch.float32, device=x.device)
-        _check(lib().hmm_gene_emissions(x.data_ptr(), b, L, s, B.data_ptr(), rows, state_row.data_ptr(),
-                                        codon.data_ptr(), nc, state_codon.data_ptr(), q, float(free_value),
-                                        float(add), int(n_mass), E.data_ptr(), _stream(x.device)))
+        _check(getattr(lib(), name)(x.data_ptr(), b, L, s, B.data_ptr(), rows, state_row.data_ptr(),
+                                    codon.data_ptr(), nc, state_codon.data_ptr(), q, float(free_value),
+                                    float(add), int(n_mass), E.data_ptr(), _stream(x.device)))
     return E
+
+
+def gene_emissions(x, B, state_row, codon, state_codon, free_value=1.0 / 4096.0, add=0.0, n_mass=1):
+    """Fused GenePredHMMEmitter.forward for one model: x (b,L,s+5) -> E (b,L,q) fp32.
+    B (rows,s) fp32, state_row (q) int32, codon (2,nc,64) fp32, state_codon (q) int32.  q <= 64, rows <= 32."""
+    return _gene_emissions("hmm_gene_emissions", x, B, state_row, codon, state_codon, free_value, add, n_mass)
+
+
+def gene_emissions_wide(x, B, state_row, codon, state_codon, free_value=1.0 / 4096.0, add=0.0, n_mass=1):
+    """gene_emissions for q <= 256 states and rows <= 256 (hmm_gene_emissions_wide): the gene models of three to
+    eighteen copies.  Same arguments, same values."""
+    return _gene_emissions("hmm_gene_emissions_wide", x, B, state_row, codon, state_codon, free_value, add, n_mass)
+
+
+def gene_emissions_routes_wide(q, rows):
+    """The routing rule of the layer and of autograd.GeneEmissions: None = no fused kernel serves the shape, False =
+    hmm_gene_emissions / _grad (q <= 64 and rows <= 32: what the 15- and 29-state models always used), True = the
+    _wide pair."""
+    if q <= 64 and rows <= 32:
+        return False
+    return True if max(q, rows) <= lib().hmm_gene_emissions_wide_max_states() else None
+
+
+def _gene_emissions_grad(name, tag, x, B, state_row, codon, state_codon, dE, free_value, add, n_mass, want_dx, want_dB):
+    x, B, state_row, codon, state_codon, (b, L, s, rows, q, nc) = _emitter_args(x, B, state_row, codon, state_codon)
+    dE = _dev(dE, "dE")
+    if tuple(dE.shape) != (b, L, q):
+        raise ValueError("dE must have shape %s, got %s" % ((b, L, q), tuple(dE.shape)))
+    if not (want_dx or want_dB):
+        return None, None
+    with torch.cuda.device(x.device):
+        # at most 1024 x rows x s floats: no floor
+        ws = _workspace(x.device, getattr(lib(), name + "_workspace_bytes")(b, L, s, rows, q), tag, floor=0)
+        dx = torch.empty_like(x) if want_dx else None
+        dB = torch.empty_like(B) if want_dB else None
+        _check(getattr(lib(), name)(x.data_ptr(), b, L, s, B.data_ptr(), rows, state_row.data_ptr(),
+                                    codon.data_ptr(), nc, state_codon.data_ptr(), q, float(free_value),
+                                    float(add), int(n_mass), dE.data_ptr(),
+                                    dx.data_ptr() if want_dx else None, dB.data_ptr() if want_dB else None,
+                                    ws.data_ptr(), ws.numel(), _stream(x.device)))
+    return dx, dB
 
 
 def gene_emissions_grad(x, B, state_row, codon, state_codon, dE, free_value=1.0 / 4096.0, add=0.0, n_mass=1,
@@ -403,23 +446,16 @@ def gene_emissions_grad(x, B, state_row, codon, state_codon, dE, free_value=1.0 
     (one (rows,s) partial per workgroup, at most 1024 of them) comes from the engine's cache under a key of its
     own per device and stream, so it never overwrites the routing records that exact_count() and its kin read
     from the recursions' workspace."""
-    x, B, state_row, codon, state_codon, (b, L, s, rows, q, nc) = _emitter_args(x, B, state_row, codon, state_codon)
-    dE = _dev(dE, "dE")
-    if tuple(dE.shape) != (b, L, q):
-        raise ValueError("dE must have shape %s, got %s" % ((b, L, q), tuple(dE.shape)))
-    if not (want_dx or want_dB):
-        return None, None
-    with torch.cuda.device(x.device):
-        # at most 1024 x rows x s floats: no floor
-        ws = _workspace(x.device, lib().hmm_gene_emissions_grad_workspace_bytes(b, L, s, rows, q), "emitter_grad", floor=0)
-        dx = torch.empty_like(x) if want_dx else None
-        dB = torch.empty_like(B) if want_dB else None
-        _check(lib().hmm_gene_emissions_grad(x.data_ptr(), b, L, s, B.data_ptr(), rows, state_row.data_ptr(),
-                                             codon.data_ptr(), nc, state_codon.data_ptr(), q, float(free_value),
-                                             float(add), int(n_mass), dE.data_ptr(),
-                                             dx.data_ptr() if want_dx else None, dB.data_ptr() if want_dB else None,
-                                             ws.data_ptr(), ws.numel(), _stream(x.device)))
-    return dx, dB
+    return _gene_emissions_grad("hmm_gene_emissions_grad", "emitter_grad", x, B, state_row, codon, state_codon, dE,
+                                free_value, add, n_mass, want_dx, want_dB)
+
+
+def gene_emissions_grad_wide(x, B, state_row, codon, state_codon, dE, free_value=1.0 / 4096.0, add=0.0, n_mass=1,
+                             want_dx=True, want_dB=True):
+    """gene_emissions_grad for q <= 256 states and rows <= 256 (hmm_gene_emissions_grad_wide).  Same arguments, same
+    values; the workspace (at most 1024 partials and at most 16 MiB, whatever b L) has a cache key of its own."""
+    return _gene_emissions_grad("hmm_gene_emissions_grad_wide", "emitter_grad_wide", x, B, state_row, codon,
+                                state_codon, dE, free_value, add, n_mass, want_dx, want_dB)
 
 
 def _embedding_args(x, col0, d, mean, inv_std, log_norm, state_row):

@@ -18,6 +18,12 @@ for inference (``forward_fused``: hmm_gene_emissions, then hmm_embedding_emissio
 with the embedding columns read in place) and for training with ``fused_training=True``
 (``forward_fused_trainable``: autograd.EmbeddingEmissions, backward hmm_embedding_emissions_grad).
 ``full_covariance=True`` raises NotImplementedError.
+
+Which kernels serve a model (``GenePredHMMEmitter.fused_route``): up to 64 states and 32 kernel rows (one and two
+copies) hmm_gene_emissions / hmm_gene_emissions_grad; above that, up to 256 states (three to eighteen copies, shared
+introns or not), hmm_gene_emissions_wide / hmm_gene_emissions_grad_wide; above 256 states ``forward()`` in torch ops.
+The embedding kernels stop at 64 states and 32 rows, so with ``emit_embeddings=True`` models of three and more copies
+take ``forward()``.
 Three more differences from the as-shipped reference, on purpose:
   * MvnMixture.__init__ copies the parameter with ``torch.tensor(kernel)`` (MvnMixture.py:40), so the
     reference never trains ``embedding_emission_kernel``; here the graph is kept and mu / sigma receive
@@ -283,12 +289,25 @@ class GenePredHMMEmitter(SimpleGenePredHMMEmitter):
             full = full * nuc
         return full
 
-    # -- fused inference path (HIP kernel hmm_gene_emissions) ---------------------------------
+    # -- fused inference path (HIP kernels hmm_gene_emissions, hmm_gene_emissions_wide) -------
+    def fused_route(self):
+        """Which class / codon kernels serve this model: "gene" (hmm_gene_emissions and its backward: q <= 64 and
+        rows <= 32), "wide" (hmm_gene_emissions_wide and its backward: up to 256 states and rows) or None
+        (forward() in torch ops).  The same rule as autograd.GeneEmissions (engine.gene_emissions_routes_wide).  The
+        embedding kernels serve q <= 64 and rows <= 32 only, so with embeddings there is no wide route."""
+        from . import engine
+        wide = engine.gene_emissions_routes_wide(self.num_states, self.kernel_rows())
+        if wide is None or (wide and self.emit_embeddings):
+            return None
+        return "wide" if wide else "gene"
+
     def can_fuse(self, inputs):
-        # (the fused kernel serves up to 64 states; larger models, e.g. five or more copies, take forward())
+        # one model on a GPU, no trainable nucleotide factor, and a kernel for the shape (fused_route): without
+        # embeddings every model of up to 256 states (18 copies), with embeddings up to 64 states and 32 kernel
+        # rows; anything larger takes forward()
         return (inputs.is_cuda and inputs.shape[0] == 1 and self.num_models == 1
                 and not self.trainable_nucleotides_at_exons and self.built
-                and self.num_states <= 64 and (not self.emit_embeddings or self.kernel_rows() <= 32))
+                and self.fused_route() is not None)
 
     def state_tables(self, device):
         """(state -> kernel row, state -> codon-table row or -1) as int32 tensors."""
@@ -304,7 +323,8 @@ class GenePredHMMEmitter(SimpleGenePredHMMEmitter):
 
     def forward_fused(self, inputs, end_hints=None, training=False):
         """Same values as forward() (inference, one model) without the (b,L,64) 3-mer tensors:
-        one HIP kernel from class probabilities + nucleotides to E.
+        one HIP kernel from class probabilities + nucleotides to E (hmm_gene_emissions, or hmm_gene_emissions_wide
+        above 64 states or 32 kernel rows: fused_route).
 
         With embeddings, a second kernel (hmm_embedding_emissions) multiplies the normal-density factor into E,
         reading the d embedding columns in place from `inputs`; the class kernel takes a compact (b, L, s + 5)
@@ -324,9 +344,10 @@ class GenePredHMMEmitter(SimpleGenePredHMMEmitter):
                 classes = torch.cat([x[..., :s], x[..., s + d:]], dim=-1)
             else:
                 classes = x
-            E = engine.gene_emissions(classes, self.B[0].to(torch.float32).contiguous(),
-                                      row, self.codon_probs.to(inputs.device, torch.float32).contiguous(), cod,
-                                      add=1e-7 if training else 0.0, n_mass=2 if self.n_mass_compat else 1)
+            kernel = engine.gene_emissions_wide if self.fused_route() == "wide" else engine.gene_emissions
+            E = kernel(classes, self.B[0].to(torch.float32).contiguous(),
+                       row, self.codon_probs.to(inputs.device, torch.float32).contiguous(), cod,
+                       add=1e-7 if training else 0.0, n_mass=2 if self.n_mass_compat else 1)
             if self.emit_embeddings:
                 mean, inv_std, log_norm = self.embedding_tables(inputs.device)
                 engine.embedding_emissions(x, s, d, mean, inv_std, log_norm, row, E=E,
@@ -335,8 +356,9 @@ class GenePredHMMEmitter(SimpleGenePredHMMEmitter):
 
     def forward_fused_trainable(self, inputs, end_hints=None, training=False):
         """forward() with its autograd graph, through the HIP kernels: make_B() (softmax, torch), ONE node
-        (autograd.GeneEmissions: hmm_gene_emissions forward, hmm_gene_emissions_grad backward), apply_end_hints
-        (torch).  Between forward and backward only the input, B and the small tables are kept.
+        (autograd.GeneEmissions: hmm_gene_emissions forward, hmm_gene_emissions_grad backward, or the _wide pair
+        above 64 states or 32 kernel rows), apply_end_hints (torch).  Between forward and backward only the input, B
+        and the small tables are kept.
 
         Difference from forward(): the gradient of the five nucleotide columns of the input is exactly zero.
         One-hot nucleotides are data, and the ``== 1`` test on the N flag is not differentiable anyway; autograd

@@ -388,6 +388,35 @@ int hmm_gene_emissions_grad(const float *x, int b, int L, int s, const float *B,
                             void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * hmm_gene_emissions and hmm_gene_emissions_grad for the gene models of three and more copies (1 + 14 c states:
+ * 43, 57, 71 .. 253 for c = 3 .. 18).  Arguments, layouts, add / n_mass / free_value, the exact-zero nucleotide
+ * columns of dx and "dB written whole" are exactly those of the two functions above; so are the values (the forward
+ * runs the same class-sum chain: where both apply, the results are bit-identical).
+ * Limits: 1 <= q <= hmm_gene_emissions_wide_max_states() (256), 1 <= rows <= 256, s <= 32, nc <= 16.  Entries of
+ * state_row outside 0..rows-1 are clamped (they never index out of B); entries of state_codon above nc-1 likewise.
+ * Checked before any HIP call, in this order: shape (HMM_ERR_BAD_SHAPE), limits (HMM_ERR_Q_UNSUPPORTED), pointers
+ * (HMM_ERR_NULL_POINTER; for the grad: any input, the workspace, or both outputs NULL), workspace
+ * (HMM_ERR_WORKSPACE: fewer than hmm_gene_emissions_grad_wide_workspace_bytes bytes, or not 256-byte aligned).
+ * The workspace holds one (rows,s) partial of dB per workgroup: at most 1024 workgroups and at most 16 MiB of
+ * partials (the grid shrinks as rows * s grows).  The query sizes it for that cap, so it does not depend on b*L, and
+ * returns 0 for an unsupported shape.  dx is summed over the groups of 64 states in ascending group order; dB over
+ * the waves of a workgroup in wave order, the states of a row in ascending state order, and the workgroups in
+ * workgroup order in fp64, rounded once.  No atomics: repeated calls, and calls for one of the two outputs, are
+ * bit-identical, and the forward does not depend on the grid.  Runs on `stream` only, no host synchronisation,
+ * capturable into a HIP graph; every offset into x, E, dE and dx is 64-bit.
+ */
+int hmm_gene_emissions_wide_max_states(void);
+int hmm_gene_emissions_wide(const float *x, int b, int L, int s, const float *B, int rows,
+                            const int *state_row, const float *codon, int nc, const int *state_codon, int q,
+                            float free_value, float add, int n_mass, float *E, void *stream);
+size_t hmm_gene_emissions_grad_wide_workspace_bytes(int b, int L, int s, int rows, int q);
+int hmm_gene_emissions_grad_wide(const float *x, int b, int L, int s, const float *B, int rows,
+                                 const int *state_row, const float *codon, int nc, const int *state_codon, int q,
+                                 float free_value, float add, int n_mass, const float *dE,
+                                 float *dx /* (b,L,s+5) or NULL */, float *dB /* (rows,s) or NULL */,
+                                 void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Per-kernel timing for the roofline report (bench.py): the same computation as
  * hmm_posterior with every kernel launch bracketed by HIP events recorded on `stream`.
  * hmm_profile_read() waits for the recorded events, returns the summed milliseconds and
