@@ -37,14 +37,16 @@ def posterior(A, pi, E, eps=EPS):
     return g / g.sum(-1, keepdim=True), ll
 
 
-def posterior_grad(A, pi, E, grad_out, log=True, eps=EPS, add_loglik=False):
+def posterior_grad(A, pi, E, grad_out, log=True, eps=EPS, add_loglik=False, dtype=torch.float64):
     """d <grad_out, out> / d(A, pi, E) with out = log gamma (log=True) or gamma, plus loglik per
-    sequence if add_loglik (the reference's no_loglik=True output); numpy in, numpy out."""
+    sequence if add_loglik (the reference's no_loglik=True output); numpy in, numpy out.
+    dtype=torch.float32 runs the same recursion and autograd in fp32: what rounding alone costs
+    (tests/postgrad_mid_cases.py derives its limits from it)."""
     import numpy as np
-    A = torch.as_tensor(np.asarray(A), dtype=torch.float64).clone().requires_grad_(True)
-    pi = torch.as_tensor(np.asarray(pi), dtype=torch.float64).clone().requires_grad_(True)
-    E = torch.as_tensor(np.asarray(E), dtype=torch.float64).clone().requires_grad_(True)
-    G = torch.as_tensor(np.asarray(grad_out), dtype=torch.float64)
+    A = torch.as_tensor(np.asarray(A), dtype=dtype).clone().requires_grad_(True)
+    pi = torch.as_tensor(np.asarray(pi), dtype=dtype).clone().requires_grad_(True)
+    E = torch.as_tensor(np.asarray(E), dtype=dtype).clone().requires_grad_(True)
+    G = torch.as_tensor(np.asarray(grad_out), dtype=dtype)
     gam, ll = posterior(A, pi, E, eps)
     out = torch.log(gam) if log else gam
     if add_loglik:

@@ -206,7 +206,8 @@ def test_full_size_expected_count_identities():
     assert bool(torch.isfinite(dA).all()) and bool((dA[A > 0] > 0).all())
 
 
-@pytest.mark.parametrize("q,b,L,sparse", [(17, 3, 60, False), (29, 4, 210, True), (48, 2, 90, True), (64, 3, 75, False)])
+@pytest.mark.parametrize("q,b,L,sparse", [(17, 3, 60, False), (29, 4, 210, True), (48, 2, 90, True), (64, 3, 75, False),
+                                          (33, 3, 60, False), (47, 2, 90, True), (63, 3, 75, False)])
 def test_mid_size_models_one_wave_per_sequence(q, b, L, sparse):
     """17..64 states (hmm_midq.inc): same oracles and tolerances as the scan path, incl. upstream
     weights of either sign, clamped emissions and two models in one call."""
@@ -218,6 +219,29 @@ def test_mid_size_models_one_wave_per_sequence(q, b, L, sparse):
     w = rng.standard_normal((2, b)).astype(np.float32)
     dA, dpi, dE, ll = check(A, pi, E, w, "midq q=%d" % q)
     assert np.all(dE[0, :, ::7, 1] == 0.0)
+    a = run_grad(A, pi, E, w)
+    for x, y in zip(a, (dA, dpi, dE, ll)):
+        assert np.array_equal(x, y)                              # deterministic
+
+
+def test_three_copy_gene_model_43_states():
+    """The 43-state three-copy gene model (k_mq_backward_grad<48> with idle lanes) and a dense 43-state model in one
+    call, against textbook.loglik_grad: same checks as test_mid_size_models_one_wave_per_sequence."""
+    from hmm_layer_amd.gene_pred_hmm_transitioner import GenePredMultiHMMTransitioner
+    rng = np.random.default_rng(43)
+    q, b, L = 43, 3, 203
+    tr = GenePredMultiHMMTransitioner(k=3, initial_exon_len=200, initial_intron_len=4500, initial_ir_len=10000)
+    with torch.no_grad():
+        Ag = tr.make_A()[0].numpy().astype(np.float32)
+        pig = tr.make_initial_distribution().reshape(-1).numpy().astype(np.float32)
+    assert Ag.shape == (q, q)
+    Ad, pid = rand_model(rng, q)
+    A, pi = np.stack([Ag, Ad]), np.stack([pig, pid])
+    E = (rng.random((2, b, L, q)) * 0.9 + 0.05).astype(np.float32)
+    E[0, :, ::7, 20] = 0.0                                      # clamped emissions: no gradient there
+    w = rng.standard_normal((2, b)).astype(np.float32)
+    dA, dpi, dE, ll = check(A, pi, E, w, "gene43")
+    assert np.all(dE[0, :, ::7, 20] == 0.0)
     a = run_grad(A, pi, E, w)
     for x, y in zip(a, (dA, dpi, dE, ll)):
         assert np.array_equal(x, y)                              # deterministic

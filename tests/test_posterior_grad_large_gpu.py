@@ -199,7 +199,7 @@ def test_rare_emissions_on_the_most_probable_path(q):
             check_model([x[0] for x in got], A, pi, E[0], G[0], mode, "rare q=%d mode=%d route=%d" % (q, mode, r))
 
 
-@pytest.mark.parametrize("q", [1, 15, 29, 64])
+@pytest.mark.parametrize("q", [1, 15, 29, 33, 43, 48, 57, 64])
 def test_equals_hmm_posterior_grad_up_to_64_states(q):
     rng = np.random.default_rng(100 + q)
     A, pi = rand_model(rng, q, sparse=q % 2 == 1)
