@@ -108,7 +108,8 @@ def gene_emissions(x, B, state_row, codon, state_codon, add=0.0, n_mass=1):
 class EmbeddingEmissions(torch.autograd.Function):
     """E_out (b,L,q) = E_in * (exp(inv_temperature * log N(x[..., col0:col0+d]; mean, 1/inv_std)) + add)[..., state_row]
     (E_in None: the factor alone).  Forward = hmm_embedding_emissions on a fresh output (E_in survives for the
-    backward), backward = hmm_embedding_emissions_grad.  Differentiable in E_in, x (embedding columns; every other
+    backward), backward = hmm_embedding_emissions_grad, or their _wide forms above 64 states or 32 kernel rows
+    (engine.embedding_emissions_routes_wide).  Differentiable in E_in, x (embedding columns; every other
     column of its gradient is exactly 0), mean, inv_std and log_norm.  Saved: E_in, x, the three tables and
     state_row — not the factor, and nothing of size b L rows d."""
 
@@ -119,9 +120,10 @@ class EmbeddingEmissions(torch.autograd.Function):
             E_in = E_in.contiguous()
         ctx.save_for_backward(E_in, x, mean, inv_std, log_norm, state_row)
         ctx.args = (int(col0), int(d), float(inv_temperature), float(add))
-        return engine.embedding_emissions(x, col0, d, mean, inv_std, log_norm, state_row,
-                                          E=None if E_in is None else E_in.clone(),
-                                          inv_temperature=inv_temperature, add=add)
+        ctx.wide = bool(engine.embedding_emissions_routes_wide(state_row.numel(), mean.shape[0]))
+        fwd = engine.embedding_emissions_wide if ctx.wide else engine.embedding_emissions
+        return fwd(x, col0, d, mean, inv_std, log_norm, state_row, E=None if E_in is None else E_in.clone(),
+                   inv_temperature=inv_temperature, add=add)
 
     @staticmethod
     def backward(ctx, dE):
@@ -129,7 +131,8 @@ class EmbeddingEmissions(torch.autograd.Function):
         col0, d, inv_temperature, add = ctx.args
         need = ctx.needs_input_grad
         tables = any(need[2:5])
-        dE_in, dx, dmean, dinv_std, dlog_norm = engine.embedding_emissions_grad(
+        bwd = engine.embedding_emissions_grad_wide if ctx.wide else engine.embedding_emissions_grad
+        dE_in, dx, dmean, dinv_std, dlog_norm = bwd(
             x, col0, d, mean, inv_std, log_norm, state_row, dE.to(torch.float32).contiguous(), E_in=E_in,
             inv_temperature=inv_temperature, add=add, want_dE_in=need[0], want_demb=need[1], want_tables=tables,
             dx_out=torch.zeros_like(x) if need[1] else None)

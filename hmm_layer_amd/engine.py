@@ -106,6 +106,11 @@ _SIGNATURES = {
     "hmm_embedding_emissions_grad_workspace_bytes": (_SZ, [_I] * 5),
     "hmm_embedding_emissions_grad": (_I, [_P, _LL, _I, _I, _I, _P, _P, _P, _I, _P, _I, _F, _F, _P, _P, _P, _P, _LL,
                                           _P, _P, _P, _P, _SZ, _P]),
+    "hmm_embedding_emissions_wide_max_states": (_I, []),
+    "hmm_embedding_emissions_wide": (_I, [_P, _LL, _I, _I, _I, _P, _P, _P, _I, _P, _I, _F, _F, _I, _P, _P]),
+    "hmm_embedding_emissions_grad_wide_workspace_bytes": (_SZ, [_I] * 5),
+    "hmm_embedding_emissions_grad_wide": (_I, [_P, _LL, _I, _I, _I, _P, _P, _P, _I, _P, _I, _F, _F, _P, _P, _P, _P, _LL,
+                                               _P, _P, _P, _P, _SZ, _P]),
     "hmm_loglik_partials": (_I, [_P, _P, _I, _I, _P, _P]),
     "hmm_loglik_allreduce": (_I, [_P, _P, _I, _P]),
     "hmm_seqshard_workspace_bytes": (_SZ, [_I] * 5),
@@ -480,11 +485,7 @@ def _is_E(t, shape):
             and tuple(t.shape) == shape)
 
 
-def embedding_emissions(x, col0, d, mean, inv_std, log_norm, state_row, E=None, inv_temperature=1.0, add=0.0):
-    """Embedding-emission factor (hmm_embedding_emissions): x (b,L,w) fp32 holds every position's embedding in
-    columns col0 .. col0+d-1, read in place (no copy of the columns is made).  mean, inv_std (rows,d) fp32,
-    log_norm (rows) fp32, state_row (q) int32.  f = exp(inv_temperature * log N(x; mean, 1/inv_std)) + add.
-    With E (b,L,q) given, E *= f in place; otherwise a new E = f.  Returns E."""
+def _embedding_emissions(name, x, col0, d, mean, inv_std, log_norm, state_row, E, inv_temperature, add):
     x, mean, inv_std, log_norm, state_row, col0, d, (b, L, w, rows, q) = _embedding_args(
         x, col0, d, mean, inv_std, log_norm, state_row)
     multiply = E is not None
@@ -494,11 +495,74 @@ def embedding_emissions(x, col0, d, mean, inv_std, log_norm, state_row, E=None, 
     with torch.cuda.device(x.device):
         if not multiply:
             E = torch.empty((b, L, q), dtype=torch.float32, device=x.device)
-        _check(lib().hmm_embedding_emissions(x.data_ptr() + 4 * col0, w, b, L, d, mean.data_ptr(), inv_std.data_ptr(),
-                                             log_norm.data_ptr(), rows, state_row.data_ptr(), q,
-                                             float(inv_temperature), float(add), int(multiply), E.data_ptr(),
-                                             _stream(x.device)))
+        _check(getattr(lib(), name)(x.data_ptr() + 4 * col0, w, b, L, d, mean.data_ptr(), inv_std.data_ptr(),
+                                    log_norm.data_ptr(), rows, state_row.data_ptr(), q,
+                                    float(inv_temperature), float(add), int(multiply), E.data_ptr(),
+                                    _stream(x.device)))
     return E
+
+
+def embedding_emissions(x, col0, d, mean, inv_std, log_norm, state_row, E=None, inv_temperature=1.0, add=0.0):
+    """Embedding-emission factor (hmm_embedding_emissions): x (b,L,w) fp32 holds every position's embedding in
+    columns col0 .. col0+d-1, read in place (no copy of the columns is made).  mean, inv_std (rows,d) fp32,
+    log_norm (rows) fp32, state_row (q) int32.  f = exp(inv_temperature * log N(x; mean, 1/inv_std)) + add.
+    With E (b,L,q) given, E *= f in place; otherwise a new E = f.  Returns E.  q <= 64, rows <= 32."""
+    return _embedding_emissions("hmm_embedding_emissions", x, col0, d, mean, inv_std, log_norm, state_row, E,
+                                inv_temperature, add)
+
+
+def embedding_emissions_wide(x, col0, d, mean, inv_std, log_norm, state_row, E=None, inv_temperature=1.0, add=0.0):
+    """embedding_emissions for q <= 256 states and rows <= 256 (hmm_embedding_emissions_wide): the gene models of
+    three to eighteen copies.  Same arguments; where both apply, bit-identical values."""
+    return _embedding_emissions("hmm_embedding_emissions_wide", x, col0, d, mean, inv_std, log_norm, state_row, E,
+                                inv_temperature, add)
+
+
+def embedding_emissions_routes_wide(q, rows):
+    """The routing rule of the layer and of autograd.EmbeddingEmissions: None = no fused kernel serves the shape,
+    False = hmm_embedding_emissions / _grad (q <= 64 and rows <= 32: what the 15- and 29-state models always used),
+    True = the _wide pair."""
+    if q <= 64 and rows <= 32:
+        return False
+    return True if max(q, rows) <= lib().hmm_embedding_emissions_wide_max_states() else None
+
+
+def _embedding_emissions_grad(name, tag, limits, x, col0, d, mean, inv_std, log_norm, state_row, dE, E_in,
+                              inv_temperature, add, want_dE_in, want_demb, want_tables, dx_out):
+    x, mean, inv_std, log_norm, state_row, col0, d, (b, L, w, rows, q) = _embedding_args(
+        x, col0, d, mean, inv_std, log_norm, state_row)
+    if not _is_E(dE, (b, L, q)):
+        raise ValueError("dE must be a contiguous fp32 device tensor of shape %s" % ((b, L, q),))
+    if E_in is not None and not _is_E(E_in, (b, L, q)):
+        raise ValueError("E_in must be a contiguous fp32 device tensor of shape %s" % ((b, L, q),))
+    if dx_out is not None and not _is_E(dx_out, (b, L, w)):
+        raise ValueError("dx_out must be a contiguous fp32 device tensor of shape %s" % ((b, L, w),))
+    want_dE_in = bool(want_dE_in) and E_in is not None
+    if not (want_dE_in or want_demb or want_tables):
+        return None, None, None, None, None
+    need = getattr(lib(), name + "_workspace_bytes")(b, L, d, rows, q)
+    if need == 0:
+        raise ValueError("%s covers %s, d <= %d (got q = %d, rows = %d, d = %d)"
+                         % (name, limits, lib().hmm_embedding_emissions_grad_max_dim(), q, rows, d))
+    with torch.cuda.device(x.device):
+        ws = _workspace(x.device, need, tag, floor=0)
+        dE_in = torch.empty_like(dE) if want_dE_in else None
+        demb, demb_ptr, ldd = None, None, 0
+        if want_demb and dx_out is not None:
+            demb, demb_ptr, ldd = dx_out, dx_out.data_ptr() + 4 * col0, w
+        elif want_demb:
+            demb = torch.empty((b, L, d), dtype=torch.float32, device=x.device)
+            demb_ptr, ldd = demb.data_ptr(), d
+        dmean = torch.empty_like(mean) if want_tables else None
+        dinv_std = torch.empty_like(inv_std) if want_tables else None
+        dlog_norm = torch.empty_like(log_norm) if want_tables else None
+        _check(getattr(lib(), name)(
+            x.data_ptr() + 4 * col0, w, b, L, d, mean.data_ptr(), inv_std.data_ptr(), log_norm.data_ptr(), rows,
+            state_row.data_ptr(), q, float(inv_temperature), float(add),
+            E_in.data_ptr() if E_in is not None else None, dE.data_ptr(), dE_in.data_ptr() if want_dE_in else None,
+            demb_ptr, ldd, dmean.data_ptr() if want_tables else None, dinv_std.data_ptr() if want_tables else None,
+            dlog_norm.data_ptr() if want_tables else None, ws.data_ptr(), ws.numel(), _stream(x.device)))
+    return dE_in, demb, dmean, dinv_std, dlog_norm
 
 
 def embedding_emissions_grad(x, col0, d, mean, inv_std, log_norm, state_row, dE, E_in=None, inv_temperature=1.0,
@@ -512,40 +576,19 @@ def embedding_emissions_grad(x, col0, d, mean, inv_std, log_norm, state_row, dE,
     a fixed order: repeated calls, and calls for a subset of the outputs, are bit-identical.  The workspace
     (W (b L, rows) and at most 16 MiB of workgroup partials) comes from the engine's cache under a key of its
     own per device and stream."""
-    x, mean, inv_std, log_norm, state_row, col0, d, (b, L, w, rows, q) = _embedding_args(
-        x, col0, d, mean, inv_std, log_norm, state_row)
-    if not _is_E(dE, (b, L, q)):
-        raise ValueError("dE must be a contiguous fp32 device tensor of shape %s" % ((b, L, q),))
-    if E_in is not None and not _is_E(E_in, (b, L, q)):
-        raise ValueError("E_in must be a contiguous fp32 device tensor of shape %s" % ((b, L, q),))
-    if dx_out is not None and not _is_E(dx_out, (b, L, w)):
-        raise ValueError("dx_out must be a contiguous fp32 device tensor of shape %s" % ((b, L, w),))
-    want_dE_in = bool(want_dE_in) and E_in is not None
-    if not (want_dE_in or want_demb or want_tables):
-        return None, None, None, None, None
-    need = lib().hmm_embedding_emissions_grad_workspace_bytes(b, L, d, rows, q)
-    if need == 0:
-        raise ValueError("hmm_embedding_emissions_grad covers q <= 64, rows <= 32, d <= %d (got q = %d, rows = %d, "
-                         "d = %d)" % (lib().hmm_embedding_emissions_grad_max_dim(), q, rows, d))
-    with torch.cuda.device(x.device):
-        ws = _workspace(x.device, need, "embedding_grad", floor=0)
-        dE_in = torch.empty_like(dE) if want_dE_in else None
-        demb, demb_ptr, ldd = None, None, 0
-        if want_demb and dx_out is not None:
-            demb, demb_ptr, ldd = dx_out, dx_out.data_ptr() + 4 * col0, w
-        elif want_demb:
-            demb = torch.empty((b, L, d), dtype=torch.float32, device=x.device)
-            demb_ptr, ldd = demb.data_ptr(), d
-        dmean = torch.empty_like(mean) if want_tables else None
-        dinv_std = torch.empty_like(inv_std) if want_tables else None
-        dlog_norm = torch.empty_like(log_norm) if want_tables else None
-        _check(lib().hmm_embedding_emissions_grad(
-            x.data_ptr() + 4 * col0, w, b, L, d, mean.data_ptr(), inv_std.data_ptr(), log_norm.data_ptr(), rows,
-            state_row.data_ptr(), q, float(inv_temperature), float(add),
-            E_in.data_ptr() if E_in is not None else None, dE.data_ptr(), dE_in.data_ptr() if want_dE_in else None,
-            demb_ptr, ldd, dmean.data_ptr() if want_tables else None, dinv_std.data_ptr() if want_tables else None,
-            dlog_norm.data_ptr() if want_tables else None, ws.data_ptr(), ws.numel(), _stream(x.device)))
-    return dE_in, demb, dmean, dinv_std, dlog_norm
+    return _embedding_emissions_grad("hmm_embedding_emissions_grad", "embedding_grad", "q <= 64, rows <= 32", x, col0,
+                                     d, mean, inv_std, log_norm, state_row, dE, E_in, inv_temperature, add,
+                                     want_dE_in, want_demb, want_tables, dx_out)
+
+
+def embedding_emissions_grad_wide(x, col0, d, mean, inv_std, log_norm, state_row, dE, E_in=None, inv_temperature=1.0,
+                                  add=0.0, want_dE_in=True, want_demb=True, want_tables=True, dx_out=None):
+    """embedding_emissions_grad for q <= 256 states and rows <= 256 (hmm_embedding_emissions_grad_wide).  Same
+    arguments, same formulas; the workspace (W (b L, rows) and at most 16 MiB of partials) has a cache key of its
+    own."""
+    return _embedding_emissions_grad("hmm_embedding_emissions_grad_wide", "embedding_grad_wide",
+                                     "q <= 256, rows <= 256", x, col0, d, mean, inv_std, log_norm, state_row, dE, E_in,
+                                     inv_temperature, add, want_dE_in, want_demb, want_tables, dx_out)
 
 
 def _viterbi(name, logA, logpi, logE):

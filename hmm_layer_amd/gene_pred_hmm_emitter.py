@@ -19,11 +19,12 @@ with the embedding columns read in place) and for training with ``fused_training
 (``forward_fused_trainable``: autograd.EmbeddingEmissions, backward hmm_embedding_emissions_grad).
 ``full_covariance=True`` raises NotImplementedError.
 
-Which kernels serve a model (``GenePredHMMEmitter.fused_route``): up to 64 states and 32 kernel rows (one and two
+Which kernels serve a model (``GenePredHMMEmitter.fused_routes``): up to 64 states and 32 kernel rows (one and two
 copies) hmm_gene_emissions / hmm_gene_emissions_grad; above that, up to 256 states (three to eighteen copies, shared
 introns or not), hmm_gene_emissions_wide / hmm_gene_emissions_grad_wide; above 256 states ``forward()`` in torch ops.
-The embedding kernels stop at 64 states and 32 rows, so with ``emit_embeddings=True`` models of three and more copies
-take ``forward()``.
+With ``emit_embeddings=True`` the embedding factor follows the same borders: hmm_embedding_emissions /
+hmm_embedding_emissions_grad up to 64 states and 32 rows, hmm_embedding_emissions_wide /
+hmm_embedding_emissions_grad_wide up to 256 states and rows (three to eighteen copies), ``forward()`` above.
 Three more differences from the as-shipped reference, on purpose:
   * MvnMixture.__init__ copies the parameter with ``torch.tensor(kernel)`` (MvnMixture.py:40), so the
     reference never trains ``embedding_emission_kernel``; here the graph is kept and mu / sigma receive
@@ -291,23 +292,41 @@ class GenePredHMMEmitter(SimpleGenePredHMMEmitter):
 
     # -- fused inference path (HIP kernels hmm_gene_emissions, hmm_gene_emissions_wide) -------
     def fused_route(self):
-        """Which class / codon kernels serve this model: "gene" (hmm_gene_emissions and its backward: q <= 64 and
-        rows <= 32), "wide" (hmm_gene_emissions_wide and its backward: up to 256 states and rows) or None
-        (forward() in torch ops).  The same rule as autograd.GeneEmissions (engine.gene_emissions_routes_wide).  The
-        embedding kernels serve q <= 64 and rows <= 32 only, so with embeddings there is no wide route."""
+        """The route that serves this model without the wide embedding kernels: "gene" (hmm_gene_emissions and its
+        backward: q <= 64 and rows <= 32), "wide" (hmm_gene_emissions_wide and its backward: up to 256 states and
+        rows, no embeddings) or None.  Kept for its callers; the layer itself goes by fused_routes(), which also
+        knows hmm_embedding_emissions_wide."""
         from . import engine
         wide = engine.gene_emissions_routes_wide(self.num_states, self.kernel_rows())
         if wide is None or (wide and self.emit_embeddings):
             return None
         return "wide" if wide else "gene"
 
+    def fused_routes(self):
+        """(class route, embedding route) of this model: ("gene" | "wide" | None, None | "mvn" | "mvn_wide").  "gene" /
+        "mvn" are hmm_gene_emissions / hmm_embedding_emissions and their backwards (q <= 64 and rows <= 32), "wide" /
+        "mvn_wide" the _wide pairs (up to 256 states and rows); the embedding route is None without embeddings.  A
+        class route of None means forward() in torch ops (then the embedding route is None too).  The same rules as
+        autograd.GeneEmissions and autograd.EmbeddingEmissions (engine.gene_emissions_routes_wide,
+        engine.embedding_emissions_routes_wide)."""
+        from . import engine
+        q, rows = self.num_states, self.kernel_rows()
+        wide = engine.gene_emissions_routes_wide(q, rows)
+        if wide is None:
+            return None, None
+        if not self.emit_embeddings:
+            return "wide" if wide else "gene", None
+        mvn = engine.embedding_emissions_routes_wide(q, rows)
+        if mvn is None:
+            return None, None
+        return "wide" if wide else "gene", "mvn_wide" if mvn else "mvn"
+
     def can_fuse(self, inputs):
-        # one model on a GPU, no trainable nucleotide factor, and a kernel for the shape (fused_route): without
-        # embeddings every model of up to 256 states (18 copies), with embeddings up to 64 states and 32 kernel
-        # rows; anything larger takes forward()
+        # one model on a GPU, no trainable nucleotide factor, and kernels for the shape (fused_routes): every model
+        # of up to 256 states and kernel rows (18 copies), with or without embeddings; anything larger takes forward()
         return (inputs.is_cuda and inputs.shape[0] == 1 and self.num_models == 1
                 and not self.trainable_nucleotides_at_exons and self.built
-                and self.fused_route() is not None)
+                and self.fused_routes()[0] is not None)
 
     def state_tables(self, device):
         """(state -> kernel row, state -> codon-table row or -1) as int32 tensors."""
@@ -324,9 +343,9 @@ class GenePredHMMEmitter(SimpleGenePredHMMEmitter):
     def forward_fused(self, inputs, end_hints=None, training=False):
         """Same values as forward() (inference, one model) without the (b,L,64) 3-mer tensors:
         one HIP kernel from class probabilities + nucleotides to E (hmm_gene_emissions, or hmm_gene_emissions_wide
-        above 64 states or 32 kernel rows: fused_route).
+        above 64 states or 32 kernel rows: fused_routes).
 
-        With embeddings, a second kernel (hmm_embedding_emissions) multiplies the normal-density factor into E,
+        With embeddings, a second kernel (hmm_embedding_emissions, or hmm_embedding_emissions_wide) multiplies the normal-density factor into E,
         reading the d embedding columns in place from `inputs`; the class kernel takes a compact (b, L, s + 5)
         copy of the other columns.  With training=True the reference adds 1e-10 to the class term before the
         product, which the class kernel cannot express: that case takes forward()."""
@@ -344,14 +363,15 @@ class GenePredHMMEmitter(SimpleGenePredHMMEmitter):
                 classes = torch.cat([x[..., :s], x[..., s + d:]], dim=-1)
             else:
                 classes = x
-            kernel = engine.gene_emissions_wide if self.fused_route() == "wide" else engine.gene_emissions
+            route, mvn_route = self.fused_routes()
+            kernel = engine.gene_emissions_wide if route == "wide" else engine.gene_emissions
             E = kernel(classes, self.B[0].to(torch.float32).contiguous(),
                        row, self.codon_probs.to(inputs.device, torch.float32).contiguous(), cod,
                        add=1e-7 if training else 0.0, n_mass=2 if self.n_mass_compat else 1)
             if self.emit_embeddings:
                 mean, inv_std, log_norm = self.embedding_tables(inputs.device)
-                engine.embedding_emissions(x, s, d, mean, inv_std, log_norm, row, E=E,
-                                           inv_temperature=1.0 / float(self.temperature))
+                mvn = engine.embedding_emissions_wide if mvn_route == "mvn_wide" else engine.embedding_emissions
+                mvn(x, s, d, mean, inv_std, log_norm, row, E=E, inv_temperature=1.0 / float(self.temperature))
             return self.apply_end_hints(E.unsqueeze(0), end_hints)
 
     def forward_fused_trainable(self, inputs, end_hints=None, training=False):
@@ -366,7 +386,7 @@ class GenePredHMMEmitter(SimpleGenePredHMMEmitter):
         A caller who concatenates network output with one-hot nucleotides never sees them.  Needs can_fuse(inputs).
 
         With embeddings a second node follows (autograd.EmbeddingEmissions: hmm_embedding_emissions forward,
-        hmm_embedding_emissions_grad backward) that multiplies the normal-density factor into E, reading the d
+        hmm_embedding_emissions_grad backward, or the _wide pair above 64 states or 32 kernel rows) that multiplies the normal-density factor into E, reading the d
         embedding columns of the input in place; the class node takes the compact (b, L, s + 5) copy of the other
         columns.  The tables come from embedding_tables_with_graph, so embedding_emission_kernel trains.  With
         training=True the reference adds 1e-10 to the class term before the product ((C + 1e-10) (f + 1e-10)

@@ -417,6 +417,53 @@ int hmm_gene_emissions_grad_wide(const float *x, int b, int L, int s, const floa
                                  void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * hmm_embedding_emissions and hmm_embedding_emissions_grad for the gene models of three and more copies with
+ * emit_embeddings=True (43 to 253 states; 37 kernel rows and more).  Arguments, layouts, formulas, multiply 0 / 1,
+ * add, inv_temperature, the clamping of state_row entries outside 0..rows-1, ld / ldd (embeddings read in place,
+ * demb written in place), the NULL-able arguments and "all three table gradients or none" are exactly those of the
+ * two functions above.  Everything is evaluated in the difference form ((x - mean) first).
+ * Limits: 1 <= q <= hmm_embedding_emissions_wide_max_states() (256), 1 <= rows <= 256,
+ * 1 <= d <= hmm_embedding_emissions_max_dim() (4096; every d from 1 up).  Checked before any HIP call, in this
+ * order: shape (HMM_ERR_BAD_SHAPE, includes ld < d, and ldd < d with demb given), limits (HMM_ERR_Q_UNSUPPORTED),
+ * pointers (HMM_ERR_NULL_POINTER; for the grad: any input, the workspace, no output at all, one or two of the three
+ * table gradients, dE_in without E_in), then multiply not 0 or 1 (forward, HMM_ERR_BAD_ARGUMENT) or the workspace
+ * (grad, HMM_ERR_WORKSPACE: fewer than hmm_embedding_emissions_grad_wide_workspace_bytes bytes, or not 256-byte
+ * aligned).
+ * Forward: the rows are processed in blocks of 32 per tile of 256 positions; per (position, row) the sum over the d
+ * columns runs in the order of hmm_embedding_emissions (slices of 16 columns in order, four partial sums per
+ * slice), so wherever both functions accept a shape (q <= 64, rows <= 32) the outputs are bit-identical.  Nothing
+ * depends on the grid.
+ * Backward, reduction orders (all fixed by b*L, d, rows, q and the row map):
+ *   Gf[p][r]   the states of row r in ascending state order, fp32;
+ *   demb[p][c] the rows in ascending order, one fma each, fp32, negated once;
+ *   tables     per block of 32 rows: fp32 inside a workgroup (workgroup x of X takes the tiles of 256 positions x,
+ *              x + X, ...; the positions of a tile in ascending order per position group, the groups in group order),
+ *              one partial per workgroup in the workspace, then the partials in workgroup order in fp64, times
+ *              inv_std^2 / -inv_std in fp64, rounded to fp32 once.
+ * No atomics: repeated calls, and calls for any subset of {dE_in, demb, tables}, are bit-identical.
+ * The workspace holds W (b*L x rows rounded up to 4 floats) and X = min(tiles, 1024, 16 MiB / partial) workgroup
+ * partials of rows * (2 d + 1) floats: at most 16 MiB of partials whatever b*L (the grid shrinks as rows * d grows).
+ * The query returns 0 for an unsupported shape.  Both run on `stream` only, without host synchronisation, and are
+ * capturable into a HIP graph; every offset into emb, demb, E, E_in, dE and dE_in is 64-bit.
+ */
+int hmm_embedding_emissions_wide_max_states(void);
+int hmm_embedding_emissions_wide(const float *emb, long long ld, int b, int L, int d,
+                                 const float *mean, const float *inv_std /* (rows,d) each */,
+                                 const float *log_norm /* (rows) */,
+                                 int rows, const int *state_row, int q,
+                                 float inv_temperature, float add, int multiply,
+                                 float *E /* (b,L,q) */, void *stream);
+size_t hmm_embedding_emissions_grad_wide_workspace_bytes(int b, int L, int d, int rows, int q);
+int hmm_embedding_emissions_grad_wide(const float *emb, long long ld, int b, int L, int d,
+                                      const float *mean, const float *inv_std, const float *log_norm, int rows,
+                                      const int *state_row, int q, float inv_temperature, float add,
+                                      const float *E_in /* (b,L,q) or NULL */, const float *dE /* (b,L,q) */,
+                                      float *dE_in /* (b,L,q) or NULL */,
+                                      float *demb, long long ldd /* or NULL */,
+                                      float *dmean, float *dinv_std /* (rows,d) */, float *dlog_norm /* (rows) */,
+                                      void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Per-kernel timing for the roofline report (bench.py): the same computation as
  * hmm_posterior with every kernel launch bracketed by HIP events recorded on `stream`.
  * hmm_profile_read() waits for the recorded events, returns the summed milliseconds and
