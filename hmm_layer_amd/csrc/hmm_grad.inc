@@ -101,12 +101,15 @@ __device__ __forceinline__ void grad_backward_body(const float *__restrict__ A, 
             const bool act = j * SUB + s < tl.len;
             // posterior mass on components the forward cell's clamp made (the sequence's first row has no prediction)
             if (psi_acc && !(tl.first && j == 0 && s == 0)) ps = fmaf(flagged_dot(fa[s], Rv), act ? inv : 0.f, ps);
-            // d loglik / d E: gamma / E, nothing where the cell clamped E (or in padded states)
+            // d loglik / d E: gamma / E, nothing where the cell clamped E (or in padded states).  The sequence's
+            // first row keeps w gamma_0 / eps in its clamped entries: dpi = w gamma_0 / pi is read off that row, and
+            // a clamped emission takes the gradient from E, not from pi; k_grad_pi zeroes them once it has read them
+            const bool row0 = tl.first && j == 0 && s == 0;
             f4 de = gm * (inv * wch) * rcp4(e[s]);
-            de.x = e[s].x > eps ? de.x : 0.f;
-            de.y = e[s].y > eps ? de.y : 0.f;
-            de.z = e[s].z > eps ? de.z : 0.f;
-            de.w = e[s].w > eps ? de.w : 0.f;
+            de.x = (e[s].x > eps || (row0 && 4 * g + 0 < q)) ? de.x : 0.f;
+            de.y = (e[s].y > eps || (row0 && 4 * g + 1 < q)) ? de.y : 0.f;
+            de.z = (e[s].z > eps || (row0 && 4 * g + 2 < q)) ? de.z : 0.f;
+            de.w = (e[s].w > eps || (row0 && 4 * g + 3 < q)) ? de.w : 0.f;
             stage_row(os, n, g, (j % OUT_GB) * SUB + s, de);
             f4 sf = e[s] * Rv;
             float S = col_sum(hsum(sf));
@@ -299,16 +302,19 @@ __global__ __launch_bounds__(256) void k_grad_sum2(const double *__restrict__ gr
     if (i < q && j < q) dA[((size_t)m * q + i) * q + j] = (float)acc;
 }
 
-// dpi[j] = sum_b gamma_0[j] w / pi[j], read back from the first row of dE (= w gamma_0 / E_0).
+// dpi[j] = sum_b gamma_0[j] w / pi[j], read back from the first row of dE (= w gamma_0 / max(E_0, eps), in clamped
+// entries too: those are zeroed here, clamped emissions get no gradient).
 __global__ __launch_bounds__(64) void k_grad_pi(const float *__restrict__ pi, const float *__restrict__ E,
-                                                const float *__restrict__ dE, int b, int L, int q, float eps,
+                                                float *__restrict__ dE, int b, int L, int q, float eps,
                                                 float *__restrict__ dpi) {
     // one wave per (model, state): lane s takes sequences s, s + 64, ..., fixed butterfly over the 64 partials
     const int m = blockIdx.y, j = blockIdx.x;
     double acc = 0.0;
     for (int s = threadIdx.x; s < b; s += 64) {
         const size_t o = ((size_t)m * b + s) * (size_t)L * q + j;
-        acc += (double)dE[o] * (double)fmaxf(E[o], eps);
+        const float e = E[o];
+        acc += (double)dE[o] * (double)fmaxf(e, eps);
+        if (!(e > eps)) dE[o] = 0.f;
     }
     for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
     if (threadIdx.x == 0) {

@@ -393,7 +393,7 @@ extern "C" int hmm_loglik_grad_large(const float *A, const float *pi, const floa
         gl_walk(A, pi, E, k, b, L, q, eps, grad_loglik, dA, dE, ll, (float *)(ws + g.o_gpart), st);
     else
         gl_gemm(A, pi, E, k, b, L, q, eps, grad_loglik, dA, dE, g, ws, st);
-    hipLaunchKernelGGL(k_mq_grad_pi, dim3(q, k), dim3(64), 0, st, pi, E, (const float *)dE, b, L, q, eps, dpi);
+    hipLaunchKernelGGL(k_mq_grad_pi, dim3(q, k), dim3(64), 0, st, pi, E, dE, b, L, q, eps, dpi);
     if (loglik)
         hipLaunchKernelGGL(k_copy_loglik, dim3((k * b + 255) / 256), dim3(256), 0, st, (const double *)ll, loglik, k * b);
     return check_launch();

@@ -617,7 +617,8 @@ __global__ __launch_bounds__(64) void k_mq_backward_grad(const float *__restrict
         const float g = act ? al * rb : 0.f;
         const float Sg = mq_wave_sum(g);
         const float ig = __builtin_amdgcn_rcpf(Sg);
-        if (act) o[(size_t)t * q + i] = eraw > eps ? g * (ig * w) * __builtin_amdgcn_rcpf(e) : 0.f;
+        // (position 0 keeps w gamma_0 / eps in its clamped entries for k_mq_grad_pi, which zeroes them)
+        if (act) o[(size_t)t * q + i] = (eraw > eps || t == 0) ? g * (ig * w) * __builtin_amdgcn_rcpf(e) : 0.f;
         if (t < L - 1) {                                    // transition (t -> t + 1): row i of sum xi / A
             const float coef = act ? al * (ig * w) : 0.f;
             MqDenseLoop<QB, 0>::outer(bd, coef, grow);
@@ -659,16 +660,20 @@ __global__ __launch_bounds__(64) void k_mq_grad_sum(const float *__restrict__ gp
     if (threadIdx.x == 0) dA[(size_t)m * q * q + e] = (float)acc;
 }
 
-// dpi[j] = sum_s dE[s,0,j] * max(E[s,0,j], eps) / pi[j]  (= sum_s w gamma_0 / pi), fixed order
+// dpi[j] = sum_s dE[s,0,j] * max(E[s,0,j], eps) / pi[j]  (= sum_s w gamma_0 / pi), fixed order.  The sweeps leave
+// w gamma_0 / eps in the clamped entries of position 0 (a clamped emission takes the gradient from E, not from pi);
+// they are zeroed here.
 __global__ __launch_bounds__(64) void k_mq_grad_pi(const float *__restrict__ pi, const float *__restrict__ E,
-                                                   const float *__restrict__ dE, int b, int L, int q, float eps,
+                                                   float *__restrict__ dE, int b, int L, int q, float eps,
                                                    float *__restrict__ dpi) {
     // one wave per (model, state): lane s takes sequences s, s + 64, ..., fixed butterfly over the 64 partials
     const int m = blockIdx.y, j = blockIdx.x;
     double acc = 0.0;
     for (int s = threadIdx.x; s < b; s += 64) {
         const size_t off = ((size_t)m * b + s) * (size_t)L * q + j;
-        acc += (double)dE[off] * (double)fmaxf(E[off], eps);
+        const float e = E[off];
+        acc += (double)dE[off] * (double)fmaxf(e, eps);
+        if (!(e > eps)) dE[off] = 0.f;
     }
     for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
     if (threadIdx.x == 0) {
@@ -710,7 +715,7 @@ static int mq_loglik_grad_run(const float *A, const float *pi, const float *E, i
     else
         hipLaunchKernelGGL((k_mq_backward_grad<64>), grid, dim3(64), 0, st, A, E, b, L, q, eps, gw, dE, gpart, need);
     hipLaunchKernelGGL(k_mq_grad_sum, dim3(q * q, k), dim3(64), 0, st, (const float *)gpart, dA, b, q);
-    hipLaunchKernelGGL(k_mq_grad_pi, dim3(q, k), dim3(64), 0, st, pi, E, (const float *)dE, b, L, q, eps, dpi);
+    hipLaunchKernelGGL(k_mq_grad_pi, dim3(q, k), dim3(64), 0, st, pi, E, dE, b, L, q, eps, dpi);
     if (loglik)
         hipLaunchKernelGGL(k_copy_loglik, dim3((k * b + 255) / 256), dim3(256), 0, st, (const double *)ll, loglik, k * b);
     return check_launch();

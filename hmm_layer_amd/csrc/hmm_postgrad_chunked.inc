@@ -764,7 +764,8 @@ __global__ __launch_bounds__(64) void k_pc_llgrad(const float *__restrict__ A, c
         const float g = x < q ? al * rb : 0.f;
         const float ig = __builtin_amdgcn_rcpf(PcW<W>::sum(g));
         if (on) phis += ig;
-        if (on && act) dE[base + (size_t)t * q + x] = eraw > eps ? g * (ig * w) * __builtin_amdgcn_rcpf(e) : 0.f;
+        // (position 0 keeps w gamma_0 / eps in its clamped entries for k_mq_grad_pi, which zeroes them)
+        if (on && act) dE[base + (size_t)t * q + x] = (eraw > eps || t == 0) ? g * (ig * w) * __builtin_amdgcn_rcpf(e) : 0.f;
         // transition (t -> t + 1): row x of sum xi / A; nothing flows through a clamped predicted state of t + 1
         const float e1 = has ? fmaxf(en, eps) : 1.f, rb1 = has ? __builtin_fabsf(rn) : 1.f;
         const float sb = x < q ? e1 * rb1 : 0.f;

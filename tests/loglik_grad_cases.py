@@ -1,0 +1,413 @@
+"""Inputs and norms of the oracle sweep of hmm_loglik_grad for 1..64 states, on its four routes:
+
+  scan16  q <= 16, per chunk of the scan plan (csrc/hmm_grad.inc: k_backward_grad<false>, k_window_grad, the serial
+          plan k_backward_grad<true>, k_grad_sum1/2, k_grad_pi)
+  wave    17..64 states, one wave per sequence (csrc/hmm_midq.inc: mq_forward_signed, k_mq_backward_grad<32|48|64>,
+          k_mq_grad_sum, k_mq_grad_pi), HMM_OPT_PGCHUNK = 0
+  pc29    the compiled two-copy gene topology per chunk (pc_loglik_grad), HMM_OPT_PGCHUNK = 2
+  gscan   hmm_loglik_grad_scan on the wave route's inputs, at least two chunks
+
+Test infrastructure; imports neither the engine nor a GPU.  tests/test_loglik_grad_sweep_cpu.py proves from the fp64
+oracle alone that these inputs can carry the comparison; tests/test_loglik_grad_sweep_gpu.py runs the kernels on them.
+
+A case is a Spec; build(spec) -> dict(A (k,q,q), pi (k,q), E (k,b,L,q), w (k,b) or None) float32, deterministic; the
+inputs depend on (models, q, b, L, emis, w, seed) alone, so a gscan case shares the arrays of its wave case.
+reference(spec) -> per model oracle.textbook.loglik_grad / loglik in fp64 and the error of the fp32 twin
+oracle.ref_cell.loglik_grad (fp32 autograd through the restated reference loop on the CPU), cached and read-only.
+
+Tensor norms (tests/test_grad_gpu.py::check restated; each reported as worst err / tolerance, <= 1 passes):
+  dA         present edges (A > 0): 2e-4 max|want|
+  dA/absent  absent edges: |g64(no clamp mask) - g64| + 5e-3 max|want|  (that module's docstring)
+  dpi        2e-4 max|want|
+  dE         2e-5 max|want| + 1e-4 |entry|
+  ll         1e-6 |ll| + 2e-4
+Finer norms (as in tests/postgrad_mid_cases.py):
+  dA/row     row i over its present edges / max|want| over those edges, worst i
+  dE/seq     max over (t, j) of |err| in sequence s / max|want| in sequence s, worst s
+  dE/col     the same per state column j — on the wave route only
+with the limit max(2e-4, 4 e32) per case, model and norm, e32 being the twin's own error under that norm: the factor 4
+pays for the kernel's approximate reciprocals (v_rcp_f32, 1 ulp) and its different summation order.  Nothing in a limit
+comes from engine output.
+
+dE/col is left off the three scan routes: their chunk-boundary vectors carry floor-level entries (~1e-16) with
+absolute, not relative, accuracy (tests/test_grad_gpu.py docstring), so a column that lives at the floor says nothing
+there.
+
+Exclusions, decided from the fp64 reference alone: a row, column or sequence whose reference scale is below SMALL =
+1e-30 of the tensor's maximum is held to the tensor norm only; on the three scan routes so is the dA row of a state that
+is dead in the reference (scaled forward mass <= DEAD = 1e-10 at every position of every sequence of the case).  At most
+5 % of a case's rows (those that have a present edge at all), columns or sequences may be excluded, and 4 e32 <= 1e-3
+in every case and norm (asserted by the CPU test).
+"""
+import collections
+import functools
+import os
+import sys
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+import numpy as np
+import torch
+
+from oracle import params, ref_cell, textbook
+
+from postgrad_mid_cases import copies_of, forward_backward64, forward_clamp_model, gene_model, rand_model
+
+EPS = 1e-16
+SMALL = 1e-30
+DEAD = 1e-10
+FINE_FLOOR, FINE_FACTOR, FINE_CAP = 2e-4, 4.0, 1e-3
+SMALL_CAP = 0.05
+TENSOR_NORMS = ("dA", "dA/absent", "dpi", "dE", "ll")
+ROUTES = ("scan16", "wave", "pc29", "gscan")
+SCAN_ROUTES = ("scan16", "pc29", "gscan")
+
+# route: see above.  models: tuple of "dense" | "sparse" (rand_model, primitive) | "tinypi" (sparse, two pi entries
+# below eps) | "deadin" (sparse, three states nothing enters, two pi entries below eps) | "gene" (7 states: the simple
+# topology; 1 + 14 c states: the c-copy model with its own initial distribution) | "fclamp" | "shipped" (the reference's
+# reducible 15-state matrix as its constructor produces it).  emis: "holes" | "blank0" | "rare" | "dead" | "clamp" |
+# "stretch".
+# w: "wide" (+-10^U(-3,3)) | "zeros" (wide, three sequences 0) | "none".  chunk: HMM_OPT_CHUNK (0: the engine's own).
+Spec = collections.namedtuple("Spec", "route models q b L emis w chunk seed")
+
+
+def spec_id(s):
+    return "%s-%s-q%d-b%d-L%d-%s-%s-c%d" % (s.route, "+".join(s.models), s.q, s.b, s.L, s.emis, s.w, s.chunk)
+
+
+def fine_norms(route):
+    return ("dA/row", "dE/seq", "dE/col") if route == "wave" else ("dA/row", "dE/seq")
+
+
+@functools.lru_cache(maxsize=None)
+def gene7():
+    """The 7-state gene topology (Ir, three introns, three exon phases) with length-based transition probabilities."""
+    ed = params.edges_simple()
+    A = params.dense_A(ed, params.init_logits(ed, 1, 200, 4500, 10000), 7).numpy().astype(np.float32)
+    pi = np.full(7, 1 / 7, dtype=np.float32)
+    A.flags.writeable = pi.flags.writeable = False
+    return A, pi
+
+
+@functools.lru_cache(maxsize=None)
+def shipped15():
+    with np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "transitioner.npz")) as z:
+        A = z["A15_as_shipped"].astype(np.float32)
+    pi = np.full(15, 1 / 15, dtype=np.float32)
+    A.flags.writeable = pi.flags.writeable = False
+    return A, pi
+
+
+STRETCH_STATE, STRETCH_SEQ, STRETCH_LEN = 9, 1, 4            # EI1 of the 15-state model: left after one step
+
+
+def build_model(rng, name, q):
+    if name == "gene":
+        return gene7() if q == 7 else gene_model(copies_of(q))
+    if name == "shipped":
+        assert q == 15
+        return shipped15()
+    if name == "fclamp":
+        return forward_clamp_model(rng, q)
+    if name == "deadin":
+        return rand_model(rng, q, sparse=True, dead=3, tiny_pi=2)
+    if name == "tinypi":
+        return rand_model(rng, q, sparse=True, tiny_pi=2)
+    return rand_model(rng, q, sparse=name == "sparse")
+
+
+def build(spec):
+    """Spec -> dict(A, pi, E, w) float32 (read-only; w None for "none"), the same arrays for the same spec in every
+    process and for every route and chunk length."""
+    return _build(spec._replace(route="", chunk=0))
+
+
+@functools.lru_cache(maxsize=None)
+def _build(spec):
+    k, q, b, L = len(spec.models), spec.q, spec.b, spec.L
+    rng = np.random.default_rng([spec.seed, q, b, L])
+    Ms = [build_model(rng, name, q) for name in spec.models]
+    A, pi = np.stack([m[0] for m in Ms]), np.stack([m[1] for m in Ms])
+    E = (rng.random((k, b, L, q)) * 0.9 + 0.05).astype(np.float32)
+    if spec.emis in ("holes", "blank0"):
+        E[..., ::5, q // 3] = 0.0                            # emissions below eps: no gradient there
+    elif spec.emis == "rare":
+        rare = rng.random(E.shape) < 0.2
+        rare[..., :min(7, q - 1)] = False
+        E[rare] = 1e-10                                      # far above eps: nothing is clamped
+    elif spec.emis == "dead":                                # the emitter's magnitude, zeros in the constrained states
+        E = E / np.float32(4096)
+        dead = rng.random(E.shape) < 0.3
+        dead[..., :1 + 6 * copies_of(q)] = False
+        E[dead] = 0.0
+    elif spec.emis == "clamp":
+        for m, name in enumerate(spec.models):
+            if name == "fclamp":
+                E[m, ..., q - 1] = 1.0
+    elif spec.emis == "stretch":                             # four positions in a row that state 9 alone can emit
+        t0 = L // 2
+        E[0, STRETCH_SEQ, t0:t0 + STRETCH_LEN, :] = 0.0
+        E[0, STRETCH_SEQ, t0:t0 + STRETCH_LEN, STRETCH_STATE] = 0.5
+    else:
+        raise ValueError(spec.emis)
+    if spec.w == "none":
+        w = None
+    else:
+        w = (10.0 ** rng.uniform(-3, 3, (k, b)) * rng.choice([-1.0, 1.0], (k, b))).astype(np.float32)
+        if spec.w == "zeros":
+            w[:, [1, b // 2, b - 1]] = 0.0
+        elif spec.w != "wide":
+            raise ValueError(spec.w)
+    if spec.emis == "blank0":                                # the whole first row of each model's heaviest sequence:
+        E[np.arange(k), np.abs(w).argmax(-1), 0, :] = 0.0    # gamma_0 is pi's and R_0's alone, dpi must not lose it
+    out = dict(A=A, pi=pi, E=E, w=w)
+    for v in out.values():
+        if v is not None:
+            v.flags.writeable = False
+    return out
+
+
+def twin(A, pi, E, w):
+    """One model: (dA, dpi, dE, ll) of oracle.ref_cell.loglik_grad, fp32 autograd on the CPU, as fp64 numpy arrays."""
+    n = torch.get_num_threads()
+    torch.set_num_threads(1)                                 # small matmuls: threads only cost
+    try:
+        out = ref_cell.loglik_grad(np.array(A)[None], np.array(pi)[None], np.array(E)[None],
+                                   None if w is None else np.array(w)[None])
+        # (L = 1: A takes no part, autograd leaves its gradient unset)
+        return tuple(np.zeros(np.shape(A)) if t is None else np.asarray(t.numpy()[0], np.float64) for t in out)
+    finally:
+        torch.set_num_threads(n)
+
+
+def oracle64(A, pi, E, w, unmasked=True, grads=None):
+    """One model: dict(want=(dA, dpi, dE, ll) fp64, dA_unmasked (None unless asked for), dead=(q,) bool), read-only.
+    grads: textbook.loglik_grad(A, pi, E, w) where the caller has it already."""
+    dA, dpi, dE = grads or textbook.loglik_grad(A, pi, E, w)
+    dAu = textbook.loglik_grad(A, pi, E, w, clamp_adjoint=False)[0] if unmasked else None
+    ah, ll = textbook.forward(A, pi, E)
+    r = dict(want=(dA, dpi, dE, ll[:, -1].copy()), dA_unmasked=dAu, dead=ah.max((0, 1)) <= DEAD)
+    for x in r["want"] + (r["dead"],) + (() if dAu is None else (dAu,)):
+        x.flags.writeable = False
+    return r
+
+
+def with_twin(r, A, pi, E, w, route):
+    """oracle64's entry plus e32={norm: the fp32 twin's error}, limit={fine norm: limit}, small={fine norm: fraction
+    excluded} under the route's norms and exclusions."""
+    e32, small = errors(twin(A, pi, E, w), r, A, route, tensor=r["dA_unmasked"] is not None)
+    limit = {n: max(FINE_FLOOR, FINE_FACTOR * e32[n]) for n in fine_norms(route)}
+    return dict(r, e32=e32, limit=limit, small=small)
+
+
+def fine_check(got, A, pi, E, w, route, tag, grads=None):
+    """For tests with inputs of their own: (dA, dpi, dE, ll) of one model under the route's finer norms against the
+    fp64 oracle, each at max(2e-4, 4 e32) with e32 measured on these very inputs; prints, then asserts."""
+    r = with_twin(oracle64(A, pi, E, w, unmasked=False, grads=grads), A, pi, E, w, route)
+    err, _ = errors(got, r, A, route, tensor=False)
+    for n in fine_norms(route):
+        print("LLSWEEP %s %s err %.3e limit %.3e e32 %.3e" % (tag, n, err[n], r["limit"][n], r["e32"][n]))
+    bad = [(n, err[n], r["limit"][n]) for n in fine_norms(route) if not err[n] <= r["limit"][n]]
+    assert not bad, (tag, bad)
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(spec):
+    c = build(spec)
+    return [oracle64(c["A"][m], c["pi"][m], c["E"][m], None if c["w"] is None else c["w"][m])
+            for m in range(len(spec.models))]
+
+
+@functools.lru_cache(maxsize=None)
+def reference(spec):
+    """-> list over the models of dict(want=(dA, dpi, dE, ll) fp64, dA_unmasked, dead=(q,) bool, e32={norm: the fp32
+    twin's error}, limit={fine norm: limit}, small={fine norm: fraction excluded}); computed once, read-only.  The
+    fp64 part is shared between the routes that share inputs; norms and exclusions are the route's own."""
+    c = build(spec)
+    return [with_twin(r, c["A"][m], c["pi"][m], c["E"][m], None if c["w"] is None else c["w"][m], spec.route)
+            for m, r in enumerate(_reference(spec._replace(route="", chunk=0)))]
+
+
+def _worst(err, tol):
+    """max of err / tol; an entry with tol == 0 passes only if its err is 0."""
+    err, tol = np.broadcast_arrays(np.asarray(err, np.float64), np.asarray(tol, np.float64))
+    if err.size == 0:
+        return 0.0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = np.where(tol > 0, err / tol, np.where(err > 0, np.inf, 0.0))
+    return float(r.max())
+
+
+def _ratio(err, scale, top, has=None, keep=None):
+    """max of err / scale over the entries `has` names (default: all) whose scale is at least SMALL * top and that
+    `keep` keeps; the fraction of the named entries that are left out."""
+    has = np.ones(scale.shape, bool) if has is None else has
+    ok = has & (scale >= SMALL * top) & (scale > 0)
+    if keep is not None:
+        ok &= keep
+    left_out = float((has & ~ok).sum()) / max(int(has.sum()), 1)
+    if top == 0.0 or not ok.any():
+        return 0.0, left_out
+    return float((err[ok] / scale[ok]).max()), left_out
+
+
+def errors(got, ref_m, A, route, tensor=True):
+    """(dA, dpi, dE, ll) of one model against oracle64's entry -> ({norm: error}, {fine norm: fraction excluded}).
+    Tensor norms (unless tensor=False) are err / tolerance (<= 1 passes), fine norms are relative errors."""
+    dA, dpi, dE, ll = (np.asarray(x, np.float64) for x in got)
+    wA, wpi, wE, wll = ref_m["want"]
+    present = np.asarray(A) > 0
+    e, small = {}, {}
+    topA = float(np.abs(wA).max())
+    errA = np.abs(dA - wA)
+    errE, refE = np.abs(dE - wE), np.abs(wE)
+    topE = float(refE.max())
+    if tensor:
+        e["dA"] = _worst(errA[present], 2e-4 * topA)
+        e["dA/absent"] = _worst(errA[~present], (np.abs(ref_m["dA_unmasked"] - wA) + 5e-3 * topA)[~present])
+        e["dpi"] = _worst(np.abs(dpi - wpi), 2e-4 * np.abs(wpi).max())
+        e["dE"] = _worst(errE, 2e-5 * topE + 1e-4 * refE)
+        e["ll"] = _worst(np.abs(ll - wll), 1e-6 * np.abs(wll) + 2e-4)
+    errP, refP = np.where(present, errA, 0.0), np.where(present, np.abs(wA), 0.0)
+    # a row without a present edge has no entry under dA/row; one whose present entries are all exactly 0 in the
+    # reference (L = 1) is held to the tensor norm, which then demands exact zeros
+    keep = ~ref_m["dead"] if route in SCAN_ROUTES else None
+    e["dA/row"], small["dA/row"] = _ratio(errP.max(-1), refP.max(-1), topA, present.any(-1), keep)
+    if topA == 0.0:
+        small["dA/row"] = 0.0
+    e["dE/seq"], small["dE/seq"] = _ratio(errE.max((1, 2)), refE.max((1, 2)), topE)
+    if route == "wave":
+        e["dE/col"], small["dE/col"] = _ratio(errE.max((0, 1)), refE.max((0, 1)), topE)
+    return e, small
+
+
+def limits(ref_m):
+    return dict({n: 1.0 for n in TENSOR_NORMS}, **ref_m["limit"])
+
+
+# ---- the cases ----------------------------------------------------------------------------------------------------
+WAVE_Q = (17, 31, 32, 33, 47, 48, 49, 63, 64)                # both ends of QB = 32, 48, 64 and idle lanes in each
+GENE_Q = (29, 43, 57)
+SCAN_Q = (1, 2, 3, 4, 5, 8, 9, 12, 13, 15, 16)               # the 4-state register groups of the 16-state tile
+SCAN_GENE_Q = (7, 15)
+SWEEP_B, SWEEP_L = 3, 203                                    # 25 prefetch blocks of MQ_PF = 8 positions, plus 3
+LENGTHS = (1, 2, 7, 8, 9, 15, 16, 17)                        # around one and two prefetch blocks
+LENGTH_MODELS = {32: ("dense", "sparse"), 43: ("gene", "dense"), 64: ("sparse", "dense"),
+                 6: ("dense", "sparse"), 15: ("gene", "dense")}
+BATCHES = (63, 64, 65, 130)                                  # the 64-lane strides of k_mq_grad_sum / k_*grad_pi
+BATCH_L = 24
+GSCAN_Q = (17, 32, 33, 49, 64)
+GSCAN_CHUNK = 16                                             # L = 203: 13 chunks, the last one of 11 positions
+PC29_SHAPES = ((3, 333, 16), (2, 700, 0), (5, 97, 16))
+# The window case: searched on an MI355X at chunk length 16.  L = 40 ... 528 (every L from 500) route the flagged sequence
+# whole, 529-537 in two windows, 538-541 whole again, 542 and above in windows (the input is drawn anew for every L; two
+# windows and their margins walk 24-37 chunks, about as much as such a sequence has).  600 is clear of that boundary.
+WINDOW_L = 600
+WINDOW_CHUNK = 16
+
+# Cases whose default seed does not meet the conditions of tests/test_loglik_grad_sweep_cpu.py, with the first seed of
+# seed + 10, + 20, ... that does.  In the four-copy gene model one row of dA and one column of dE are 1e-7 of their
+# tensors, and 4 e32 of dA/row and dE/col came to 1.6e-3 and 5.6e-3 (seed 1), 6e-3 (11) and 2.5e-2 (21).
+# The two-copy model with a blank first row, seed 7: one row of dA at 4 e32 = 1.2e-3.
+SEEDS = {"wave-gene-q57-b3-L203-holes-wide-c0": 31, "pc29-gene-q29-b3-L97-blank0-wide-c16": 17}
+
+
+def seeded(specs):
+    return [s._replace(seed=SEEDS.get(spec_id(s), s.seed)) for s in specs]
+
+
+def wave_state_sweep():
+    out = []
+    for n, q in enumerate(WAVE_Q):
+        out.append(Spec("wave", ("dense",), q, SWEEP_B, SWEEP_L, "rare" if n % 2 else "holes", "wide", 0, 1))
+        out.append(Spec("wave", ("sparse",), q, SWEEP_B, SWEEP_L, "holes" if n % 2 else "rare", "wide", 0, 1))
+    for q in GENE_Q:
+        for emis in ("holes", "rare", "dead"):
+            out.append(Spec("wave", ("gene",), q, SWEEP_B, SWEEP_L, emis, "wide", 0, 1))
+    return seeded(out)
+
+
+def scan16_state_sweep():
+    out = []
+    for n, q in enumerate(SCAN_Q):
+        out.append(Spec("scan16", ("sparse" if n % 2 else "dense",), q, SWEEP_B, SWEEP_L, "holes", "wide", 0, 1))
+        out.append(Spec("scan16", ("dense" if n % 2 else "sparse",), q, SWEEP_B, SWEEP_L, "rare", "wide", 0, 1))
+    for q in SCAN_GENE_Q:
+        for emis in ("holes", "rare"):
+            out.append(Spec("scan16", ("gene",), q, SWEEP_B, SWEEP_L, emis, "wide", 0, 1))
+    return seeded(out)
+
+
+def state_sweep():
+    return wave_state_sweep() + scan16_state_sweep()
+
+
+def length_sweep():
+    return seeded([Spec("wave" if q > 16 else "scan16", LENGTH_MODELS[q], q, 3, L, "holes", "wide", 0, 2)
+                   for q in (32, 43, 64, 6, 15) for L in LENGTHS])
+
+
+def batch_sweep():
+    return seeded([Spec(route, ("gene", "sparse"), q, b, BATCH_L, "holes", "wide", 0, 4)
+                   for route, q in (("wave", 43), ("scan16", 15)) for b in BATCHES])
+
+
+def weight_cases():
+    out = []
+    for route, q in (("wave", 47), ("scan16", 12)):
+        out.append(Spec(route, ("dense", "sparse"), q, 65, 17, "holes", "zeros", 0, 5))
+        out.append(Spec(route, ("dense", "sparse"), q, 5, 40, "holes", "none", 0, 5))
+        out.append(Spec(route, ("tinypi", "dense"), q, 5, 40, "holes", "wide", 0, 5))
+        out.append(Spec(route, ("dense", "sparse"), q, 5, 40, "blank0", "wide", 0, 5))
+    out.append(Spec("wave", ("deadin",), 47, 3, SWEEP_L, "holes", "wide", 0, 5))
+    return seeded(out)
+
+
+def clamp_cases():
+    return seeded([Spec("wave", ("fclamp",), q, 3, 60, "clamp", "wide", 0, 3) for q in (40, 60)])
+
+
+def window_case():
+    return seeded([Spec("scan16", ("gene",), 15, 3, WINDOW_L, "stretch", "wide", WINDOW_CHUNK, 6)])[0]
+
+
+def shipped_case():
+    """Reducible: the engine's model check sends it whole to the serial plan.  Rare emissions, not holes: a hole in
+    state 5 every fifth position kills the closed class 4 -> 5 -> 6 -> 4 within 15 steps and leaves its dA rows at 1e-16
+    of the tensor, where fp32 autograd itself is off by 1e6 (e32); and L = 100, not 300: by then one absorbing class
+    has won every sequence and the rows of the others are at 1e-10."""
+    return seeded([Spec("scan16", ("shipped",), 15, 7, 100, "rare", "wide", WINDOW_CHUNK, 6)])[0]
+
+
+def pc29_cases():
+    return seeded([Spec("pc29", ("gene",), 29, b, L, "holes", "wide", chunk, 7) for b, L, chunk in PC29_SHAPES]
+                  + [Spec("pc29", ("gene",), 29, 3, 97, "blank0", "wide", 16, 7)])
+
+
+def gscan_cases():
+    src = [s for s in wave_state_sweep() if s.emis == "holes" and (s.q in GSCAN_Q or (s.models[0] == "gene" and s.q != 29))]
+    return [s._replace(route="gscan", chunk=GSCAN_CHUNK) for s in src]
+
+
+def all_specs():
+    return (state_sweep() + length_sweep() + batch_sweep() + weight_cases() + clamp_cases()
+            + [window_case(), shipped_case()] + pc29_cases() + gscan_cases())
+
+
+def primitive(spec):
+    """False for the models whose support the engine's model check sends to the serial plan as a whole."""
+    return not any(n in ("deadin", "shipped", "fclamp") for n in spec.models)
+
+
+def engages(spec):
+    """The clamps a case must engage in the fp64 recursion (per model: set of forward / pi / E)."""
+    out = []
+    for name in spec.models:
+        s = set()
+        if spec.emis in ("holes", "blank0", "dead", "stretch"):
+            s.add("E")
+        if name in ("tinypi", "deadin"):
+            s.add("pi")
+        if name == "fclamp" or (name == "deadin" and spec.L >= 100):
+            s.add("forward")
+        out.append(s)
+    return out

@@ -18,6 +18,7 @@ from hmm_layer_amd import engine
 from oracle import build as obuild
 from oracle import params, textbook
 
+import loglik_grad_cases as lc
 from test_engine_gpu import assert_log_close_in_probability_space, check_all, dev, rand_model, run_post
 from test_engine_gpu import DEV as DEV_
 
@@ -229,6 +230,9 @@ def test_gradients_of_routed_models():
         assert np.abs(dE.cpu().numpy()[0] - rE).max() <= 3e-4 * np.abs(rE).max()
         assert np.abs(dpi.cpu().numpy()[0] - rpi).max() <= 3e-4 * np.abs(rpi).max()
         assert np.all(np.abs(ll.cpu().numpy()[0] - textbook.loglik(A, pi, E)) <= 2e-4 + 1e-6 * L)
+        # ... and per row of dA over its present edges and per sequence of dE (tests/loglik_grad_cases.py)
+        lc.fine_check([t.cpu().numpy()[0] for t in (dA, dpi, dE, ll)], A, pi, E, w, "scan16", "routed model q=%d" % q,
+                      grads=(rA, rpi, rE))
 
 
 def test_one_sequence_per_wave_layout_of_the_serial_plan():
@@ -243,6 +247,7 @@ def test_one_sequence_per_wave_layout_of_the_serial_plan():
     rA, rpi, rE = textbook.loglik_grad(A, pi, E)
     assert np.abs(dA.cpu().numpy()[0] - rA).max() <= 3e-4 * np.abs(rA).max()
     assert np.abs(dE.cpu().numpy()[0] - rE).max() <= 3e-4 * np.abs(rE).max()
+    lc.fine_check([t.cpu().numpy()[0] for t in (dA, dpi, dE, ll)], A, pi, E, None, "scan16", "narrow", grads=(rA, rpi, rE))
 
 
 # ---------------------------------------------------------------- windows: cost proportional to the flagged chunks
@@ -306,6 +311,8 @@ def test_local_impossible_stretch_is_recomputed_in_a_window():
                 assert np.abs(dE.cpu().numpy()[0] - rE).max() <= 3e-4 * np.abs(rE).max()
                 assert np.abs(dpi.cpu().numpy()[0] - rpi).max() <= 3e-4 * np.abs(rpi).max()
                 assert np.all(np.abs(llg.cpu().numpy()[0] - ll64) <= 1e-6 * np.abs(ll64) + 2e-4)
+                lc.fine_check([t.cpu().numpy()[0] for t in (dA, dpi, dE, llg)], A, pi, E, w, "scan16", "windows, chunk 64",
+                              grads=(rA, rpi, rE))
                 with engine.option(engine.OPT_EXACT, engine.EXACT_OFF):
                     sA, _, sE, _ = engine.loglik_grad(dev(A)[None], dev(pi)[None], dev(E)[None], dev(w)[None])
                 assert np.abs(sE.cpu().numpy()[0] - rE).max() > 3e-3 * np.abs(rE).max()        # what the windows repaired
