@@ -30,6 +30,9 @@
 //          a multiply-high and its factor in LDS.  With multiply, E is read and written once.
 // LDS: MV_THREADS * (MV_KS + 4) + rows * (MV_THREADS + 1) floats + q ints: 34 KB for 13 rows, 54 KB at
 // the limit of 32.  No workspace, no atomics, no dependence on the grid: results are deterministic.
+// The load / sum walk is mv_md, shared with the backward (hmm_emitter_mvn_grad.inc) and with the kernels for up to 256
+// states (hmm_emitter_mvn_wide.inc, hmm_emitter_mvn_grad_wide.inc), which run it per block of 32 rows.
+// Compiler figures (gfx950, hipcc -O3): 70 VGPRs, no scratch.
 
 #define MV_MAXQ 64
 #define MV_MAXR 32
@@ -112,6 +115,59 @@ __device__ __forceinline__ void mv_sum_narrow(const float *xrow, const float *__
     }
 }
 
+// srow[q] (clamped), rstart[rows + 1], rlist[q]: states of row r are rlist[rstart[r] .. rstart[r + 1]), ascending
+__device__ __forceinline__ void mv_row_lists(const int *__restrict__ state_row, int q, int rows, int *srow, int *rstart,
+                                              int *rlist, int tid) {
+    for (int j = tid; j < q; j += MV_THREADS) {
+        const int r = state_row[j];
+        srow[j] = r < 0 ? 0 : (r < rows ? r : rows - 1);
+    }
+    __syncthreads();
+    for (int r = tid; r <= rows; r += MV_THREADS) {
+        int n = 0;
+        for (int j = 0; j < q; ++j) n += srow[j] < r;
+        rstart[r] = n;
+        if (r < rows)
+            for (int j = 0; j < q; ++j)
+                if (srow[j] == r) rlist[n++] = j;
+    }
+    __syncthreads();
+}
+
+// The walk over the d columns of tile P0 for rows [r0, r0 + nr), shared by the forward and backward kernels of both
+// widths (the 64-state ones pass r0 = 0, nr = rows): md into fs[0 .. nr)[tid].  pre holds the tile's first slice on
+// entry and the first slice of tile Pnext (if Pnext >= 0) on exit.
+__device__ __forceinline__ void mv_md(const float *__restrict__ emb, long long ld, long long npos, int d,
+                                       const float *__restrict__ mean, const float *__restrict__ inv_std, int r0, int nr,
+                                       long long P0, long long Pnext, MvSlice &pre, float *xs, float *fs, int tid) {
+    const int nslices = (d + MV_KS - 1) / MV_KS;
+    const float *mb = mean + (size_t)r0 * d, *sb = inv_std + (size_t)r0 * d;
+    for (int sl = 0; sl < nslices; ++sl) {
+        const int k0 = mv_k0(sl, d), skip = sl * MV_KS - k0;
+        __syncthreads();                                  // the previous slice's readers / the previous item's flush are done
+#pragma unroll
+        for (int i = 0; i < MV_KS / 4; ++i) {
+            const int ch = tid + i * MV_THREADS;
+            *reinterpret_cast<f4 *>(xs + (ch / (MV_KS / 4)) * MV_XS + 4 * (ch % (MV_KS / 4))) = pre.v[i];
+        }
+        __syncthreads();
+        // one slice ahead: the next slice of this tile, or the first of tile Pnext.  One call site on purpose: with one
+        // per case the compiler keeps both sets of row addresses alive, which costs k_embedding_emissions a wave per SIMD
+        const bool last = sl + 1 == nslices;
+        if (!last || Pnext >= 0) pre = mv_load(emb, ld, npos, d, last ? Pnext : P0, last ? 0 : mv_k0(sl + 1, d), tid);
+
+        float xr[MV_KS];
+#pragma unroll
+        for (int i = 0; i < MV_KS / 4; ++i) {
+            const f4 v = *reinterpret_cast<const f4 *>(xs + tid * MV_XS + 4 * i);
+            xr[4 * i] = v.x; xr[4 * i + 1] = v.y; xr[4 * i + 2] = v.z; xr[4 * i + 3] = v.w;
+        }
+        if (d < MV_KS) mv_sum_narrow(xs + tid * MV_XS, mb, sb, d, nr, fs + tid);
+        else if (skip == 0) mv_sum<false>(xr, mb + k0, sb + k0, d, nr, 0, fs + tid, sl == 0);
+        else mv_sum<true>(xr, mb + k0, sb + k0, d, nr, skip, fs + tid, false);
+    }
+}
+
 __global__ __launch_bounds__(MV_THREADS) void k_embedding_emissions(const float *__restrict__ emb, long long ld,
                                                                     long long npos, int d,
                                                                     const float *__restrict__ mean,
@@ -131,7 +187,6 @@ __global__ __launch_bounds__(MV_THREADS) void k_embedding_emissions(const float 
     }
     // e / q == umulhi(e, ceil(2^32 / q)) for e < 2^14 and 2 <= q <= 64: the excess e * (q - 1) / (q * 2^32) stays below 1/q
     const unsigned qmagic = (unsigned)((0x100000000ull + (unsigned)q - 1u) / (unsigned)q);
-    const int nslices = (d + MV_KS - 1) / MV_KS;
     const long long ntiles = (npos + MV_THREADS - 1) / MV_THREADS;
 
     long long tile = blockIdx.x;
@@ -139,29 +194,8 @@ __global__ __launch_bounds__(MV_THREADS) void k_embedding_emissions(const float 
     MvSlice pre = mv_load(emb, ld, npos, d, tile * MV_THREADS, 0, tid);
     for (; tile < ntiles; tile += gridDim.x) {
         const long long P0 = tile * MV_THREADS;
-        for (int sl = 0; sl < nslices; ++sl) {
-            const int k0 = mv_k0(sl, d), skip = sl * MV_KS - k0;
-            __syncthreads();                              // the previous slice's readers / the previous tile's flush are done
-#pragma unroll
-            for (int i = 0; i < MV_KS / 4; ++i) {
-                const int ch = tid + i * MV_THREADS;
-                *reinterpret_cast<f4 *>(xs + (ch / (MV_KS / 4)) * MV_XS + 4 * (ch % (MV_KS / 4))) = pre.v[i];
-            }
-            __syncthreads();
-            // one slice ahead: the next slice of this tile, or the first of this workgroup's next tile
-            if (sl + 1 < nslices) pre = mv_load(emb, ld, npos, d, P0, mv_k0(sl + 1, d), tid);
-            else if (tile + gridDim.x < ntiles) pre = mv_load(emb, ld, npos, d, (tile + gridDim.x) * MV_THREADS, 0, tid);
-
-            float xr[MV_KS];
-#pragma unroll
-            for (int i = 0; i < MV_KS / 4; ++i) {
-                const f4 v = *reinterpret_cast<const f4 *>(xs + tid * MV_XS + 4 * i);
-                xr[4 * i] = v.x; xr[4 * i + 1] = v.y; xr[4 * i + 2] = v.z; xr[4 * i + 3] = v.w;
-            }
-            if (d < MV_KS) mv_sum_narrow(xs + tid * MV_XS, mean, inv_std, d, rows, fs + tid);
-            else if (skip == 0) mv_sum<false>(xr, mean + k0, inv_std + k0, d, rows, 0, fs + tid, sl == 0);
-            else mv_sum<true>(xr, mean + k0, inv_std + k0, d, rows, skip, fs + tid, false);
-        }
+        mv_md(emb, ld, npos, d, mean, inv_std, 0, rows, P0, tile + gridDim.x < ntiles ? (tile + gridDim.x) * MV_THREADS : -1, pre,
+              xs, fs, tid);
         // md -> f, in place (lane p owns column p of fs)
 #pragma unroll 1
         for (int r = 0; r < rows; ++r)

@@ -22,7 +22,7 @@
 // next to one row's far-from-zero mean, and it is that row's gradient that matters).
 //
 // Two kernels and a small sum, because the two halves want opposite layouts:
-//   k_embedding_emissions_grad_w     lane = position.  The forward's tile walk (mv_load / mv_sum, unchanged) gives
+//   k_embedding_emissions_grad_w     lane = position.  The forward's tile walk (mv_md, unchanged) gives
 //        md, then g, in LDS.  The tile of dE (and E_in) is walked flat in 16-byte pieces: dE_in leaves at once,
 //        dE * E_in is parked in LDS (the slice stage is free by then; row stride q | 1).  Lane p then folds its
 //        position's states into rows in ascending state order and writes W[p][0 .. RS) (RS = rows rounded up
@@ -68,48 +68,14 @@ __global__ __launch_bounds__(MV_THREADS) void k_embedding_emissions_grad_w(
     const long long ntiles = (npos + MV_THREADS - 1) / MV_THREADS;
     long long tile = blockIdx.x;
     if (tile >= ntiles) return;
-    if (tid < q) {
-        const int r = state_row[tid];
-        srow[tid] = r < 0 ? 0 : (r < rows ? r : rows - 1);
-    }
-    __syncthreads();
-    if (tid <= rows) {
-        int n = 0;
-        for (int j = 0; j < q; ++j) n += srow[j] < tid;
-        rstart[tid] = n;
-        if (tid < rows)
-            for (int j = 0; j < q; ++j)
-                if (srow[j] == tid) rlist[n++] = j;
-    }
+    mv_row_lists(state_row, q, rows, srow, rstart, rlist, tid);
     const unsigned qmagic = (unsigned)((0x100000000ull + (unsigned)q - 1u) / (unsigned)q);   // as in the forward
-    const int nslices = (d + MV_KS - 1) / MV_KS;
 
     MvSlice pre = mv_load(emb, ld, npos, d, tile * MV_THREADS, 0, tid);
     for (; tile < ntiles; tile += gridDim.x) {
         const long long P0 = tile * MV_THREADS;
-        // md: the forward's walk
-        for (int sl = 0; sl < nslices; ++sl) {
-            const int k0 = mv_k0(sl, d), skip = sl * MV_KS - k0;
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < MV_KS / 4; ++i) {
-                const int ch = tid + i * MV_THREADS;
-                *reinterpret_cast<f4 *>(xs + (ch / (MV_KS / 4)) * MV_XS + 4 * (ch % (MV_KS / 4))) = pre.v[i];
-            }
-            __syncthreads();
-            if (sl + 1 < nslices) pre = mv_load(emb, ld, npos, d, P0, mv_k0(sl + 1, d), tid);
-            else if (tile + gridDim.x < ntiles) pre = mv_load(emb, ld, npos, d, (tile + gridDim.x) * MV_THREADS, 0, tid);
-
-            float xr[MV_KS];
-#pragma unroll
-            for (int i = 0; i < MV_KS / 4; ++i) {
-                const f4 v = *reinterpret_cast<const f4 *>(xs + tid * MV_XS + 4 * i);
-                xr[4 * i] = v.x; xr[4 * i + 1] = v.y; xr[4 * i + 2] = v.z; xr[4 * i + 3] = v.w;
-            }
-            if (d < MV_KS) mv_sum_narrow(xs + tid * MV_XS, mean, inv_std, d, rows, fs + tid);
-            else if (skip == 0) mv_sum<false>(xr, mean + k0, inv_std + k0, d, rows, 0, fs + tid, sl == 0);
-            else mv_sum<true>(xr, mean + k0, inv_std + k0, d, rows, skip, fs + tid, false);
-        }
+        mv_md(emb, ld, npos, d, mean, inv_std, 0, rows, P0, tile + gridDim.x < ntiles ? (tile + gridDim.x) * MV_THREADS : -1, pre,
+              xs, fs, tid);
         // md -> g, in place
 #pragma unroll 1
         for (int r = 0; r < rows; ++r)

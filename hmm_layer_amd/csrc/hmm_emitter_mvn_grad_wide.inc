@@ -14,7 +14,7 @@
 // None of the 64-state layouts stretches to 256 rows (a 256 x (q | 1) stage of dE * E_in, three accumulators per
 // row in registers).  Four kernels:
 //   k_embedding_emissions_grad_w_wide   lane = position; work item = (tile of 256 positions, block of 32 rows), as
-//        the wide forward (mvw_md gives md, then g, of the block's rows in LDS).  The block's states — a contiguous
+//        the wide forward (mv_md gives md, then g, of the block's rows in LDS).  The block's states — a contiguous
 //        piece of the row-sorted state list — are taken 32 at a time: lane (position e / 32, entry e % 32) reads dE
 //        (and E_in), writes dE_in and parks dE * E_in in LDS (row stride 33; the slice stage is free by then);
 //        then lane p adds its position's entries in list order, that is row by row and in ascending state order
@@ -60,7 +60,7 @@ __global__ __launch_bounds__(MV_THREADS) void k_embedding_emissions_grad_w_wide(
     const long long nitems = ntiles * nrb;
     long long item = blockIdx.x;
     if (item >= nitems) return;
-    mvw_row_lists(state_row, q, rows, srow, rstart, rlist, tid);
+    mv_row_lists(state_row, q, rows, srow, rstart, rlist, tid);
 
     MvSlice pre = mv_load(emb, ld, npos, d, (item / nrb) * MV_THREADS, 0, tid);
     for (; item < nitems; item += gridDim.x) {
@@ -68,7 +68,7 @@ __global__ __launch_bounds__(MV_THREADS) void k_embedding_emissions_grad_w_wide(
         const int r0 = (int)(item % nrb) * MVW_RB;
         const int nr = rows - r0 < MVW_RB ? rows - r0 : MVW_RB;
         const long long nxt = item + gridDim.x;
-        mvw_md(emb, ld, npos, d, mean, inv_std, r0, nr, P0, nxt < nitems ? (nxt / nrb) * MV_THREADS : -1, pre, xs, fs, tid);
+        mv_md(emb, ld, npos, d, mean, inv_std, r0, nr, P0, nxt < nitems ? (nxt / nrb) * MV_THREADS : -1, pre, xs, fs, tid);
         // md -> g, in place
 #pragma unroll 1
         for (int r = 0; r < nr; ++r)

@@ -1,6 +1,6 @@
 // hmm_emitter_mvn_wide.inc — the embedding-emission factor (hmm_emitter_mvn.inc) for up to 256 states and 256
 // kernel rows: the gene models of three to eighteen copies.  Included by hmm_engine.hip after hmm_emitter_mvn.inc,
-// whose helpers (mv_load, mv_k0, mv_sum, mv_sum_narrow) it calls unchanged.  Same arguments, layouts and formulas:
+// whose helpers (mv_load, mv_md, mv_row_lists) it calls unchanged.  Same arguments, layouts and formulas:
 //
 //   md[p][r] = sum_c ((x[p][c] - mean[r][c]) * inv_std[r][c])^2
 //   f[p][j]  = exp(inv_temperature * (log_norm[r] - 0.5 md[p][r])) + add,   r = state_row[j]
@@ -32,56 +32,6 @@
 #define MVW_SC 32                     // states per chunk of the flush
 #define MVW_MAXGRID 1024
 
-// srow[q] (clamped), rstart[rows + 1], rlist[q]: states of row r are rlist[rstart[r] .. rstart[r + 1]), ascending
-__device__ __forceinline__ void mvw_row_lists(const int *__restrict__ state_row, int q, int rows, int *srow, int *rstart,
-                                              int *rlist, int tid) {
-    for (int j = tid; j < q; j += MV_THREADS) {
-        const int r = state_row[j];
-        srow[j] = r < 0 ? 0 : (r < rows ? r : rows - 1);
-    }
-    __syncthreads();
-    for (int r = tid; r <= rows; r += MV_THREADS) {
-        int n = 0;
-        for (int j = 0; j < q; ++j) n += srow[j] < r;
-        rstart[r] = n;
-        if (r < rows)
-            for (int j = 0; j < q; ++j)
-                if (srow[j] == r) rlist[n++] = j;
-    }
-    __syncthreads();
-}
-
-// the forward's walk over the d columns of tile P0 for rows [r0, r0 + nr): md into fs[0 .. nr)[tid].  pre holds the
-// tile's first slice on entry and the first slice of tile Pnext (if Pnext >= 0) on exit.
-__device__ __forceinline__ void mvw_md(const float *__restrict__ emb, long long ld, long long npos, int d,
-                                       const float *__restrict__ mean, const float *__restrict__ inv_std, int r0, int nr,
-                                       long long P0, long long Pnext, MvSlice &pre, float *xs, float *fs, int tid) {
-    const int nslices = (d + MV_KS - 1) / MV_KS;
-    const float *mb = mean + (size_t)r0 * d, *sb = inv_std + (size_t)r0 * d;
-    for (int sl = 0; sl < nslices; ++sl) {
-        const int k0 = mv_k0(sl, d), skip = sl * MV_KS - k0;
-        __syncthreads();                                  // the previous slice's readers / the previous item's flush are done
-#pragma unroll
-        for (int i = 0; i < MV_KS / 4; ++i) {
-            const int ch = tid + i * MV_THREADS;
-            *reinterpret_cast<f4 *>(xs + (ch / (MV_KS / 4)) * MV_XS + 4 * (ch % (MV_KS / 4))) = pre.v[i];
-        }
-        __syncthreads();
-        if (sl + 1 < nslices) pre = mv_load(emb, ld, npos, d, P0, mv_k0(sl + 1, d), tid);
-        else if (Pnext >= 0) pre = mv_load(emb, ld, npos, d, Pnext, 0, tid);
-
-        float xr[MV_KS];
-#pragma unroll
-        for (int i = 0; i < MV_KS / 4; ++i) {
-            const f4 v = *reinterpret_cast<const f4 *>(xs + tid * MV_XS + 4 * i);
-            xr[4 * i] = v.x; xr[4 * i + 1] = v.y; xr[4 * i + 2] = v.z; xr[4 * i + 3] = v.w;
-        }
-        if (d < MV_KS) mv_sum_narrow(xs + tid * MV_XS, mb, sb, d, nr, fs + tid);
-        else if (skip == 0) mv_sum<false>(xr, mb + k0, sb + k0, d, nr, 0, fs + tid, sl == 0);
-        else mv_sum<true>(xr, mb + k0, sb + k0, d, nr, skip, fs + tid, false);
-    }
-}
-
 __global__ __launch_bounds__(MV_THREADS) void k_embedding_emissions_wide(const float *__restrict__ emb, long long ld,
                                                                          long long npos, int d,
                                                                          const float *__restrict__ mean,
@@ -102,7 +52,7 @@ __global__ __launch_bounds__(MV_THREADS) void k_embedding_emissions_wide(const f
     const long long nitems = ntiles * nrb;
     long long item = blockIdx.x;
     if (item >= nitems) return;
-    mvw_row_lists(state_row, q, rows, srow, rstart, rlist, tid);
+    mv_row_lists(state_row, q, rows, srow, rstart, rlist, tid);
 
     MvSlice pre = mv_load(emb, ld, npos, d, (item / nrb) * MV_THREADS, 0, tid);
     for (; item < nitems; item += gridDim.x) {
@@ -110,7 +60,7 @@ __global__ __launch_bounds__(MV_THREADS) void k_embedding_emissions_wide(const f
         const int r0 = (int)(item % nrb) * MVW_RB;
         const int nr = rows - r0 < MVW_RB ? rows - r0 : MVW_RB;
         const long long nxt = item + gridDim.x;
-        mvw_md(emb, ld, npos, d, mean, inv_std, r0, nr, P0, nxt < nitems ? (nxt / nrb) * MV_THREADS : -1, pre, xs, fs, tid);
+        mv_md(emb, ld, npos, d, mean, inv_std, r0, nr, P0, nxt < nitems ? (nxt / nrb) * MV_THREADS : -1, pre, xs, fs, tid);
         // md -> f, in place (lane p owns column p of fs)
 #pragma unroll 1
         for (int r = 0; r < nr; ++r)

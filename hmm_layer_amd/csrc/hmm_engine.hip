@@ -2883,8 +2883,6 @@ int hmm_loglik_partials(const double *loglik, const float *weights, int k, int b
 #include "hmm_viterbi_large.inc"
 #include "hmm_emitter.inc"
 #include "hmm_emitter_grad.inc"
-#include "hmm_emitter_wide.inc"
-#include "hmm_emitter_grad_wide.inc"
 #include "hmm_emitter_mvn.inc"
 #include "hmm_emitter_mvn_grad.inc"
 #include "hmm_emitter_mvn_wide.inc"

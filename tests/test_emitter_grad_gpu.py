@@ -152,6 +152,27 @@ def test_gradient_at_one_position_stays_there(model, b, L, at):
     assert bool(torch.isfinite(dB).all()) and float(dB.abs().max()) > 0
 
 
+def test_state_row_out_of_range_is_clamped():
+    """The test of the same name in test_emitter_wide_gpu on the 64-state entry points: entries of state_row below 0
+    or from rows on read row 0 / rows - 1 of B, in the forward and in both outputs of the backward."""
+    q, rows, s, nc, b, L = 29, 20, 15, 9, 3, 150
+    g = torch.Generator().manual_seed(5)
+    x = make_inputs(b, L, s, False, g)[0]
+    B = torch.softmax(torch.randn((rows, s), generator=g), -1)
+    row = torch.randint(0, rows, (q,), generator=g, dtype=torch.int32)
+    codon = torch.rand((2, nc, 64), generator=g) * (torch.rand((2, nc, 64), generator=g) < 0.5)
+    cod = torch.randint(-1, nc, (q,), generator=g, dtype=torch.int32)
+    bad_row = row.clone()
+    bad_row[3], bad_row[17], bad_row[28] = -7, 20, 1 << 20
+    row[3], row[17], row[28] = 0, 19, 19
+    dE = torch.randn((b, L, q), generator=g).to(DEV)
+    a = [t.to(DEV) for t in (x, B, row, codon, cod)]
+    bad = [t.to(DEV) for t in (x, B, bad_row, codon, cod)]
+    assert torch.equal(engine.gene_emissions(*a), engine.gene_emissions(*bad))
+    for u, v in zip(engine.gene_emissions_grad(*a, dE), engine.gene_emissions_grad(*bad, dE)):
+        assert torch.equal(u, v)
+
+
 # ------------------------------------------------------------------------------------------------ layer level
 
 def gene_cell(b, L, seed, fused, **kw):

@@ -177,6 +177,30 @@ def test_wide_forward_equals_the_64_state_forward_bit_for_bit(b, L):
 
 # ------------------------------------------------------------------------------------------------ backward
 
+@pytest.mark.parametrize("b,L", [(4, 37), (2, 1100)])
+def test_wide_backward_dx_equals_the_64_state_backward_bit_for_bit(b, L):
+    """29 states: one group, so both kernels run the same chain per position (H, then H Bexp over <NT = 4, KT = 2>).
+    (2, 1100) has several runs, a run border inside a sequence and a ragged last tile.  dB is not compared: the two
+    kernels sum it over runs of different lengths by design."""
+    g = torch.Generator().manual_seed(19 * b + L)
+    em = GenePredHMMEmitter(**CODONS, num_copies=2)
+    em.build((1, b, L, S))
+    with torch.no_grad():
+        em.emission_kernel.copy_(torch.randn(em.emission_kernel.shape, generator=g))
+        Bm = em.make_B()[0].to(DEV).contiguous()
+    row, cod = em.state_tables(torch.device(DEV))
+    codon = em.codon_probs.to(DEV, torch.float32).contiguous()
+    for soft in (False, True):
+        x = make_inputs(b, L, S, soft, g)[0].to(DEV)
+        dE = torch.randn((b, L, em.num_states), generator=g).to(DEV)
+        for add in (0.0, 1e-7):
+            for want_dB in (True, False):
+                wide, _ = engine.gene_emissions_grad_wide(x, Bm, row, codon, cod, dE, add=add, want_dB=want_dB)
+                narrow, _ = engine.gene_emissions_grad(x, Bm, row, codon, cod, dE, add=add, want_dB=want_dB)
+                assert float(wide.abs().max()) > 0
+                assert torch.equal(wide, narrow), (soft, add, want_dB)
+
+
 def torch_grads(em, x, G, training):
     """Autograd through GenePredHMMEmitter.forward with loss = (E G).sum(): (dx, d emission_kernel)."""
     x = x.clone().requires_grad_(True)
