@@ -520,6 +520,24 @@ int hmm_loglik_allreduce(void *comm, double *partial, int k, void *stream);
  *                                     sequence needs the unsharded call (serial exact-clamp kernels).
  * seq_start: 1 on the rank that owns position 0 (r == 0), else 0.  The same workspace (same size query)
  * must be passed to steps 1 and 3: the chunk operators stay in it.
+ * Only the leading q x q block of an operator and the first q entries of its exponent row are defined
+ * (the other rows and columns of the block are zero; the other exponent lanes carry no contract).
+ *
+ * hmm_seqshard_workspace_bytes: a multiple of 256, non-decreasing in R; 0 for q > hmm_scan_max_states(),
+ * for R < 1 and for a bad shape.
+ * Argument checks of hmm_seqshard_reduce and hmm_seqshard_posterior, in this order, all before any HIP
+ * call (tests/test_seqshard_sweep_cpu.py):
+ *   1. q > hmm_scan_max_states()                     HMM_ERR_Q_UNSUPPORTED (-2), ahead of everything, a
+ *                                                    bad shape included
+ *   2. R < 1                                         HMM_ERR_BAD_ARGUMENT  (-6)
+ *   3. k, b, Ls or q < 1 (or k * b > 2^24)           HMM_ERR_BAD_SHAPE     (-1)
+ *   4. hmm_seqshard_posterior only: r outside 0 .. R-1, or (seq_start != 0) != (r == 0), then a mode
+ *      outside HMM_POST_PROB .. HMM_POST_LOG_NO_LL   HMM_ERR_BAD_ARGUMENT  (-6)
+ *   5. a NULL pointer among A, E, slab_op, slab_exp, workspace (reduce) or A, pi, E, all_ops, all_exps,
+ *      out, workspace (posterior; loglik and phi_out may be NULL)
+ *                                                    HMM_ERR_NULL_POINTER  (-3)
+ *   6. workspace_bytes below the size query, or a workspace not aligned to 256 bytes
+ *                                                    HMM_ERR_WORKSPACE     (-4)
  */
 size_t hmm_seqshard_workspace_bytes(int k, int b, int Ls, int q, int R);
 int hmm_seqshard_reduce(const float *A, const float *E, int k, int b, int Ls, int q, float eps, int seq_start,

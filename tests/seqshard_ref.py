@@ -10,9 +10,19 @@ EPS = 1e-16
 
 
 def _rescale(X, ex):
-    s = X.sum(0)
+    """Power-of-two rescale of every column (sum over the rows, axis -2) into [0.5, 1); exact."""
+    s = X.sum(-2)
     e = np.where(s > 0, np.frexp(np.where(s > 0, s, 1.0))[1], 0)
-    return X * np.ldexp(1.0, -e)[None, :], ex + e
+    return X * np.ldexp(1.0, -e)[..., None, :], ex + e
+
+
+def primitive(A, eps=EPS):
+    """The engine's question of a model (k_topo_check): is the support of A (entries > eps) primitive?  If not, the
+    eps clamps decide its posteriors and no slab operator can stand for them: phi = +inf."""
+    P = np.asarray(A) > eps
+    for _ in range(8):                                   # S^256 > 0; Wielandt: (q-1)^2 + 1 = 226 suffices for q = 16
+        P = (P.astype(np.int64) @ P.astype(np.int64)) > 0
+    return bool(P.all())
 
 
 class RefBackend:
@@ -21,18 +31,18 @@ class RefBackend:
         k, b, L, q = E.shape
         op = np.zeros((k, b, 16, 16), np.float32)
         ex = np.zeros((k, b, 16), np.int32)
-        for m in range(k):
-            for s in range(b):
-                X, e = np.eye(q), np.zeros(q, np.int64)
-                for t in range(L):
-                    em = np.maximum(E[m, s, t], EPS)
-                    if t == 0 and seq_start:
-                        X = em[:, None] * X
-                    else:
-                        X = em[:, None] * (A[m].T @ X)
-                    X, e = _rescale(X, e)
-                op[m, s, :q, :q] = X
-                ex[m, s, :q] = e
+        At = np.swapaxes(A, 1, 2)[:, None]                   # every sequence of a model at once
+        X = np.broadcast_to(np.eye(q), (k, b, q, q)).copy()
+        e = np.zeros((k, b, q), np.int64)
+        for t in range(L):
+            em = np.maximum(E[:, :, t], EPS)
+            if t == 0 and seq_start:
+                X = em[..., None] * X
+            else:
+                X = em[..., None] * np.matmul(At, X)
+            X, e = _rescale(X, e)
+        op[..., :q, :q] = X
+        ex[..., :q] = e
         return torch.from_numpy(op), torch.from_numpy(ex)
 
     def posterior(self, A, pi, E_slab, all_ops, all_exps, r, mode):
@@ -47,7 +57,9 @@ class RefBackend:
         phi = np.zeros((k, b), np.float32)
         for m in range(k):
             for s in range(b):
-                X = [ops[m, s, j, :q, :q] * np.ldexp(1.0, exs[m, s, j, :q])[None, :] for j in range(R)]
+                # (columns relative to the slab's largest exponent: a slab of a thousand positions is beyond fp64's range)
+                top = [int(exs[m, s, j, :q].max()) for j in range(R)]
+                X = [ops[m, s, j, :q, :q] * np.ldexp(1.0, exs[m, s, j, :q] - top[j])[None, :] for j in range(R)]
                 # alpha_hat entering slab r, log-likelihood of the whole sequence
                 a, tot = np.maximum(pi[m], EPS), 0.0
                 ent = None
@@ -55,7 +67,7 @@ class RefBackend:
                     if j == r:
                         ent = a.copy()
                     a = X[j] @ a
-                    tot += np.log(a.sum())
+                    tot += np.log(a.sum()) + top[j] * np.log(2.0)
                     a = a / a.sum()
                 # beta leaving slab r
                 v = np.ones(q)
@@ -86,7 +98,7 @@ class RefBackend:
                     bm = u <= EPS
                     Rv = np.maximum(u, EPS)
                 ll[m, s] = tot
-                phi[m, s] = acc
+                phi[m, s] = acc if primitive(A[m]) else np.inf
         return torch.from_numpy(out), torch.from_numpy(ll), torch.from_numpy(phi)
 
     def unsharded(self, A, pi, E, mode):

@@ -1,45 +1,18 @@
 """Sequence-sharded posteriors on ONE GPU: the R time slabs of a batch go through the engine's own
 hmm_seqshard_reduce / hmm_seqshard_posterior one after the other (what R ranks would run side by side), the
-"all-gather" is seqshard.stack_slab_operators on the same device.  Against the unsharded engine call and the
-fp64 oracle."""
+"all-gather" is seqshard.stack_slab_operators on the same device (sharded() of tests/seqshard_cases.py).  Against
+the unsharded engine call and the fp64 oracle.  The sweep over state counts, slab geometries, hard inputs and the slab
+operator itself is tests/test_seqshard_sweep_gpu.py."""
 import numpy as np
 import pytest
-import torch
 
 from hmm_layer_amd import engine, seqshard
 from oracle import params, textbook
 
+from seqshard_cases import sharded
 from test_engine_gpu import dev, rand_model
 
 pytestmark = pytest.mark.gpu
-
-
-def sharded(A, pi, E, cuts, mode=engine.POST_PROB):
-    """A (k,q,q), pi (k,q), E (k,b,L,q) numpy; cuts = slab boundaries.  -> out, loglik per rank, phi summed."""
-    R = len(cuts) - 1
-    Ad, pid = dev(A), dev(pi)
-    slabs = [dev(E[:, :, cuts[r]:cuts[r + 1]].copy()) for r in range(R)]
-    be = seqshard.EngineBackend()
-    # one workspace per "rank": the chunk operators of step 1 have to survive until step 3
-    streams = [torch.cuda.Stream() for _ in range(R)]
-    ops, exs = [], []
-    for r in range(R):
-        with torch.cuda.stream(streams[r]):
-            o, e = be.reduce(Ad, slabs[r], r == 0, R)
-        ops.append(o)
-        exs.append(e)
-    torch.cuda.synchronize()
-    all_ops, all_exps = seqshard.stack_slab_operators(ops, exs)
-    torch.cuda.synchronize()                    # (stacked on the default stream, consumed on the ranks' streams)
-    outs, lls, phi = [], [], 0
-    for r in range(R):
-        with torch.cuda.stream(streams[r]):
-            o, ll, ph = be.posterior(Ad, pid, slabs[r], all_ops, all_exps, r, mode)
-        streams[r].synchronize()
-        outs.append(o.cpu().numpy())
-        lls.append(ll.cpu().numpy())
-        phi = phi + ph.cpu().numpy()
-    return np.concatenate(outs, axis=2), lls, phi
 
 
 @pytest.mark.parametrize("q,b,L,cuts", [(15, 3, 5000, [0, 2500, 5000]), (15, 2, 4001, [0, 1000, 1017, 4001]),
