@@ -143,3 +143,33 @@ class EmbeddingEmissions(torch.autograd.Function):
 def embedding_emissions(E_in, x, mean, inv_std, log_norm, state_row, col0, d, inv_temperature=1.0, add=0.0):
     """Differentiable embedding-emission factor multiplied into E_in (b,L,q) (None: the factor alone)."""
     return EmbeddingEmissions.apply(E_in, x, mean, inv_std, log_norm, state_row, col0, d, inv_temperature, add)
+
+
+class NucleotideEmissions(torch.autograd.Function):
+    """E_out (b,L,q) = E_in * f, f[p][j] = sum_a (x[p][col0+a] + x[p][col0+4] / 4) P[state_nuc[j]][a] on the states
+    with state_nuc[j] >= 0 and 1/4 on the others (E_in None: the factor alone).  Forward = hmm_nucleotide_emissions
+    on a fresh output (E_in survives for the backward), backward = hmm_nucleotide_emissions_grad; one kernel pair
+    serves every model of up to 256 states.  Differentiable in E_in and P; nucleotides are data, the gradient for x
+    is None.  Saved: E_in, x, P and state_nuc — not the factor."""
+
+    @staticmethod
+    def forward(ctx, E_in, x, P, state_nuc, col0):
+        x, P = x.contiguous(), P.contiguous()
+        if E_in is not None:
+            E_in = E_in.contiguous()
+        ctx.save_for_backward(E_in, x, P, state_nuc)
+        ctx.col0 = int(col0)
+        return engine.nucleotide_emissions(x, col0, P, state_nuc, E=None if E_in is None else E_in.clone())
+
+    @staticmethod
+    def backward(ctx, dE):
+        E_in, x, P, state_nuc = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dE_in, dP = engine.nucleotide_emissions_grad(x, ctx.col0, P, state_nuc, dE.to(torch.float32).contiguous(),
+                                                     E_in=E_in, want_dE_in=need[0], want_dP=need[2])
+        return dE_in, None, dP, None, None
+
+
+def nucleotide_emissions(E_in, x, P, state_nuc, col0):
+    """Differentiable trainable-nucleotide factor multiplied into E_in (b,L,q) (None: the factor alone)."""
+    return NucleotideEmissions.apply(E_in, x, P, state_nuc, col0)

@@ -2887,6 +2887,7 @@ int hmm_loglik_partials(const double *loglik, const float *weights, int k, int b
 #include "hmm_emitter_mvn_grad.inc"
 #include "hmm_emitter_mvn_wide.inc"
 #include "hmm_emitter_mvn_grad_wide.inc"
+#include "hmm_emitter_nuc.inc"
 #include "hmm_grad.inc"
 #include "hmm_postgrad.inc"
 #include "hmm_grad_scan.inc"

@@ -111,6 +111,10 @@ _SIGNATURES = {
     "hmm_embedding_emissions_grad_wide_workspace_bytes": (_SZ, [_I] * 5),
     "hmm_embedding_emissions_grad_wide": (_I, [_P, _LL, _I, _I, _I, _P, _P, _P, _I, _P, _I, _F, _F, _P, _P, _P, _P, _LL,
                                                _P, _P, _P, _P, _SZ, _P]),
+    "hmm_nucleotide_emissions_max_states": (_I, []),
+    "hmm_nucleotide_emissions": (_I, [_P, _LL, _I, _I, _P, _I, _P, _I, _F, _I, _P, _P]),
+    "hmm_nucleotide_emissions_grad_workspace_bytes": (_SZ, [_I] * 4),
+    "hmm_nucleotide_emissions_grad": (_I, [_P, _LL, _I, _I, _P, _I, _P, _I, _F, _P, _P, _P, _P, _P, _SZ, _P]),
     "hmm_loglik_partials": (_I, [_P, _P, _I, _I, _P, _P]),
     "hmm_loglik_allreduce": (_I, [_P, _P, _I, _P]),
     "hmm_seqshard_workspace_bytes": (_SZ, [_I] * 5),
@@ -589,6 +593,72 @@ def embedding_emissions_grad_wide(x, col0, d, mean, inv_std, log_norm, state_row
     return _embedding_emissions_grad("hmm_embedding_emissions_grad_wide", "embedding_grad_wide",
                                      "q <= 256, rows <= 256", x, col0, d, mean, inv_std, log_norm, state_row, dE, E_in,
                                      inv_temperature, add, want_dE_in, want_demb, want_tables, dx_out)
+
+
+def _nucleotide_args(x, col0, P, state_nuc):
+    """Validation shared by nucleotide_emissions and nucleotide_emissions_grad -> (the three tensors, col0,
+    (b, L, w, rows, q))."""
+    x, P = _dev(x, "x"), _dev(P, "P")
+    state_nuc = _dev(state_nuc, "state_nuc", torch.int32)
+    if x.dim() != 3:
+        raise ValueError("x must have shape (b, L, w), got %s" % (tuple(x.shape),))
+    b, L, w = x.shape
+    col0 = int(col0)
+    if col0 < 0 or col0 + 5 > w:
+        raise ValueError("columns %d .. %d lie outside x's %d columns" % (col0, col0 + 4, w))
+    if P.dim() != 2 or P.shape[1] != 4:
+        raise ValueError("P must have shape (rows, 4), got %s" % (tuple(P.shape),))
+    rows, q = P.shape[0], state_nuc.numel()
+    limit = lib().hmm_nucleotide_emissions_max_states()
+    if not (1 <= q <= limit and 1 <= rows <= limit):
+        raise ValueError("hmm_nucleotide_emissions covers 1 <= q, rows <= %d (got q = %d, rows = %d)" % (limit, q, rows))
+    return x, P, state_nuc, col0, (b, L, w, rows, q)
+
+
+def nucleotide_emissions(x, col0, P, state_nuc, E=None, free_value=0.25):
+    """Trainable nucleotide factor (hmm_nucleotide_emissions): x (b,L,w) fp32 holds every position's five nucleotide
+    floats A,C,G,T,N in columns col0 .. col0+4, read in place (no copy of the columns is made).  P (rows,4) fp32,
+    state_nuc (q) int32: the row of P feeding state j, or < 0 for a free state (f = free_value).
+    f = sum_a (x[col0+a] + x[col0+4] / 4) P[state_nuc[j]][a].  With E (b,L,q) given, E *= f in place; otherwise a
+    new E = f.  Returns E.  q <= 256, rows <= 256."""
+    x, P, state_nuc, col0, (b, L, w, rows, q) = _nucleotide_args(x, col0, P, state_nuc)
+    multiply = E is not None
+    if multiply and not _is_E(E, (b, L, q)):
+        raise ValueError("E must be a contiguous fp32 device tensor of shape %s" % ((b, L, q),))
+    with torch.cuda.device(x.device):
+        if not multiply:
+            E = torch.empty((b, L, q), dtype=torch.float32, device=x.device)
+        _check(lib().hmm_nucleotide_emissions(x.data_ptr() + 4 * col0, w, b, L, P.data_ptr(), rows,
+                                              state_nuc.data_ptr(), q, float(free_value), int(multiply),
+                                              E.data_ptr(), _stream(x.device)))
+    return E
+
+
+def nucleotide_emissions_grad(x, col0, P, state_nuc, dE, E_in=None, free_value=0.25, want_dE_in=True, want_dP=True):
+    """Backward of nucleotide_emissions (hmm_nucleotide_emissions_grad): dE (b,L,q) = dL/dE_out ->
+    (dE_in (b,L,q) | None, dP (rows,4) | None).  x, col0, P and state_nuc as for nucleotide_emissions; E_in (b,L,q)
+    is the tensor the forward multiplied into (None: the forward wrote E = f, E_in counts as ones).  There is no
+    gradient for x: nucleotides are data.  dP is written whole and summed in a fixed order: repeated calls, and
+    calls for either output alone, are bit-identical.  The workspace (one (rows,4) partial per workgroup, at most
+    1024 of them) comes from the engine's cache under a key of its own per device and stream."""
+    x, P, state_nuc, col0, (b, L, w, rows, q) = _nucleotide_args(x, col0, P, state_nuc)
+    if not _is_E(dE, (b, L, q)):
+        raise ValueError("dE must be a contiguous fp32 device tensor of shape %s" % ((b, L, q),))
+    if E_in is not None and not _is_E(E_in, (b, L, q)):
+        raise ValueError("E_in must be a contiguous fp32 device tensor of shape %s" % ((b, L, q),))
+    if not (want_dE_in or want_dP):
+        return None, None
+    with torch.cuda.device(x.device):
+        # at most 1024 x rows x 4 floats: no floor
+        ws = _workspace(x.device, lib().hmm_nucleotide_emissions_grad_workspace_bytes(b, L, rows, q),
+                        "nucleotide_grad", floor=0)
+        dE_in = torch.empty_like(dE) if want_dE_in else None
+        dP = torch.empty_like(P) if want_dP else None
+        _check(lib().hmm_nucleotide_emissions_grad(
+            x.data_ptr() + 4 * col0, w, b, L, P.data_ptr(), rows, state_nuc.data_ptr(), q, float(free_value),
+            E_in.data_ptr() if E_in is not None else None, dE.data_ptr(), dE_in.data_ptr() if want_dE_in else None,
+            dP.data_ptr() if want_dP else None, ws.data_ptr(), ws.numel(), _stream(x.device)))
+    return dE_in, dP
 
 
 def _viterbi(name, logA, logpi, logE):

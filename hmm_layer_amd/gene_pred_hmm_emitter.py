@@ -25,7 +25,17 @@ introns or not), hmm_gene_emissions_wide / hmm_gene_emissions_grad_wide; above 2
 With ``emit_embeddings=True`` the embedding factor follows the same borders: hmm_embedding_emissions /
 hmm_embedding_emissions_grad up to 64 states and 32 rows, hmm_embedding_emissions_wide /
 hmm_embedding_emissions_grad_wide up to 256 states and rows (three to eighteen copies), ``forward()`` above.
-Three more differences from the as-shipped reference, on purpose:
+With ``trainable_nucleotides_at_exons=True`` one more factor follows on every route: hmm_nucleotide_emissions multiplies
+the learned nucleotide distribution of the exon states into E (``forward_fused``), reading the five nucleotide columns
+in place; with ``fused_training=True`` it is one more node (autograd.NucleotideEmissions, backward
+hmm_nucleotide_emissions_grad), through which ``nuc_emission_kernel`` trains.  One kernel pair serves every model of
+up to 256 states.
+Four more differences from the as-shipped reference, on purpose:
+  * with ``trainable_nucleotides_at_exons=True`` the reference reads ``inputs[..., -5:]`` after ``inputs`` has already
+    lost its nucleotide columns (gene_pred_hmm_emitter.py:265-266), so its nucleotide factor is computed from the last
+    five class (or embedding) columns.  Here the factor is computed from the nucleotides, the intended meaning:
+    acgt = nuc[..., :4] + nuc[..., 4:] / 4, f = acgt . softmax(nuc_emission_kernel) on E0/E1/E2 of every copy and 1/4
+    elsewhere.  There is therefore no fixture from the reference for this factor; the tests go by an fp64 restatement.
   * MvnMixture.__init__ copies the parameter with ``torch.tensor(kernel)`` (MvnMixture.py:40), so the
     reference never trains ``embedding_emission_kernel``; here the graph is kept and mu / sigma receive
     gradients.
@@ -167,6 +177,8 @@ class SimpleGenePredHMMEmitter(nn.Module):
     def apply_end_hints(self, emit, end_hints):
         if end_hints is None:
             return emit
+        if emit.shape[-2] == 1:               # one position: it is the first and the last
+            return end_hints[..., :1, :] * end_hints[..., 1:, :] * emit
         left = end_hints[..., :1, :] * emit[..., :1, :]
         right = end_hints[..., 1:, :] * emit[..., -1:, :]
         return torch.cat([left, emit[..., 1:-1, :], right], dim=-2)
@@ -245,7 +257,12 @@ class GenePredHMMEmitter(SimpleGenePredHMMEmitter):
         super().build(input_shape)
         if self.trainable_nucleotides_at_exons:
             assert self.num_models == 1, "trainable nucleotide emissions support one model"
-            self.nuc_emission_kernel = nn.Parameter(torch.zeros(self.num_models, 3 * self.num_copies, 4))
+            shape = (self.num_models, 3 * self.num_copies, 4)
+            if torch.is_tensor(self.nucleotide_kernel_init):
+                start = self.nucleotide_kernel_init.detach().clone().to(torch.float32).reshape(shape)
+            else:
+                start = torch.zeros(shape)
+            self.nuc_emission_kernel = nn.Parameter(start)
 
     def get_nucleotide_probs(self):
         return torch.softmax(self.nuc_emission_kernel, dim=-1)
@@ -322,10 +339,10 @@ class GenePredHMMEmitter(SimpleGenePredHMMEmitter):
         return "wide" if wide else "gene", "mvn_wide" if mvn else "mvn"
 
     def can_fuse(self, inputs):
-        # one model on a GPU, no trainable nucleotide factor, and kernels for the shape (fused_routes): every model
-        # of up to 256 states and kernel rows (18 copies), with or without embeddings; anything larger takes forward()
-        return (inputs.is_cuda and inputs.shape[0] == 1 and self.num_models == 1
-                and not self.trainable_nucleotides_at_exons and self.built
+        # one model on a GPU and kernels for the shape (fused_routes): every model of up to 256 states and kernel rows
+        # (18 copies), with or without embeddings or the trainable nucleotide factor (hmm_nucleotide_emissions serves
+        # the same 256 states); anything larger takes forward()
+        return (inputs.is_cuda and inputs.shape[0] == 1 and self.num_models == 1 and self.built
                 and self.fused_routes()[0] is not None)
 
     def state_tables(self, device):
@@ -340,6 +357,14 @@ class GenePredHMMEmitter(SimpleGenePredHMMEmitter):
         return (torch.tensor(rows, dtype=torch.int32, device=device),
                 torch.tensor(cod, dtype=torch.int32, device=device))
 
+    def nucleotide_table(self, device):
+        """state -> row of get_nucleotide_probs()[0] as an int32 tensor: j - (1 + 3c) on the exon states E0/E1/E2 of
+        every copy (1 + 3c <= j < 1 + 6c), -1 (free: the factor is 1/4) on every other state."""
+        c = self.num_copies
+        tab = torch.full((self.num_states,), -1, dtype=torch.int32)
+        tab[1 + 3 * c:1 + 6 * c] = torch.arange(3 * c, dtype=torch.int32)
+        return tab.to(device)
+
     def forward_fused(self, inputs, end_hints=None, training=False):
         """Same values as forward() (inference, one model) without the (b,L,64) 3-mer tensors:
         one HIP kernel from class probabilities + nucleotides to E (hmm_gene_emissions, or hmm_gene_emissions_wide
@@ -348,7 +373,10 @@ class GenePredHMMEmitter(SimpleGenePredHMMEmitter):
         With embeddings, a second kernel (hmm_embedding_emissions, or hmm_embedding_emissions_wide) multiplies the normal-density factor into E,
         reading the d embedding columns in place from `inputs`; the class kernel takes a compact (b, L, s + 5)
         copy of the other columns.  With training=True the reference adds 1e-10 to the class term before the
-        product, which the class kernel cannot express: that case takes forward()."""
+        product, which the class kernel cannot express: that case takes forward().
+
+        With trainable_nucleotides_at_exons, hmm_nucleotide_emissions then multiplies the nucleotide factor into E in
+        place, reading the last five columns of `inputs` where they lie."""
         from . import engine
         with torch.no_grad():
             if self.emit_embeddings and training:
@@ -372,6 +400,9 @@ class GenePredHMMEmitter(SimpleGenePredHMMEmitter):
                 mean, inv_std, log_norm = self.embedding_tables(inputs.device)
                 mvn = engine.embedding_emissions_wide if mvn_route == "mvn_wide" else engine.embedding_emissions
                 mvn(x, s, d, mean, inv_std, log_norm, row, E=E, inv_temperature=1.0 / float(self.temperature))
+            if self.trainable_nucleotides_at_exons:
+                engine.nucleotide_emissions(x, x.shape[-1] - 5, self.get_nucleotide_probs()[0].to(torch.float32).contiguous(),
+                                            self.nucleotide_table(inputs.device), E=E)
             return self.apply_end_hints(E.unsqueeze(0), end_hints)
 
     def forward_fused_trainable(self, inputs, end_hints=None, training=False):
@@ -392,8 +423,16 @@ class GenePredHMMEmitter(SimpleGenePredHMMEmitter):
         training=True the reference adds 1e-10 to the class term before the product ((C + 1e-10) (f + 1e-10)
         (cod + 1e-7)): the compact tensor gets one more class column of value 1e-10 and B a column of ones, so
         that C + 1e-10 comes out of the unchanged class kernel (torch.cat's backward drops the column again).
-        That needs s + 1 <= 32 classes; above that, and where can_fuse(inputs) does not hold, this is forward()."""
+        That needs s + 1 <= 32 classes; above that, and where can_fuse(inputs) does not hold, this is forward().
+
+        With trainable_nucleotides_at_exons one more node follows the class node and the embedding node
+        (autograd.NucleotideEmissions: hmm_nucleotide_emissions forward, hmm_nucleotide_emissions_grad backward): it
+        multiplies the nucleotide factor into E, reading the five nucleotide columns of the input in place, with
+        P = get_nucleotide_probs()[0] and its graph, so nuc_emission_kernel trains.  Where can_fuse(inputs) does not
+        hold, that option takes forward() too."""
         from . import autograd
+        if self.trainable_nucleotides_at_exons and not self.can_fuse(inputs):
+            return self.forward(inputs, end_hints=end_hints, training=training)
         B = self.make_B()[0].to(torch.float32)
         row, cod = self.state_tables(inputs.device)
         x = inputs[0].to(torch.float32)
@@ -401,7 +440,7 @@ class GenePredHMMEmitter(SimpleGenePredHMMEmitter):
         codon = self.codon_probs.to(inputs.device, torch.float32).contiguous()
         if not self.emit_embeddings:
             E = autograd.gene_emissions(x, B, row, codon, cod, **kw)
-            return self.apply_end_hints(E.unsqueeze(0), end_hints)
+            return self.apply_end_hints(self._nucleotide_node(E, x).unsqueeze(0), end_hints)
         d = self.embedding_dim
         s = x.shape[-1] - d - 5
         if (training and s + 1 > 32) or not self.can_fuse(inputs):
@@ -415,7 +454,15 @@ class GenePredHMMEmitter(SimpleGenePredHMMEmitter):
         E = autograd.embedding_emissions(E, x, mean, inv_std, log_norm, row, s, d,
                                          inv_temperature=1.0 / float(self.temperature),
                                          add=1e-10 if training else 0.0)
-        return self.apply_end_hints(E.unsqueeze(0), end_hints)
+        return self.apply_end_hints(self._nucleotide_node(E, x).unsqueeze(0), end_hints)
+
+    def _nucleotide_node(self, E, x):
+        """E (b,L,q) times the trainable nucleotide factor (autograd.NucleotideEmissions); E itself without the option."""
+        if not self.trainable_nucleotides_at_exons:
+            return E
+        from . import autograd
+        return autograd.nucleotide_emissions(E, x, self.get_nucleotide_probs()[0].to(torch.float32),
+                                             self.nucleotide_table(x.device), x.shape[-1] - 5)
 
     def get_config(self):
         config = super().get_config()

@@ -20,7 +20,7 @@ def make_k_mers(sequences, k, pivot_left=True, n_mass=1):
     n = sequences.shape[-1] - 1
     is_n = (sequences[..., -1:] == 1).to(sequences.dtype)
     acgt = sequences[..., :-1] + (n_mass / n) * is_n
-    pad = torch.full_like(acgt[:, :k - 1, :], 1.0 / n)
+    pad = acgt.new_full((acgt.shape[0], k - 1, n), 1.0 / n)           # k - 1 rows also where L < k - 1
     if pivot_left:
         ext = torch.cat([acgt, pad], dim=-2)
         offsets = range(1, k)

@@ -464,6 +464,56 @@ int hmm_embedding_emissions_grad_wide(const float *emb, long long ld, int b, int
                                       void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * Trainable nucleotide factor of the gene-prediction models (trainable_nucleotides_at_exons=True): a learned
+ * 4-way nucleotide distribution on the exon states E0/E1/E2 of every copy, multiplied into (or written as) the
+ * emission tensor.  Replaces the acgt einsum, the concatenation with the 1/4 columns and the product of
+ * GenePredHMMEmitter.forward (hmm_layer/gene_pred_hmm_emitter.py:224-229, 265-272) for one model:
+ *   nuc         first nucleotide float (A) of position 0; position p's five floats A,C,G,T,N start at nuc + p * ld
+ *               (ld >= 5).  Read in place: the layer passes x + s (x + s + d with embeddings) with ld = the row
+ *               width.  Needs 4-byte alignment only; nothing outside those five floats is read.
+ *   P           (rows,4)    softmax of the nucleotide kernel (emitter.get_nucleotide_probs()[0])
+ *   state_nuc   (q) int     row of P feeding state j, or < 0 for a free state (f = free_value, 1/4); entries
+ *                           >= rows are clamped to rows - 1
+ *   acgt[p][a] = nuc[p][a] + nuc[p][4] / 4    (plain arithmetic: no test for N == 1)
+ *   f[p][j]    = state_nuc[j] >= 0 ? sum_a acgt[p][a] * P[state_nuc[j]][a] : free_value     (a = 0, 1, 2, 3 in order)
+ *   E           (b,L,q)     multiply = 1: E[p][j] *= f[p][j] (read and written once); multiply = 0: E[p][j] = f[p][j]
+ * Backward (hmm_nucleotide_emissions_grad), with dE (b,L,q) = dL/dE_out and E_in (b,L,q) the tensor the forward
+ * multiplied into (NULL for the multiply = 0 forward: E_in = 1):
+ *   dE_in       (b,L,q)     or NULL: dE[p][j] * f[p][j].  Must not alias dE.
+ *   dP          (rows,4)    or NULL: sum_p acgt[p][a] * sum_{j: state_nuc[j] = r} dE[p][j] * E_in[p][j].  Written
+ *                           whole (the caller zeroes nothing; a row no state points at is 0).
+ * Nucleotides are data: there is no gradient for them.  There is no division anywhere, so an all-zero nucleotide
+ * row (padding) gives f = 0 and finite gradients.  Reduction order of dP, fixed by b*L, q, rows and state_nuc
+ * alone: workgroup x of X = min(tiles of 256 positions, 1024) takes tiles x, x + X, ...; inside it lane (g, j) —
+ * state j, position group g of G = 256 / q — adds its positions (g, g + G, ... of every tile) in ascending order
+ * in fp32, then element (r, a) of the workgroup's partial is the sum over the states j of row r in ascending
+ * order, and per state over g in ascending order; the partials are added in workgroup order in fp64 and rounded
+ * once.  No atomics: repeated calls, and calls for either output alone, are bit-identical; the forward does not
+ * depend on the grid.
+ * Limits: 1 <= q <= hmm_nucleotide_emissions_max_states() (256), 1 <= rows <= 256; one kernel serves every q
+ * (E rows need 4-byte alignment only).  Checked before any HIP call, in this order: shape (HMM_ERR_BAD_SHAPE:
+ * b, L, q or rows < 1, ld < 5), limits (HMM_ERR_Q_UNSUPPORTED), pointers (HMM_ERR_NULL_POINTER; for the grad: any
+ * input, the workspace, or both outputs NULL), then multiply not 0 or 1 (forward, HMM_ERR_BAD_ARGUMENT) or the
+ * workspace (grad, HMM_ERR_WORKSPACE: fewer than hmm_nucleotide_emissions_grad_workspace_bytes bytes, or not
+ * 256-byte aligned).  The workspace holds the X partials of rows * 4 floats (at most 4 MiB): the query returns a
+ * multiple of 256 that stops growing with b*L, and 0 for an unsupported shape.  Both run on `stream` only,
+ * without host synchronisation, and are capturable into a HIP graph; every offset into nuc, E, E_in, dE and
+ * dE_in is 64-bit.
+ */
+int hmm_nucleotide_emissions_max_states(void);
+int hmm_nucleotide_emissions(const float *nuc, long long ld, int b, int L,
+                             const float *P /* (rows,4) */, int rows,
+                             const int *state_nuc /* (q) */, int q,
+                             float free_value, int multiply,
+                             float *E /* (b,L,q) */, void *stream);
+size_t hmm_nucleotide_emissions_grad_workspace_bytes(int b, int L, int rows, int q);
+int hmm_nucleotide_emissions_grad(const float *nuc, long long ld, int b, int L,
+                                  const float *P, int rows, const int *state_nuc, int q, float free_value,
+                                  const float *E_in /* (b,L,q) or NULL (= ones) */, const float *dE /* (b,L,q) */,
+                                  float *dE_in /* (b,L,q) or NULL */, float *dP /* (rows,4) or NULL */,
+                                  void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Per-kernel timing for the roofline report (bench.py): the same computation as
  * hmm_posterior with every kernel launch bracketed by HIP events recorded on `stream`.
  * hmm_profile_read() waits for the recorded events, returns the summed milliseconds and
