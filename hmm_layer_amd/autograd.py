@@ -39,7 +39,8 @@ def loglik(A, pi, E, eps=engine.EPS):
 class Posterior(torch.autograd.Function):
     """State posteriors (k,b,L,q), probabilities or logs, differentiable in A, pi and E.  Forward =
     hmm_posterior (the chunked kernels), backward = hmm_posterior_grad (its four sweeps per chunk of the
-    scan plan, or over whole sequences where the device-side routing says so; hmm_posterior_grad_large above
+    scan plan, or over whole sequences where the device-side routing says so — 17..64 states per chunk through
+    hmm_posterior_grad_scan where its predicate says it pays; hmm_posterior_grad_large above
     64 states) — the reference gets this gradient by autograd through its forward and backward loops
     (hmm_layer/MsaHMMLayer.py:422-521 with training=True)."""
 

@@ -94,7 +94,7 @@ static bool pc_wanted(int k, int b, int L, int q) {
     return (long long)k * b <= (W == QP ? 4096 : 512) && C >= 4;
 }
 
-// W: the row width; 0 = pc_width's (hmm_grad_scan.inc asks for Q32 / Q64 for any model of 17..64 states)
+// W: the row width; 0 = pc_width's (hmm_grad_scan.inc and hmm_postgrad_scan.inc ask for Q32 / Q64 for any model of 17..64 states)
 static int make_pcplan(int k, int b, int L, int q, PcPlan *pc, int W = 0) {
     if (W == 0) W = pc_width(q);
     if (W == 0) return HMM_ERR_Q_UNSUPPORTED;
@@ -513,23 +513,28 @@ __global__ __launch_bounds__(64) void k_pc_scan(const float *__restrict__ ops, c
                                                 const float *__restrict__ cvec, const PgSide *__restrict__ sides,
                                                 const int *__restrict__ topo, Plan p, float eps, int mode,
                                                 int exact_mode, int force, float *__restrict__ lam,
-                                                int *__restrict__ need) {
+                                                int *__restrict__ need, const int *__restrict__ risk = nullptr) {
     const int seq = blockIdx.x, dir = blockIdx.y, x = threadIdx.x & 63, n = x & (W - 1);
     const int C = p.C, q = p.q, L = p.L;
     const size_t ch0 = (size_t)seq * C;
     const bool model_exact = PcW<W>::model_serial(topo, seq / p.b);
     if (dir == 0) {
         float s = 0.f, gp = 0.f, gq = 0.f, gt = 0.f;
-        if (!model_exact)
+        bool mark = false;                                   // risk (or null): the reduces' marks, as k_pc_llselect reads them
+        if (!model_exact) {
+            const int el = topo[seq / p.b];
             for (int c = x; c < C; c += 64) {
                 const PgSide sd = sides[(size_t)p.nchains + ch0 + c];               // (the sums are the descending sweep's)
                 s += sd.inv_sg; gp += sd.g_over_gamma; gq += sd.g_tiny; gt += sd.g_all;
+                if (risk) mark = mark || (elig_dense(el) ? risk[ch0 + c] != 0 : exps[(ch0 + c) * W + W - 1] != 0);
             }
+        }
+        mark = __builtin_amdgcn_ballot_w64(mark) != 0ull;
         const float F = mq_wave_sum(s) * eps;
         gp = mq_wave_sum(gp); gq = mq_wave_sum(gq); gt = mq_wave_sum(gt);
         bool flagged = !(F <= EXACT_DELTA);                                           // (also catches inf / NaN)
         if (mode == HMM_POST_LOG) flagged = flagged || !(F * gp + gq <= PC_LOG_EXPOSED * gt);
-        flagged = flagged && !force && exact_mode == HMM_EXACT_AUTO;
+        flagged = (flagged || mark) && !force && exact_mode == HMM_EXACT_AUTO;
         if (x == 0) need[seq] = (model_exact || flagged) ? 1 : 0;
     }
     if (model_exact) return;
@@ -683,9 +688,12 @@ __global__ __launch_bounds__(256) void k_pc_fold_seq(const float *__restrict__ g
 }
 #define PC_FOLD_WAVES_MAX_SEQS 256        // up to here a wave per entry, above a block per sequence
 
+// risk (or null): the dense reduces' per-chain marks flag a sequence as well (hmm_postgrad_scan.inc; hmm_posterior_grad's
+// own paths run without)
 template <int W>
 static int pc_launch_w(const float *A, const float *pi, const float *E, int k, int b, int L, int q, float eps, int mode,
-                       const float *G, float *dA, float *dpi, float *dE, char *ws, const PcPlan &pc, hipStream_t st) {
+                       const float *G, float *dA, float *dpi, float *dE, char *ws, const PcPlan &pc, hipStream_t st,
+                       const int *risk = nullptr) {
     const Plan &p = pc.p;
     const PgPlan &pp = pc.pg;
     char *wp = ws + pc.o_pg;
@@ -704,15 +712,17 @@ static int pc_launch_w(const float *A, const float *pi, const float *E, int k, i
     hipLaunchKernelGGL(k_pc_scan<W>, dim3(p.NB, 2), dim3(64), 0, st, (const float *)(ws + pc.o_ops),
                        (const int *)(ws + pc.o_exps), (const float *)AH, (const float *)RB, (const float *)cvec,
                        (const PgSide *)sides, route, p, eps, mode, opt(HMM_OPT_EXACT), opt(HMM_OPT_PGCHUNK) == 2 ? 1 : 0,
-                       lam, need);
+                       lam, need, risk);
     hipLaunchKernelGGL(k_pc_final<W>, chains2, dim3(64), 0, st, A, pi, E, (const float *)AH, (const float *)S,
                        (const float *)RB, G, route, (const int *)need, p, eps, mode, (const float *)lam, dE, dEa, gpart, dpp);
     if (p.NB <= PC_FOLD_WAVES_MAX_SEQS)
         hipLaunchKernelGGL(k_pc_fold, dim3(q * q, p.NB, 2), dim3(64), 0, st, (const float *)gpart, (const int *)need, p, gb, ga);
     else
         hipLaunchKernelGGL(k_pc_fold_seq, dim3(p.NB, 2), dim3(256), 0, st, (const float *)gpart, (const int *)need, p, 2, gb, ga);
-    // the serial sweeps for what is flagged (their waves exit at once otherwise), then the common tail
-    pg_launch<W>(A, pi, E, k, b, L, q, eps, mode, G, dA, dE, wp, pp, st, need);
+    // the serial sweeps for what is flagged (their waves exit at once otherwise), then the common tail.  The redo is
+    // hmm_posterior_grad's own instantiation for q, bit for bit: rows of 64 serve 33..48 states with k_pg_*<48>
+    if (W == Q64 && q <= 48) pg_launch<48>(A, pi, E, k, b, L, q, eps, mode, G, dA, dE, wp, pp, st, need);
+    else pg_launch<W>(A, pi, E, k, b, L, q, eps, mode, G, dA, dE, wp, pp, st, need);
     hipLaunchKernelGGL(k_pg_sum_rows, dim3(q, k), dim3(64), 0, st, (const float *)dpp, dpi, b, q);
     return check_launch();
 }

@@ -22,7 +22,7 @@
 // certificate (psi, or the one-directional CERT / CERT3 sums) fires or that a reduce marked (k_scan_select) — is
 // served by the one-wave-per-sequence kernels of hmm_midq.inc, which implement the cell's serial semantics exactly
 // and take a per-sequence mask.  hmm_posterior (all modes), hmm_forward and hmm_backward use this path; the gradients
-// run per chunk of this plan (hmm_postgrad_chunked.inc, hmm_grad_scan.inc), otherwise — and Viterbi always — on
+// run per chunk of this plan (hmm_postgrad_chunked.inc, hmm_grad_scan.inc, hmm_postgrad_scan.inc), otherwise — and Viterbi always — on
 // hmm_midq.inc.  This file holds the kernels; the plan (MidPlan) and the host drivers are in hmm_scan_mid.inc.
 
 #define Q32 32

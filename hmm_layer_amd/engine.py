@@ -90,6 +90,12 @@ _SIGNATURES = {
     "hmm_posterior_grad_workspace_bytes": (_SZ, [_I] * 4),
     "hmm_posterior_grad": (_I, _POSTERIOR_GRAD),
     "hmm_posterior_grad_serial_count": (_LL, _LAST_CALL),
+    "hmm_posterior_grad_scan_max_states": (_I, []),
+    "hmm_posterior_grad_scan_chunk_len": (_I, [_I] * 4),
+    "hmm_posterior_grad_scan_pays": (_I, [_I] * 4),
+    "hmm_posterior_grad_scan_workspace_bytes": (_SZ, [_I] * 4),
+    "hmm_posterior_grad_scan_serial_count": (_LL, _LAST_CALL),
+    "hmm_posterior_grad_scan": (_I, _POSTERIOR_GRAD),
     "hmm_posterior_grad_large_max_states": (_I, []),
     "hmm_posterior_grad_large_workspace_bytes": (_SZ, [_I] * 4),
     "hmm_posterior_grad_large": (_I, _POSTERIOR_GRAD),
@@ -294,6 +300,11 @@ def loglik_grad_serial_count(dims, device=None):
 def loglik_grad_scan_serial_count(dims, device=None):
     """The same for the LAST loglik_grad_scan call (also one that loglik_grad routed there)."""
     return posterior_grad_serial_count(dims, device, _fn="hmm_loglik_grad_scan_serial_count", _tag="loglik_grad_scan")
+
+
+def posterior_grad_scan_serial_count(dims, device=None):
+    """The same for the LAST posterior_grad_scan call (also one that posterior_grad routed there)."""
+    return posterior_grad_serial_count(dims, device, _fn="hmm_posterior_grad_scan_serial_count", _tag="posterior_grad_scan")
 
 
 def posterior_grad_serial_count(dims, device=None, _fn="hmm_posterior_grad_serial_count", _tag=None):
@@ -837,19 +848,26 @@ def loglik_grad_large(A, pi, E, grad_loglik=None, eps=EPS):
 
 
 def _posterior_grad(name, A, pi, E, grad_out, mode, eps):
-    """The body of posterior_grad / posterior_grad_large: hmm_<name>, covering q <= hmm_<name>_max_states()."""
+    """The body of posterior_grad / posterior_grad_scan / posterior_grad_large: hmm_<name>, covering
+    q <= hmm_<name>_max_states().  posterior_grad_scan keeps its workspace under a tag of its own."""
     if int(mode) not in (POST_PROB, POST_LOG):
         raise ValueError("%s supports mode POST_PROB or POST_LOG" % name)
     A, pi, E, grad_out = _dev(A, "A"), _dev(pi, "pi"), _dev(E, "E"), _dev(grad_out, "grad_out")
     A, pi, dims = _shapes(A, E, pi)
     k, b, L, q = dims
+    if name == "posterior_grad" and lib().hmm_scan_max_states() < q <= lib().hmm_posterior_grad_scan_max_states() \
+            and lib().hmm_posterior_grad_scan_pays(*dims):
+        name = "posterior_grad_scan"
     limit = getattr(lib(), "hmm_%s_max_states" % name)()
     if q > limit:
         raise ValueError("%s covers q <= %d states, got %d" % (name, limit, q))
     if grad_out.shape != E.shape:
         raise ValueError("grad_out must be shaped like E")
     with torch.cuda.device(E.device):
-        ws = _workspace(E.device, getattr(lib(), "hmm_%s_workspace_bytes" % name)(*dims))
+        need = getattr(lib(), "hmm_%s_workspace_bytes" % name)(*dims)
+        if name == "posterior_grad_scan" and need == 0:
+            raise ValueError("posterior_grad_scan does not support the shape (k, b, L, q) = %s" % (dims,))
+        ws = _workspace(E.device, need, "posterior_grad_scan" if name == "posterior_grad_scan" else None)
         dA = torch.empty((k, q, q), dtype=torch.float32, device=E.device)
         dpi = torch.empty((k, q), dtype=torch.float32, device=E.device)
         dE = torch.empty_like(E)
@@ -863,8 +881,17 @@ def posterior_grad(A, pi, E, grad_out, mode=POST_LOG, eps=EPS):
     """Gradients of <grad_out, out> with out = posterior(A, pi, E, mode) -> (dA (k,q,q), dpi (k,q), dE (k,b,L,q)).
 
     What autograd through the reference's _state_posterior_log_probs_impl loops computes
-    (hmm_layer/MsaHMMLayer.py:422-521); mode POST_PROB or POST_LOG."""
+    (hmm_layer/MsaHMMLayer.py:422-521); mode POST_PROB or POST_LOG.  17..64 states: through posterior_grad_scan where
+    hmm_posterior_grad_scan_pays says so."""
     return _posterior_grad("posterior_grad", A, pi, E, grad_out, mode, eps)
+
+
+def posterior_grad_scan(A, pi, E, grad_out, mode=POST_LOG, eps=EPS):
+    """posterior_grad() through hmm_posterior_grad_scan, per chunk of the scan plan for 1 <= q <= 64 (same arguments,
+    results and semantics): what few, long sequences of the 17..64-state models want.  OPT_CHUNK forces the chunk
+    length, OPT_PGCHUNK = 2 serves every sequence per chunk (tests); posterior_grad_scan_serial_count() tells how many
+    sequences the whole-sequence sweeps redid."""
+    return _posterior_grad("posterior_grad_scan", A, pi, E, grad_out, mode, eps)
 
 
 def posterior_grad_large(A, pi, E, grad_out, mode=POST_LOG, eps=EPS):

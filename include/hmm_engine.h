@@ -719,6 +719,48 @@ int hmm_posterior_grad(const float *A, const float *pi, const float *E,
                        void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * The same gradient, per chunk of the scan plan, for 1 <= q <= hmm_posterior_grad_scan_max_states() (64): arguments,
+ * outputs, modes (HMM_POST_PROB, HMM_POST_LOG) and clamp semantics exactly those of hmm_posterior_grad.
+ * hmm_posterior_grad itself evaluates 17..64 states per chunk only for the compiled 29-state topology; every other
+ * model of that range walks four whole-sequence sweeps, one workgroup per sequence.  This entry point is the
+ * explicit request to run ANY primitive model of 17..64 states per chunk: the reduce and chunk scan of its row
+ * width (32 lanes for 17..32 states, 64 for 33..64), the two value sweeps per chunk, every chunk's affine adjoint
+ * map, a scan of those maps, and the adjoint sweeps again from the true entering vectors.  Models whose support is
+ * not primitive, sequences over the floor-transition certificate (F = eps * sum_t 1 / Sg_t > 2e-6), in log mode
+ * sequences whose upstream gradient is exposed to the floors (hmm_posterior_grad's rule above) and sequences a
+ * reduce marked are redone by the masked whole-sequence sweeps inside the same call, bit-identical to
+ * hmm_posterior_grad under HMM_OPT_PGCHUNK = 0.  The exception stated above for dA entries of absent edges holds
+ * here as well.  q <= 16 forwards to hmm_posterior_grad (call, workspace query and serial count alike).
+ *   hmm_posterior_grad_scan_chunk_len        the chunk length the call would use (17..64 states: a multiple of 16,
+ *                                            <= 512; HMM_OPT_CHUNK forces it); 0 for an unsupported shape
+ *   hmm_posterior_grad_scan_pays             1 where the measured rule prefers this call to
+ *                                            hmm_posterior_grad; 0 for q <= 16, under HMM_OPT_PGCHUNK = 0, where
+ *                                            hmm_posterior_grad already runs per chunk, below 4 chunks, and for
+ *                                            every shape the call would refuse
+ *   hmm_posterior_grad_scan_workspace_bytes  exactly what the call uses, in 64-bit sizes (three arrays of k*b*L*q
+ *                                            floats, the chunk operators and more); 0 for an unsupported shape
+ *   hmm_posterior_grad_scan_serial_count     how many sequences of the LAST call with this shape the
+ *                                            whole-sequence sweeps served (synchronous copy from the workspace)
+ * Unsupported: L * q * 4 >= 2^31 - 4096 (the kernels' 32-bit row offsets) and k * b > 2^24: HMM_ERR_BAD_SHAPE.
+ * Options: HMM_OPT_CHUNK, HMM_OPT_EXACT and HMM_OPT_FORCE_DENSE act as for hmm_posterior's 17..64-state plans;
+ * HMM_OPT_PGCHUNK = 2 serves every sequence of an eligible model per chunk, without certificate and marks (tests).
+ * Runs on `stream` only, no host synchronisation; fixed summation orders (fp32 inside a chunk, fp64 across chunks
+ * and sequences): repeated calls are bit-identical.
+ * Argument checks, before any HIP call and in hmm_posterior_grad's order: k, b, L or q < 1 -1, q > 64 -2, mode not
+ * HMM_POST_PROB / HMM_POST_LOG -6, a NULL A / pi / E / grad_out / dA / dpi / dE / workspace -3, an unsupported shape
+ * -1, a small or misaligned (256 bytes) workspace -4.
+ */
+int hmm_posterior_grad_scan_max_states(void);
+int hmm_posterior_grad_scan_chunk_len(int k, int b, int L, int q);
+int hmm_posterior_grad_scan_pays(int k, int b, int L, int q);
+size_t hmm_posterior_grad_scan_workspace_bytes(int k, int b, int L, int q);
+long long hmm_posterior_grad_scan_serial_count(int k, int b, int L, int q, const void *workspace, size_t workspace_bytes);
+int hmm_posterior_grad_scan(const float *A, const float *pi, const float *E,
+                            int k, int b, int L, int q, float eps, int mode, const float *grad_out,
+                            float *dA, float *dpi, float *dE,
+                            void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * The same gradient for any 1 <= q <= hmm_posterior_grad_large_max_states() (4096): arguments, outputs, modes and
  * clamp handling exactly those of hmm_posterior_grad (all four clamps pass nothing: max(E, eps), max(pi, eps), the
  * forward cell's clamp of the predicted state and the backward max(A bh, eps)).  The four sweeps of
