@@ -2,7 +2,7 @@
 // included after hmm_midq.inc, hmm_largeq.inc and hmm_grad.inc.
 //
 // Same derivatives and clamp handling as hmm_grad.inc / k_mq_backward_grad (oracle.textbook.loglik_grad):
-//   dE_t = w gamma_t / E_t (0 where E_t <= eps),   dpi = sum_s w gamma_0 / pi (0 where pi <= eps),
+//   dE_t = w gamma_t / E_t (0 where E_t <= eps),   dpi = sum_s w gamma_0 / pi (0 where pi <= eps, whatever E_0 is),
 //   dA   = sum_t coef_t^T bh_{t+1},  coef_t = alpha_hat_t w / <alpha_hat_t, R_t>,
 //   R_t  = max(bh_{t+1} A^T, eps),   bh_t = live_t * normalised(max(E_t, eps) R_t),   gamma_t ∝ alpha_hat_t R_t,
 // where live_t[j] says that the forward cell's clamp of the predicted state, (alpha_hat_{t-1} A)[j] <= eps
@@ -147,10 +147,11 @@ __global__ __launch_bounds__(QB) void k_gl_walk_bwd(const float *__restrict__ A,
         for (int x = 1; x < NW; ++x) v += p[s][x];
         return v;
     };
-    // dE of position t1 from its published sums; returns w / Sg
+    // dE of position t1 from its published sums; returns w / Sg.  Position 0 keeps w gamma_0 / eps in its clamped
+    // entries for k_mq_grad_pi, which zeroes them.
     auto finish = [&](int t1) {
         const float sc = wt / sum3(gp, t1 % 3);
-        if (act) o[(size_t)t1 * q + i] = eprev > eps ? gprev * sc / fmaxf(eprev, eps) : 0.f;
+        if (act) o[(size_t)t1 * q + i] = (eprev > eps || t1 == 0) ? gprev * sc / fmaxf(eprev, eps) : 0.f;
         return sc;
     };
     __syncthreads();                                          // At staged
@@ -241,7 +242,7 @@ __global__ __launch_bounds__(256) void k_gl_bpost(const float *__restrict__ E, f
     }
     for (int j = threadIdx.x; j < q; j += 256) {
         const float u = o[j], au = __builtin_fabsf(u), e = er[j];
-        o[j] = e > eps ? au * Rr[j] * sc / fmaxf(e, eps) : 0.f;
+        o[j] = (e > eps || t == 0) ? au * Rr[j] * sc / fmaxf(e, eps) : 0.f;     // (t = 0: as finish(0) of the walk)
         if (coef) coef[(size_t)row * q + j] = au * cb;
         if (__builtin_bit_cast(int, u) < 0) nxt[(size_t)row * q + j] = 0.f;
     }

@@ -605,7 +605,8 @@ int hmm_seqshard_posterior(const float *A, const float *pi, const float *E, int 
  * forward-backward pass (Baum-Welch expectations), for q <= hmm_grad_max_states():
  *   grad_loglik (k,b) fp32 or NULL (= ones): d loss / d loglik[m][s], the upstream gradient
  *   dA  (k,q,q) : sum_s grad_loglik * d loglik / d A    (= sum_t xi_t(i,j) / A[i][j], dense)
- *   dpi (k,q)   : sum_s grad_loglik * d loglik / d pi
+ *   dpi (k,q)   : sum_s grad_loglik * d loglik / d pi   (= sum_s grad_loglik * gamma_0 / pi, whatever E_0 is: a
+ *                 sequence whose first emissions are clamped still contributes its gamma_0)
  *   dE  (k,b,L,q): grad_loglik * gamma / E; zero where the cell clamps E below eps
  *   loglik (k,b) fp64 or NULL
  * Entries of E / pi that the cell clamps to eps receive no gradient (torch.maximum semantics).
@@ -670,6 +671,8 @@ int hmm_loglik_grad_scan(const float *A, const float *pi, const float *E,
  *          above returns HMM_ERR_BAD_ARGUMENT.
  *   GEMMs  per position one f32-MFMA GEMM of the forward recursion, one of the adjoint recursion with an
  *          elementwise pass for dE, and one (q x b)(b x q) product for dA, added into an fp64 accumulator.
+ * Under both, position 0 keeps w gamma_0 / eps in its clamped entries of dE until dpi has been summed from that
+ * row; they are zeroed afterwards, so dE is 0 wherever E <= eps and dpi loses nothing.
  * The workspace does not depend on L.  Sums run in a fixed order (fp32 within a sequence or a tile, fp64 across
  * sequences and positions): repeated calls return bit-identical results.  Everything runs in order on `stream`.
  * Argument checks, before any HIP call: bad shape -1, q > 4096 -2, a NULL A / pi / E / dA / dpi / dE / workspace

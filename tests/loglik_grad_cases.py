@@ -24,7 +24,8 @@ Tensor norms (tests/test_grad_gpu.py::check restated; each reported as worst err
 Finer norms (as in tests/postgrad_mid_cases.py):
   dA/row     row i over its present edges / max|want| over those edges, worst i
   dE/seq     max over (t, j) of |err| in sequence s / max|want| in sequence s, worst s
-  dE/col     the same per state column j — on the wave route only
+  dE/col     the same per state column j — on the wave route only (and on the two routes of hmm_loglik_grad_large,
+             tests/largeq_grad_cases.py)
 with the limit max(2e-4, 4 e32) per case, model and norm, e32 being the twin's own error under that norm: the factor 4
 pays for the kernel's approximate reciprocals (v_rcp_f32, 1 ulp) and its different summation order.  Nothing in a limit
 comes from engine output.
@@ -50,7 +51,8 @@ import torch
 
 from oracle import params, ref_cell, textbook
 
-from postgrad_mid_cases import copies_of, forward_backward64, forward_clamp_model, gene_model, rand_model
+from postgrad_mid_cases import (backward_clamp_model, copies_of, forward_backward64, forward_clamp_model, gene_model,
+                                rand_model)
 
 EPS = 1e-16
 SMALL = 1e-30
@@ -60,6 +62,7 @@ SMALL_CAP = 0.05
 TENSOR_NORMS = ("dA", "dA/absent", "dpi", "dE", "ll")
 ROUTES = ("scan16", "wave", "pc29", "gscan")
 SCAN_ROUTES = ("scan16", "pc29", "gscan")
+COL_ROUTES = ("wave", "lwalk", "lgemm")                      # lwalk, lgemm: hmm_loglik_grad_large (tests/largeq_grad_cases.py)
 
 # route: see above.  models: tuple of "dense" | "sparse" (rand_model, primitive) | "tinypi" (sparse, two pi entries
 # below eps) | "deadin" (sparse, three states nothing enters, two pi entries below eps) | "gene" (7 states: the simple
@@ -75,7 +78,7 @@ def spec_id(s):
 
 
 def fine_norms(route):
-    return ("dA/row", "dE/seq", "dE/col") if route == "wave" else ("dA/row", "dE/seq")
+    return ("dA/row", "dE/seq", "dE/col") if route in COL_ROUTES else ("dA/row", "dE/seq")
 
 
 @functools.lru_cache(maxsize=None)
@@ -108,6 +111,8 @@ def build_model(rng, name, q):
         return shipped15()
     if name == "fclamp":
         return forward_clamp_model(rng, q)
+    if name == "bclamp":
+        return backward_clamp_model(rng, q)
     if name == "deadin":
         return rand_model(rng, q, sparse=True, dead=3, tiny_pi=2)
     if name == "tinypi":
@@ -121,42 +126,61 @@ def build(spec):
     return _build(spec._replace(route="", chunk=0))
 
 
+def draw_E(rng, models, b, L, q, emis):
+    """Emissions (k, b, L, q) float32 in [0.05, 0.95] with the pattern `emis`; "mid" (tests/largeq_grad_cases.py):
+    a fifth of the entries 10^U(-16, -6), clamped under eps = 1e-6 and not under the default."""
+    k = len(models)
+    E = (rng.random((k, b, L, q)) * 0.9 + 0.05).astype(np.float32)
+    if emis in ("holes", "blank0"):
+        E[..., ::5, q // 3] = 0.0                            # emissions below eps: no gradient there
+    elif emis == "rare":
+        rare = rng.random(E.shape) < 0.2
+        rare[..., :min(7, q - 1)] = False
+        E[rare] = 1e-10                                      # far above eps: nothing is clamped
+    elif emis == "dead":                                     # the emitter's magnitude, zeros in the constrained states
+        E = E / np.float32(4096)
+        dead = rng.random(E.shape) < 0.3
+        dead[..., :1 + 6 * copies_of(q)] = False
+        E[dead] = 0.0
+    elif emis == "clamp":
+        for m, name in enumerate(models):
+            if name == "fclamp":
+                E[m, ..., q - 1] = 1.0
+            elif name == "bclamp":
+                E[m, ..., q - 1] = 0.0
+    elif emis == "stretch":                                  # four positions in a row that state 9 alone can emit
+        t0 = L // 2
+        E[0, STRETCH_SEQ, t0:t0 + STRETCH_LEN, :] = 0.0
+        E[0, STRETCH_SEQ, t0:t0 + STRETCH_LEN, STRETCH_STATE] = 0.5
+    elif emis == "mid":
+        mid = rng.random(E.shape) < 0.2
+        mid[..., :min(7, q - 1)] = False
+        E[mid] = (10.0 ** rng.uniform(-16, -6, int(mid.sum()))).astype(np.float32)
+    else:
+        raise ValueError(emis)
+    return E
+
+
+def draw_w(rng, k, b, kind):
+    """Sequence weights (k, b) float32, or None for "none"."""
+    if kind == "none":
+        return None
+    w = (10.0 ** rng.uniform(-3, 3, (k, b)) * rng.choice([-1.0, 1.0], (k, b))).astype(np.float32)
+    if kind == "zeros":
+        w[:, [1, b // 2, b - 1]] = 0.0
+    elif kind != "wide":
+        raise ValueError(kind)
+    return w
+
+
 @functools.lru_cache(maxsize=None)
 def _build(spec):
     k, q, b, L = len(spec.models), spec.q, spec.b, spec.L
     rng = np.random.default_rng([spec.seed, q, b, L])
     Ms = [build_model(rng, name, q) for name in spec.models]
     A, pi = np.stack([m[0] for m in Ms]), np.stack([m[1] for m in Ms])
-    E = (rng.random((k, b, L, q)) * 0.9 + 0.05).astype(np.float32)
-    if spec.emis in ("holes", "blank0"):
-        E[..., ::5, q // 3] = 0.0                            # emissions below eps: no gradient there
-    elif spec.emis == "rare":
-        rare = rng.random(E.shape) < 0.2
-        rare[..., :min(7, q - 1)] = False
-        E[rare] = 1e-10                                      # far above eps: nothing is clamped
-    elif spec.emis == "dead":                                # the emitter's magnitude, zeros in the constrained states
-        E = E / np.float32(4096)
-        dead = rng.random(E.shape) < 0.3
-        dead[..., :1 + 6 * copies_of(q)] = False
-        E[dead] = 0.0
-    elif spec.emis == "clamp":
-        for m, name in enumerate(spec.models):
-            if name == "fclamp":
-                E[m, ..., q - 1] = 1.0
-    elif spec.emis == "stretch":                             # four positions in a row that state 9 alone can emit
-        t0 = L // 2
-        E[0, STRETCH_SEQ, t0:t0 + STRETCH_LEN, :] = 0.0
-        E[0, STRETCH_SEQ, t0:t0 + STRETCH_LEN, STRETCH_STATE] = 0.5
-    else:
-        raise ValueError(spec.emis)
-    if spec.w == "none":
-        w = None
-    else:
-        w = (10.0 ** rng.uniform(-3, 3, (k, b)) * rng.choice([-1.0, 1.0], (k, b))).astype(np.float32)
-        if spec.w == "zeros":
-            w[:, [1, b // 2, b - 1]] = 0.0
-        elif spec.w != "wide":
-            raise ValueError(spec.w)
+    E = draw_E(rng, spec.models, b, L, q, spec.emis)
+    w = draw_w(rng, k, b, spec.w)
     if spec.emis == "blank0":                                # the whole first row of each model's heaviest sequence:
         E[np.arange(k), np.abs(w).argmax(-1), 0, :] = 0.0    # gamma_0 is pi's and R_0's alone, dpi must not lose it
     out = dict(A=A, pi=pi, E=E, w=w)
@@ -166,43 +190,43 @@ def _build(spec):
     return out
 
 
-def twin(A, pi, E, w):
+def twin(A, pi, E, w, eps=EPS):
     """One model: (dA, dpi, dE, ll) of oracle.ref_cell.loglik_grad, fp32 autograd on the CPU, as fp64 numpy arrays."""
     n = torch.get_num_threads()
     torch.set_num_threads(1)                                 # small matmuls: threads only cost
     try:
         out = ref_cell.loglik_grad(np.array(A)[None], np.array(pi)[None], np.array(E)[None],
-                                   None if w is None else np.array(w)[None])
+                                   None if w is None else np.array(w)[None], eps=eps)
         # (L = 1: A takes no part, autograd leaves its gradient unset)
         return tuple(np.zeros(np.shape(A)) if t is None else np.asarray(t.numpy()[0], np.float64) for t in out)
     finally:
         torch.set_num_threads(n)
 
 
-def oracle64(A, pi, E, w, unmasked=True, grads=None):
+def oracle64(A, pi, E, w, unmasked=True, grads=None, eps=EPS):
     """One model: dict(want=(dA, dpi, dE, ll) fp64, dA_unmasked (None unless asked for), dead=(q,) bool), read-only.
     grads: textbook.loglik_grad(A, pi, E, w) where the caller has it already."""
-    dA, dpi, dE = grads or textbook.loglik_grad(A, pi, E, w)
-    dAu = textbook.loglik_grad(A, pi, E, w, clamp_adjoint=False)[0] if unmasked else None
-    ah, ll = textbook.forward(A, pi, E)
+    dA, dpi, dE = grads or textbook.loglik_grad(A, pi, E, w, eps=eps)
+    dAu = textbook.loglik_grad(A, pi, E, w, eps=eps, clamp_adjoint=False)[0] if unmasked else None
+    ah, ll = textbook.forward(A, pi, E, eps=eps)
     r = dict(want=(dA, dpi, dE, ll[:, -1].copy()), dA_unmasked=dAu, dead=ah.max((0, 1)) <= DEAD)
     for x in r["want"] + (r["dead"],) + (() if dAu is None else (dAu,)):
         x.flags.writeable = False
     return r
 
 
-def with_twin(r, A, pi, E, w, route):
+def with_twin(r, A, pi, E, w, route, eps=EPS):
     """oracle64's entry plus e32={norm: the fp32 twin's error}, limit={fine norm: limit}, small={fine norm: fraction
     excluded} under the route's norms and exclusions."""
-    e32, small = errors(twin(A, pi, E, w), r, A, route, tensor=r["dA_unmasked"] is not None)
+    e32, small = errors(twin(A, pi, E, w, eps), r, A, route, tensor=r["dA_unmasked"] is not None)
     limit = {n: max(FINE_FLOOR, FINE_FACTOR * e32[n]) for n in fine_norms(route)}
     return dict(r, e32=e32, limit=limit, small=small)
 
 
-def fine_check(got, A, pi, E, w, route, tag, grads=None):
+def fine_check(got, A, pi, E, w, route, tag, grads=None, eps=EPS):
     """For tests with inputs of their own: (dA, dpi, dE, ll) of one model under the route's finer norms against the
     fp64 oracle, each at max(2e-4, 4 e32) with e32 measured on these very inputs; prints, then asserts."""
-    r = with_twin(oracle64(A, pi, E, w, unmasked=False, grads=grads), A, pi, E, w, route)
+    r = with_twin(oracle64(A, pi, E, w, unmasked=False, grads=grads, eps=eps), A, pi, E, w, route, eps)
     err, _ = errors(got, r, A, route, tensor=False)
     for n in fine_norms(route):
         print("LLSWEEP %s %s err %.3e limit %.3e e32 %.3e" % (tag, n, err[n], r["limit"][n], r["e32"][n]))
@@ -275,7 +299,7 @@ def errors(got, ref_m, A, route, tensor=True):
     if topA == 0.0:
         small["dA/row"] = 0.0
     e["dE/seq"], small["dE/seq"] = _ratio(errE.max((1, 2)), refE.max((1, 2)), topE)
-    if route == "wave":
+    if route in COL_ROUTES:
         e["dE/col"], small["dE/col"] = _ratio(errE.max((0, 1)), refE.max((0, 1)), topE)
     return e, small
 

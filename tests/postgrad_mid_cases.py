@@ -200,13 +200,14 @@ def _build(spec):
     return out
 
 
-def oracle(A, pi, E, G, log, dtype=torch.float64):
+def oracle(A, pi, E, G, log, dtype=torch.float64, eps=EPS, add_loglik=False):
     """One model: (dA, dpi, dE) of <G, gamma | log gamma> as fp64 numpy arrays, by autograd in `dtype`."""
     n = torch.get_num_threads()
     torch.set_num_threads(1)                                 # small matmuls: threads only cost
     try:
         A, pi, E, G = (np.array(x) for x in (A, pi, E, G))     # writable copies of the read-only inputs
-        return tuple(np.asarray(x, np.float64) for x in torch64.posterior_grad(A, pi, E, G, log=log, dtype=dtype)[:3])
+        out = torch64.posterior_grad(A, pi, E, G, log=log, eps=eps, add_loglik=add_loglik, dtype=dtype)
+        return tuple(np.asarray(x, np.float64) for x in out[:3])
     finally:
         torch.set_num_threads(n)
 

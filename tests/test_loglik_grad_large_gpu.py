@@ -16,6 +16,8 @@ import torch
 from hmm_layer_amd import engine
 from oracle import ref_cell, textbook
 
+import loglik_grad_cases as lc
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 WALK_MAX = 128
@@ -123,7 +125,9 @@ def test_five_copy_gene_model():
 
 
 def test_two_models_weights_and_short_sequences():
-    """k = 2 with separate matrices, grad_loglik with zeros and negative values, L = 1..7 (L = 1: dA = 0)."""
+    """k = 2 with separate matrices, grad_loglik with zeros and negative values, L = 1..7 (L = 1: dA = 0); then the
+    same with the whole first row of each model's heaviest sequence blank (dpi keeps its gamma_0), under the finer
+    norms of tests/largeq_grad_cases.py as well."""
     rng = np.random.default_rng(5)
     q = 90
     m1, m2 = rand_model(rng, q, dead=2), rand_model(rng, q, sparse=True, tiny_pi=3)
@@ -137,6 +141,13 @@ def test_two_models_weights_and_short_sequences():
                 assert np.all(r[0] == 0.0)
         for r in res.values():                           # zero weight: no gradient from that sequence
             assert np.all(r[2][0, 0] == 0.0) and np.all(r[2][1, 1] == 0.0)
+        E0 = E.copy()
+        E0[np.arange(2), np.abs(w).argmax(-1), 0, :] = 0.0
+        for r, got in check_all(A, pi, E0, w, "blank0 L=%d" % L).items():
+            for m in range(2):
+                assert np.all(got[2][m][E0[m] <= 1e-16] == 0.0)
+                lc.fine_check([x[m] for x in got], A[m], pi[m], E0[m], w[m], "lwalk" if r == 1 else "lgemm",
+                              "blank0 L=%d route=%d m=%d" % (L, r, m))
 
 
 @pytest.mark.parametrize("q", [15, 29, 43, 64])

@@ -11,6 +11,8 @@ import torch
 from hmm_layer_amd import engine
 from oracle import ref_cell, torch64
 
+import largeq_grad_cases as lg
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 WALK_MAX = 128
@@ -136,7 +138,9 @@ def test_config5_shape_and_every_gemm_tile(b, q, L, cols):
 
 
 def test_two_models_short_sequences_and_labels():
-    """k = 2 with separate matrices, L = 1..7 (L = 1: dA exactly 0), label-like upstream gradients in log mode."""
+    """k = 2 with separate matrices, L = 1..7 (L = 1: dA exactly 0), label-like upstream gradients in log mode; then
+    the whole first row of each model's sequence 3 blank, under the finer norms of tests/largeq_grad_cases.py as
+    well."""
     rng = np.random.default_rng(5)
     q = 90
     m1, m2 = rand_model(rng, q, dead=2), rand_model(rng, q, sparse=True, tiny_pi=3)
@@ -152,6 +156,12 @@ def test_two_models_short_sequences_and_labels():
             got = run(A, pi, E, G, engine.POST_LOG, r)
             for m in range(2):
                 check_model([x[m] for x in got], A[m], pi[m], E[m], G[m], engine.POST_LOG, "labels L=%d r=%d" % (L, r))
+        E0, G0 = E.copy(), rand_G(np.random.default_rng(50 + L), E.shape)      # (a generator of its own: the draws above stay)
+        E0[:, 3, 0, :] = 0.0
+        for (mode, r), got in check_all(A, pi, E0, G0, "blank0 L=%d" % L).items():
+            for m in range(2):
+                lg.post_fine_check([x[m] for x in got], A[m], pi[m], E0[m], G0[m], mode == engine.POST_LOG,
+                                   "blank0 L=%d mode=%d route=%d m=%d" % (L, mode, r, m))
 
 
 @pytest.mark.parametrize("q", [70, 150])
