@@ -467,6 +467,38 @@ __host__ __device__ constexpr int out_degree(int i) {
 // one edge gives: the gene models' START, EI, IE and STOP states): k_reduce_sparse then never forms
 // x_i = y_i * e_i for those states but feeds (e_i, y_i) straight into the successor's fma.
 #define TOPO_UNIT 16
+// A pass-through state has exactly one incoming and one outgoing edge (START, EI, IE, STOP): with weight 1 on the
+// way out (TOPO_UNIT) it is a pure one-step delay, and the unit-weight sparse reduce runs a second-order recurrence
+// on the remaining (live) states that never forms it (HMM_RS_ORDER2, reduce_sparse_wave).
+template <class T>
+__host__ __device__ constexpr bool passthrough(int j) {
+    return T::start[j + 1] - T::start[j] == 1 && out_degree<T>(j) == 1;
+}
+template <class T>
+__host__ __device__ constexpr int pt_src(int p) { return T::src[T::start[p]]; }      // the one state that feeds p
+template <class T>
+__host__ __device__ constexpr int pt_dst(int p) {                                     // the one state p feeds
+    for (int j = 0; j < T::Q; ++j)
+        for (int e = T::start[j]; e < T::start[j + 1]; ++e)
+            if (T::src[e] == p) return j;
+    return -1;
+}
+template <class T>
+__host__ __device__ constexpr int n_passthrough() {
+    int n = 0;
+    for (int j = 0; j < T::Q; ++j) n += passthrough<T>(j) ? 1 : 0;
+    return n;
+}
+// both neighbours of every pass-through state are live: delays do not chain, the recurrence has order two
+template <class T>
+__host__ __device__ constexpr bool passthrough_between_live() {
+    for (int p = 0; p < T::Q; ++p)
+        if (passthrough<T>(p) && (passthrough<T>(pt_src<T>(p)) || passthrough<T>(pt_dst<T>(p)))) return false;
+    return true;
+}
+static_assert(n_passthrough<TopoGene15>() == 8 && passthrough_between_live<TopoGene15>(), "15-state gene model: 7 live states");
+static_assert(n_passthrough<TopoGene29>() == 16 && passthrough_between_live<TopoGene29>(), "29-state gene model: 13 live states");
+static_assert(n_passthrough<TopoGene7>() == 0, "the 7-state model has no pass-through state");
 // entry (i -> j) of A lies inside topology T's support
 template <class T>
 __device__ __forceinline__ bool edge_in(int i, int j) {
@@ -560,6 +592,14 @@ __global__ __launch_bounds__(64) void k_topo_check(const float *__restrict__ A, 
 #ifndef HMM_RS_SUM2
 #define HMM_RS_SUM2 1      // sparse reduce: the column sum (and the rescale test) every second step
 #endif
+#ifndef HMM_RS_ORDER2
+#define HMM_RS_ORDER2 1    // sparse reduce, unit-weight wave of one model: second-order recurrence on the live states
+                           // (the pass-through states' incoming weight folded into the staged emission)
+#endif
+#ifndef HMM_RS_ROW128
+#define HMM_RS_ROW128 1    // sparse reduce: read a staged row's last three floats together with the pad float: a 16-byte
+                           // LDS read takes 4 LDS cycles per wave, a 12-byte one 8 (A/B: 1.47-1.51 -> 1.37-1.43 ms)
+#endif
 #ifndef HMM_RS_WPE
 #define HMM_RS_WPE 4       // waves per SIMD the register allocator of the 16-lane sparse reduce is held to (0: its own choice)
 #endif
@@ -579,6 +619,7 @@ template <class T> struct RsCfg {
 };
 
 // UNIT: every single-out-edge state of T has weight 1 on its edge (TOPO_UNIT, for all of the wave's chains)
+//       With UNI as well, and pass-through states in T, the wave runs the second-order recurrence (HMM_RS_ORDER2).
 // UNI:  all chains of the wave belong to one model (always, unless k > 1 and the wave straddles two): the
 //       transition weights are then wave-uniform and live in SGPRs — 15 to 23 vector registers that the column
 //       and the emission row need (held to 128 VGPRs for four waves per SIMD, the kernel spilled 26 dwords)
@@ -588,6 +629,11 @@ __device__ __forceinline__ void reduce_sparse_wave(const float *__restrict__ A, 
                                                    float eps, typename RsCfg<T>::Lds &ldsw, long long wchain0,
                                                    bool mine, int m, long long chain, int c) {
     constexpr int Q = T::Q, W = RsCfg<T>::W, CPW = RsCfg<T>::CPW, RPC = RsCfg<T>::RPC;
+    // O2: the second-order recurrence on the live states (see `step`); needs unit weights out of the pass-through
+    // states and ONE model per wave, whose incoming weights are folded into the staged emissions
+    constexpr bool O2 = HMM_RS_ORDER2 && UNIT && UNI && n_passthrough<T>() > 0;
+    static_assert(!O2 || passthrough_between_live<T>(), "a pass-through state between two live states");
+    auto live = [](int j) constexpr { return !O2 || !passthrough<T>(j); };
     const int lane = threadIdx.x & 63, cl = lane / W, kc = lane % W;
     const int t0 = c * p.T;
     const int len = mine ? min(p.T, p.L - t0) : 0;
@@ -628,6 +674,22 @@ __device__ __forceinline__ void reduce_sparse_wave(const float *__restrict__ A, 
             const int idx = 4 * (rr * 64 + lane) + u;
             loff[rr][u] = (idx / Q) * W + (idx % Q);
         }
+    // O2: the staged value of a pass-through state p is e'_p = max(E[p], eps) * a(src(p) -> p): the state of each of
+    // the lane's four floats per piece is fixed, so the factor is a per-lane constant (1 for a live state)
+    float smul[O2 ? RPC : 1][4];
+    if constexpr (O2) {
+#pragma unroll
+        for (int rr = 0; rr < RPC; ++rr)
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int st = (4 * (rr * 64 + lane) + u) % Q;
+                float mv = 1.f;
+#pragma unroll
+                for (int pp = 0; pp < Q; ++pp)
+                    if (passthrough<T>(pp)) mv = (st == pp) ? a[T::start[pp]] : mv;
+                smul[rr][u] = mv;
+            }
+    }
     for (int i = lane; i < 2 * CPW * (SP_TILE * W + 16); i += 64) (&ldsw[0][0][0])[i] = 0.f;   // pad columns = 0
 
     f4 r[CPW * RPC];
@@ -647,10 +709,17 @@ __device__ __forceinline__ void reduce_sparse_wave(const float *__restrict__ A, 
                 for (int j = 0; j < CPW; ++j) {
                     float *dst = &ldsw[buf][j][0];
                     const f4 v = r[j * RPC + rr];
-                    dst[loff[rr][0]] = fmaxf(v.x, eps);     // the cell's max(E, eps), once per value
-                    dst[loff[rr][1]] = fmaxf(v.y, eps);
-                    dst[loff[rr][2]] = fmaxf(v.z, eps);
-                    dst[loff[rr][3]] = fmaxf(v.w, eps);
+                    if constexpr (O2) {
+                        dst[loff[rr][0]] = fmaxf(v.x, eps) * smul[rr][0];
+                        dst[loff[rr][1]] = fmaxf(v.y, eps) * smul[rr][1];
+                        dst[loff[rr][2]] = fmaxf(v.z, eps) * smul[rr][2];
+                        dst[loff[rr][3]] = fmaxf(v.w, eps) * smul[rr][3];
+                    } else {
+                        dst[loff[rr][0]] = fmaxf(v.x, eps);     // the cell's max(E, eps), once per value
+                        dst[loff[rr][1]] = fmaxf(v.y, eps);
+                        dst[loff[rr][2]] = fmaxf(v.z, eps);
+                        dst[loff[rr][3]] = fmaxf(v.w, eps);
+                    }
                 }
             }
         }
@@ -660,12 +729,30 @@ __device__ __forceinline__ void reduce_sparse_wave(const float *__restrict__ A, 
     // y_j and pend[j] the emission it still has to be multiplied with (the true entry is x[j] * pend[j]):
     // its only consumer multiplies by a weight of 1, so (pend[j], x[j]) go straight into that fma and the
     // product is never formed — 8 of the 15 emission multiplies of the 15-state model.
-    float x[Q], pend[Q];
+    // O2: only the live states have an x[j], the column one step back, and an xb[j], the column two steps back; for
+    // a pass-through state p, pend[p] is e'_p of the last row taken and its entry is pend[p] * xb[src(p)], formed
+    // only at the column's end.  A column that STARTS in pass-through state p is a unit of mass in flight: this
+    // lane alone sees pend[p] = 1 in front of its first step, with xb[src(p)] = 1.
+    float x[Q], pend[Q], xb[O2 ? Q : 1];
+    auto flight_src = [&](int i) {       // O2: this lane's start state is a pass-through state fed by state i
+        bool f = false;
 #pragma unroll
-    for (int j = 0; j < Q; ++j) { x[j] = (j == kc) ? 1.f : 0.f; pend[j] = 1.f; }
+        for (int pp = 0; pp < Q; ++pp)
+            if (passthrough<T>(pp) && pt_src<T>(pp) == i) f = f || (kc == pp);
+        return f;
+    };
+#pragma unroll
+    for (int j = 0; j < Q; ++j) {
+        x[j] = (j == kc) ? 1.f : 0.f;
+        pend[j] = 1.f;
+        if constexpr (O2) {
+            pend[j] = x[j];
+            xb[j] = flight_src(j) ? 1.f : 0.f;
+        }
+    }
     int ex = 0;
     float cs = (kc < Q) ? 1.f : 0.f;     // sum of the column as currently scaled
-    auto deferred = [](int j) constexpr { return UNIT && out_degree<T>(j) == 1; };
+    auto deferred = [](int j) constexpr { return !O2 && UNIT && out_degree<T>(j) == 1; };
 
     // exact power-of-two rescale of the column (sum back into [0.5, 1)).  The exponent is clamped
     // so that the factor cannot overflow when a column has underflowed to a denormal or to zero
@@ -682,16 +769,30 @@ __device__ __forceinline__ void reduce_sparse_wave(const float *__restrict__ A, 
         int xe = max(__builtin_amdgcn_frexp_expf(cs), -100);
         float sc = __builtin_amdgcn_ldexpf(1.0f, -xe);
 #pragma unroll
-        for (int j = 0; j < Q; ++j) x[j] *= sc;
+        for (int j = 0; j < Q; ++j) {
+            if (live(j)) x[j] *= sc;
+            if constexpr (O2) { if (live(j)) xb[j] *= sc; }       // (mass in flight scales through xb)
+        }
         cs *= sc;
         ex += xe;
     };
 
     // finalise and store this lane's operator column (called once, at the lane's last step)
+    auto entry = [&](int j) {            // entry j of the column as it stands
+        if constexpr (O2) return live(j) ? x[j] : pend[j] * xb[pt_src<T>(j)];
+        else return deferred(j) ? x[j] * pend[j] : x[j];
+    };
     auto column_sum = [&]() {
         float s = 0.f;
+        if constexpr (O2) {
 #pragma unroll
-        for (int j = 0; j < Q; ++j) s += deferred(j) ? x[j] * pend[j] : x[j];
+            for (int j = 0; j < Q; ++j) if (live(j)) s += x[j];
+#pragma unroll
+            for (int j = 0; j < Q; ++j) if (!live(j)) s = fmaf(pend[j], xb[pt_src<T>(j)], s);
+        } else {
+#pragma unroll
+            for (int j = 0; j < Q; ++j) s += entry(j);
+        }
         return s;
     };
     auto finish = [&]() {
@@ -699,7 +800,7 @@ __device__ __forceinline__ void reduce_sparse_wave(const float *__restrict__ A, 
         rescale();
         float *o = ops + (size_t)chain * W * W;
 #pragma unroll
-        for (int j = 0; j < Q; ++j) o[j * W + kc] = (kc < Q) ? (deferred(j) ? x[j] * pend[j] : x[j]) : 0.f;
+        for (int j = 0; j < Q; ++j) o[j * W + kc] = (kc < Q) ? entry(j) : 0.f;
 #pragma unroll
         for (int j = Q; j < W; ++j) o[j * W + kc] = 0.f;
         static_assert(Q < W, "the exponent row's last lane is a pad lane");
@@ -718,26 +819,61 @@ __device__ __forceinline__ void reduce_sparse_wave(const float *__restrict__ A, 
     // the operators carry no floor.  From the threshold two steps of the smallest emissions a realistic path
     // sees (2^-32: a free state's 1/4096 times a class probability of 1e-6) stay normal numbers; a column that
     // loses more than that in two steps has met two impossible observations and weighs nothing.
+    //
+    // O2.  A pass-through state p only delays its source's mass by a step: x_p(t) = e_p(t) a(i->p) x_i(t-1), all of
+    // which moves on to p's one successor with weight 1.  With e'_p = e_p a(i->p) staged once per emission value
+    // (the product is the same for all Q columns of a chain) the live states obey
+    //     y_j(t) = sum_{live i->j} a_ij x_i(t-1)  +  sum_{p->j} e'_p(t-1) x_src(p)(t-2),      x_j(t) = y_j(t) e_j(t)
+    // 15-state model: 7 multiplies + 8 fma's + 7 emission multiplies = 22 per step for 30, and no pass-through
+    // value inside the loop.  The true column sum is sum_live x_j(t) + sum_p e'_p(t) x_src(p)(t-1): the same number
+    // as before, so threshold, risk mark and the argument above stand; x and xb take the same power of two.
     auto step = [&](const float (&e)[Q], auto sumc) {
         constexpr bool SUM = decltype(sumc)::value;
         float y[Q];
-#pragma unroll
-        for (int j = 0; j < Q; ++j) {
-            float acc = 0.f;
-#pragma unroll
-            for (int ed = T::start[j]; ed < T::start[j + 1]; ++ed) {
-                const int i = T::src[ed];
-                const float w = deferred(i) ? pend[i] : a[ed];               // weight 1: the pending emission instead
-                acc = (ed == T::start[j]) ? w * x[i] : fmaf(w, x[i], acc);
-            }
-            y[j] = acc;
-        }
         float s = 0.f;
+        if constexpr (O2) {
 #pragma unroll
-        for (int j = 0; j < Q; ++j) {
-            if (SUM) s = fmaf(y[j], e[j], s);
-            if (deferred(j)) { x[j] = y[j]; pend[j] = e[j]; }
-            else x[j] = y[j] * e[j];
+            for (int j = 0; j < Q; ++j) {
+                if (!live(j)) continue;
+                float acc = 0.f;
+                bool any = false;
+#pragma unroll
+                for (int pass = 0; pass < 2; ++pass)            // the direct edges first, then the delayed ones
+#pragma unroll
+                    for (int ed = T::start[j]; ed < T::start[j + 1]; ++ed) {
+                        const int i = T::src[ed];
+                        if (live(i) != (pass == 0)) continue;
+                        const float w = live(i) ? a[ed] : pend[i];
+                        const float v = live(i) ? x[i] : xb[pt_src<T>(i)];
+                        acc = any ? fmaf(w, v, acc) : w * v;
+                        any = true;
+                    }
+                y[j] = acc;
+            }
+#pragma unroll
+            for (int j = 0; j < Q; ++j) {
+                if (live(j)) { xb[j] = x[j]; x[j] = y[j] * e[j]; }
+                else pend[j] = e[j];
+            }
+            if (SUM) s = column_sum();
+        } else {
+#pragma unroll
+            for (int j = 0; j < Q; ++j) {
+                float acc = 0.f;
+#pragma unroll
+                for (int ed = T::start[j]; ed < T::start[j + 1]; ++ed) {
+                    const int i = T::src[ed];
+                    const float w = deferred(i) ? pend[i] : a[ed];           // weight 1: the pending emission instead
+                    acc = (ed == T::start[j]) ? w * x[i] : fmaf(w, x[i], acc);
+                }
+                y[j] = acc;
+            }
+#pragma unroll
+            for (int j = 0; j < Q; ++j) {
+                if (SUM) s = fmaf(y[j], e[j], s);
+                if (deferred(j)) { x[j] = y[j]; pend[j] = e[j]; }
+                else x[j] = y[j] * e[j];
+            }
         }
         if (SUM) {
             // (32-lane rows — the 29-state model: a column that loses more than 2^-45 between two sums has met an
@@ -757,9 +893,11 @@ __device__ __forceinline__ void reduce_sparse_wave(const float *__restrict__ A, 
         }
     };
 
-    // exactly Q floats of a staged row: whole 16-byte reads plus one 12- / 8- / 4-byte read.  (Reading
-    // the pad too leaves a dead destination register that the allocator hands out again at once: the
-    // prefetch then has to be waited for on the spot.)
+    // Q floats of a staged row: whole 16-byte reads plus one 8- / 4-byte read.  Three floats at the end are read
+    // with the pad float behind them (HMM_RS_ROW128): the LDS serves a wave's 16-byte read in 4 cycles and its
+    // 12-byte read in 8, and with the second-order step the LDS is as busy as the vector unit (the look-ahead copy
+    // of a row, HMM_RS_AHEAD, is what the dead fourth register hurt: the allocator hands it out again at once and
+    // the prefetch then has to be waited for on the spot).
     auto ldrow = [&](const float *rowp, float (&r)[Q]) {
 #pragma unroll
         for (int v = 0; v + 4 <= Q; v += 4) {
@@ -767,7 +905,11 @@ __device__ __forceinline__ void reduce_sparse_wave(const float *__restrict__ A, 
             r[v] = t.x; r[v + 1] = t.y; r[v + 2] = t.z; r[v + 3] = t.w;
         }
         constexpr int R0 = Q & ~3;
-        if constexpr (Q - R0 == 3) {
+        if constexpr (Q - R0 == 3 && HMM_RS_ROW128) {
+            static_assert(R0 + 4 <= W, "the pad float belongs to the row");
+            const f4 t = *reinterpret_cast<const f4 *>(rowp + R0);
+            r[R0] = t.x; r[R0 + 1] = t.y; r[R0 + 2] = t.z;
+        } else if constexpr (Q - R0 == 3) {
             typedef float f3 __attribute__((ext_vector_type(3)));
             const f3 t = *reinterpret_cast<const f3 *>(rowp + R0);
             r[R0] = t.x; r[R0 + 1] = t.y; r[R0 + 2] = t.z;
@@ -803,12 +945,20 @@ __device__ __forceinline__ void reduce_sparse_wave(const float *__restrict__ A, 
             // X = diag(E_0); everyone else takes the generic step
             float xs[Q];
 #pragma unroll
-            for (int j = 0; j < Q; ++j) xs[j] = x[j];
+            for (int j = 0; j < Q; ++j) xs[j] = O2 ? (j == kc ? 1.f : 0.f) : x[j];
+            // (O2: the staged value of a pass-through state carries its incoming weight: the row itself instead)
+            float e0 = 1.f;
+            if constexpr (O2) { if (first && mine && kc < Q) e0 = fmaxf(E[(chain / p.C) * (long long)p.L * Q + kc], eps); }
             step(c, std::true_type());
             if (first) {
-                const float e0 = tp[kc < Q ? kc : 0];
+                if constexpr (!O2) e0 = tp[kc < Q ? kc : 0];
 #pragma unroll
-                for (int j = 0; j < Q; ++j) { x[j] = xs[j] * e0; pend[j] = 1.f; }      // xs = unit column kc
+                for (int j = 0; j < Q; ++j) {                                            // xs = unit column kc
+                    x[j] = xs[j] * e0;
+                    pend[j] = 1.f;
+                    // O2: e0 on a pass-through state is mass in flight, as at a chunk's start but with weight e0
+                    if constexpr (O2) { pend[j] = x[j]; xb[j] = flight_src(j) ? 1.f : 0.f; }
+                }
                 cs = (kc < Q) ? e0 : 0.f;
                 ex = 0;
                 rescale();
