@@ -3029,6 +3029,7 @@ int hmm_loglik_partials(const double *loglik, const float *weights, int k, int b
 
 #include "hmm_seqshard.inc"
 #include "hmm_viterbi.inc"
+#include "hmm_seqshard_viterbi.inc"
 #include "hmm_viterbi_scan.inc"
 #include "hmm_viterbi_large.inc"
 #include "hmm_emitter.inc"

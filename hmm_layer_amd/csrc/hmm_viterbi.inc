@@ -212,7 +212,7 @@ __global__ __launch_bounds__(256) void k_vit_reduce(const float *__restrict__ lo
     const long long chn = inrange ? chain : wchain0;
     const int seq = (int)(chn / p.C), c = (int)(chn - (long long)seq * p.C);
     const int len = inrange ? min(p.T, p.L - c * p.T) : 0;
-    const bool first = (c == 0);
+    const bool first = (c == 0) && p.seq_start;        // (a later time slab's chunk 0 is an ordinary chunk)
     const VStage st = make_vstage(logE, p, wchain0, lane);
     int *xw = &xs[w][0][0][0];
     // column kc of the identity in the max-plus sense is not representable with bounded spread;
@@ -290,7 +290,7 @@ __device__ __forceinline__ void vit_reduce_sparse_body(const float *__restrict__
     const long long chn = inrange ? chain : wchain0;
     const int seq = (int)(chn / p.C), c = (int)(chn - (long long)seq * p.C);
     const int len = inrange ? min(p.T, p.L - c * p.T) : 0;
-    const bool first = (c == 0);
+    const bool first = (c == 0) && p.seq_start;        // (a later time slab's chunk 0 is an ordinary chunk)
     const int a_off = M.a_off;
     int a[T::NE];
 #pragma unroll
@@ -507,8 +507,9 @@ __global__ __launch_bounds__(256) void k_vit_scan_compose(const int *__restrict_
         wb = k < q ? wb + mx : 0;
     }
 #pragma unroll
-    for (int r = 0; r < 4; ++r) gvops[(size_t)wv * QP * QP + (4 * ig + r) * QP + k] = wr[r];
-    if (ig == 0) gvbase[(size_t)wv * QP + k] = wb;
+    // (a group of one chunk is that chunk's operator, whose columns from q on were never written: they leave as 0)
+    for (int r = 0; r < 4; ++r) gvops[(size_t)wv * QP * QP + (4 * ig + r) * QP + k] = k < q ? wr[r] : 0;
+    if (ig == 0) gvbase[(size_t)wv * QP + k] = k < q ? wb : 0;
 }
 
 // one block per (sequence, group): the hops of the single-level scan over the group's chunks, from the
@@ -524,7 +525,7 @@ __global__ __launch_bounds__(64) void k_vit_scan_inner(const int *__restrict__ v
     const int c0 = grp * p.gsize, c1 = min(p.C, c0 + p.gsize);
     const size_t chain0 = (size_t)seq * p.C;
     long long d;
-    if (grp == 0) {
+    if (grp == 0 && p.seq_start) {
         d = (i < q) ? (long long)vops[chain0 * QP * QP + i * QP + 0] + vbase[chain0 * QP + 0] : 0;
     } else {
         // scores entering chunk c0: recorded for the chunk itself, then through its operator
@@ -566,7 +567,7 @@ __global__ __launch_bounds__(256) void k_vit_apply(const float *__restrict__ log
     const int seq = (int)(chn / p.C), c = (int)(chn - (long long)seq * p.C);
     const int t0 = c * p.T;
     const int len = inrange ? min(p.T, p.L - t0) : 0;
-    const bool first = (c == 0);
+    const bool first = (c == 0) && p.seq_start;        // (a later time slab's chunk 0 is an ordinary chunk)
     const bool act_state = j < q;
     const int e0 = M.rowptr[j], e1 = M.rowptr[j + 1], a_off = M.a_off;
     const VStage st = make_vstage(logE, p, wchain0, lane);
@@ -672,7 +673,7 @@ __global__ __launch_bounds__(64) void k_vit_apply_sparse(const float *__restrict
     const int c = (int)(chn - seq * p.C);
     const int t0 = c * p.T;
     const int len = inrange ? min(p.T, p.L - t0) : 0;
-    const bool first = (c == 0);
+    const bool first = (c == 0) && p.seq_start;        // (a later time slab's chunk 0 is an ordinary chunk)
     // emission rows: 32-bit offsets from the wave's first row, range-checked by the descriptor
     const long long seq0 = wchain0 / p.C;
     const long long row0 = seq0 * p.L + (wchain0 - seq0 * p.C) * p.T;
@@ -809,6 +810,9 @@ __global__ void k_vit_scan_bwd(const unsigned char *__restrict__ forig, const in
 // ---- two-level backward scan: the maps "state at chunk end -> state before the chunk" compose exactly.
 // k_vit_bwd_compose: per (sequence, group) the map of the whole group; k_vit_scan_bwd over the groups gives
 // the state at every group's end; k_vit_bwd_inner walks the chunks of every group in parallel.
+// SLAB (hmm_seqshard_viterbi.inc): the groups are whole time slabs, whose chunk 0 has a map of its own unless the slab
+// starts its sequence; entries that mean nothing (states from q on, a slab that starts its sequence) leave as 0
+template <bool SLAB>
 __global__ void k_vit_bwd_compose(const unsigned char *__restrict__ forig, unsigned char *__restrict__ gforig, Plan p) {
     const long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x;       // (sequence, group, end state)
     if (id >= (long long)p.NB * p.G * QP) return;
@@ -817,7 +821,8 @@ __global__ void k_vit_bwd_compose(const unsigned char *__restrict__ forig, unsig
     const int seq = (int)(wv / p.G), grp = (int)(wv - (long long)seq * p.G);
     const int c0 = grp * p.gsize, c1 = min(p.C, c0 + p.gsize);
     int s = j;
-    for (int c = c1 - 1; c >= c0; --c) s = forig[((size_t)seq * p.C + c) * QP + s] & 15;    // (chunk 0's map is never used)
+    for (int c = c1 - 1; c >= c0; --c) s = forig[((size_t)seq * p.C + c) * QP + s] & 15;    // (hmm_viterbi never uses chunk 0's map)
+    if (SLAB && (j >= p.q || p.seq_start)) s = 0;
     gforig[(size_t)wv * QP + j] = (unsigned char)s;
 }
 
@@ -1284,6 +1289,19 @@ static int vit_groups(int b, int L, int q, VGroups *G) {
     return HMM_OK;
 }
 
+// the chunk operators of one model's chains (the kernel that does not serve the model returns at once)
+static void vit_launch_reduce(const float *Em, const VPlan &v, char *ws, const VModel *model, int q, hipStream_t st) {
+    const Plan &p = v.p;
+    int *vops = (int *)(ws + v.o_vops);
+    long long *vbase = (long long *)(ws + v.o_vbase);
+    const unsigned nb16 = (unsigned)((p.nchains + 15) / 16);
+    if (q == TopoGene15::Q)
+        hipLaunchKernelGGL(k_vit_reduce_sparse<TopoGene15>, dim3(nb16), dim3(256), 0, st, Em, model, vops, vbase, p);
+    else if (q == TopoGene7::Q)
+        hipLaunchKernelGGL(k_vit_reduce_sparse<TopoGene7>, dim3(nb16), dim3(256), 0, st, Em, model, vops, vbase, p);
+    hipLaunchKernelGGL(k_vit_reduce, dim3(nb16), dim3(256), 0, st, Em, model, vops, vbase, p);
+}
+
 // reduce + chunk scan of one group (scores -> score), on st
 static void vit_phase_a(const float *Em, const VPlan &v, char *ws, const VModel *model, double *score, int q,
                         hipStream_t st) {
@@ -1293,12 +1311,7 @@ static void vit_phase_a(const float *Em, const VPlan &v, char *ws, const VModel 
     int *dstart = (int *)(ws + v.o_dstart);
     long long *dbase = (long long *)(ws + v.o_dbase);
     int *sfinal = (int *)(ws + v.o_sfinal);
-    const unsigned nb16 = (unsigned)((p.nchains + 15) / 16);
-    if (q == TopoGene15::Q)
-        hipLaunchKernelGGL(k_vit_reduce_sparse<TopoGene15>, dim3(nb16), dim3(256), 0, st, Em, model, vops, vbase, p);
-    else if (q == TopoGene7::Q)
-        hipLaunchKernelGGL(k_vit_reduce_sparse<TopoGene7>, dim3(nb16), dim3(256), 0, st, Em, model, vops, vbase, p);
-    hipLaunchKernelGGL(k_vit_reduce, dim3(nb16), dim3(256), 0, st, Em, model, vops, vbase, p);
+    vit_launch_reduce(Em, v, ws, model, q, st);
     const bool two = p.G > 0 && opt(HMM_OPT_SCAN2) != 0;
     if (!two) {
         hipLaunchKernelGGL(k_vit_scan_fwd, dim3(p.NB), dim3(64), 0, st, (const int *)vops, (const long long *)vbase,
@@ -1318,22 +1331,29 @@ static void vit_phase_a(const float *Em, const VPlan &v, char *ws, const VModel 
     }
 }
 
-// in-chunk pass, backward chunk scan and backtrace of one group (-> path), on st
-static void vit_phase_b(const float *Em, const VPlan &v, char *ws, const VModel *model, int32_t *path, int q,
-                        hipStream_t st) {
+// the in-chunk pass of one model's chains from the scores entering them: backpointers and the chunks' maps
+static void vit_launch_apply(const float *Em, const VPlan &v, char *ws, const VModel *model, int q, hipStream_t st) {
     const Plan &p = v.p;
     const int *dstart = (const int *)(ws + v.o_dstart);
     unsigned char *forig = (unsigned char *)(ws + v.o_forig);
-    int *send = (int *)(ws + v.o_send);
-    const int *sfinal = (const int *)(ws + v.o_sfinal);
     unsigned long long *bp = (unsigned long long *)(ws + v.o_bp);
     const unsigned nb16 = (unsigned)((p.nchains + 15) / 16), nb64 = (unsigned)((p.nchains + 63) / 64);
-    const bool two = p.G > 0 && opt(HMM_OPT_SCAN2) != 0;
     if (q == TopoGene15::Q)
         hipLaunchKernelGGL(k_vit_apply_sparse<TopoGene15>, dim3(nb64), dim3(64), 0, st, Em, model, dstart, forig, bp, p);
     else if (q == TopoGene7::Q)
         hipLaunchKernelGGL(k_vit_apply_sparse<TopoGene7>, dim3(nb64), dim3(64), 0, st, Em, model, dstart, forig, bp, p);
     hipLaunchKernelGGL(k_vit_apply, dim3(nb16), dim3(256), 0, st, Em, model, dstart, forig, (unsigned int *)bp, p);
+}
+
+// backward chunk scan from the sequences' end states (o_sfinal) and backtrace (-> path), on st; gforig_ready: the
+// groups' maps are already in the workspace
+static void vit_launch_backtrace(const VPlan &v, char *ws, int32_t *path, bool gforig_ready, hipStream_t st) {
+    const Plan &p = v.p;
+    unsigned char *forig = (unsigned char *)(ws + v.o_forig);
+    int *send = (int *)(ws + v.o_send);
+    const int *sfinal = (const int *)(ws + v.o_sfinal);
+    unsigned long long *bp = (unsigned long long *)(ws + v.o_bp);
+    const bool two = p.G > 0 && opt(HMM_OPT_SCAN2) != 0;
     if (!two) {
         hipLaunchKernelGGL(k_vit_scan_bwd, dim3((p.NB + 63) / 64), dim3(64), 0, st, (const unsigned char *)forig, sfinal,
                            send, p);
@@ -1341,8 +1361,9 @@ static void vit_phase_b(const float *Em, const VPlan &v, char *ws, const VModel 
         unsigned char *gforig = (unsigned char *)(ws + v.o_gforig);
         int *gsend = (int *)(ws + v.o_gsend);
         const long long nwv = (long long)p.NB * p.G;
-        hipLaunchKernelGGL(k_vit_bwd_compose, dim3((unsigned)((nwv * QP + 255) / 256)), dim3(256), 0, st,
-                           (const unsigned char *)forig, gforig, p);
+        if (!gforig_ready)
+            hipLaunchKernelGGL(k_vit_bwd_compose<false>, dim3((unsigned)((nwv * QP + 255) / 256)), dim3(256), 0, st,
+                               (const unsigned char *)forig, gforig, p);
         Plan pg = p;
         pg.C = p.G;
         hipLaunchKernelGGL(k_vit_scan_bwd, dim3((p.NB + 63) / 64), dim3(64), 0, st, (const unsigned char *)gforig, sfinal,
@@ -1352,6 +1373,13 @@ static void vit_phase_b(const float *Em, const VPlan &v, char *ws, const VModel 
     }
     hipLaunchKernelGGL(k_vit_backtrace, dim3((unsigned)((p.nchains + 63) / 64)), dim3(64), 0, st,
                        (const unsigned long long *)bp, (const int *)send, path, p);
+}
+
+// in-chunk pass, backward chunk scan and backtrace of one group (-> path), on st
+static void vit_phase_b(const float *Em, const VPlan &v, char *ws, const VModel *model, int32_t *path, int q,
+                        hipStream_t st) {
+    vit_launch_apply(Em, v, ws, model, q, st);
+    vit_launch_backtrace(v, ws, path, false, st);
 }
 
 extern "C" size_t hmm_viterbi_workspace_bytes(int k, int b, int L, int q) {

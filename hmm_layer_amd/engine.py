@@ -126,6 +126,11 @@ _SIGNATURES = {
     "hmm_seqshard_workspace_bytes": (_SZ, [_I] * 5),
     "hmm_seqshard_reduce": (_I, [_P, _P, _I, _I, _I, _I, _F, _I, _I, _P, _P, _P, _SZ, _P]),
     "hmm_seqshard_posterior": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _SZ, _P]),
+    "hmm_seqshard_viterbi_max_states": (_I, []),
+    "hmm_seqshard_viterbi_workspace_bytes": (_SZ, [_I] * 5),
+    "hmm_seqshard_viterbi_reduce": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
+    "hmm_seqshard_viterbi_apply": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P, _SZ, _P]),
+    "hmm_seqshard_viterbi_path": (_I, [_I, _I, _I, _I, _P, _P, _I, _I, _P, _P, _SZ, _P]),
 }
 
 
@@ -778,6 +783,81 @@ def seqshard_posterior(A, pi, E_slab, all_ops, all_exps, r, mode=POST_PROB, eps=
                                             out.data_ptr(), ll.data_ptr(), phi.data_ptr(), ws.data_ptr(), ws.numel(),
                                             _stream(E.device)))
     return out, ll, phi
+
+
+def _seqshard_viterbi_ws(dims, R, device):
+    q = dims[3]
+    if q > lib().hmm_seqshard_viterbi_max_states():
+        raise ValueError("sequence-sharded Viterbi covers q <= %d states, got %d"
+                         % (lib().hmm_seqshard_viterbi_max_states(), q))
+    need = lib().hmm_seqshard_viterbi_workspace_bytes(*dims, int(R))
+    if need == 0:
+        raise ValueError("bad sequence-sharded Viterbi call: (k, b, Ls, q) = %s, R = %d" % (tuple(dims), R))
+    return _workspace(device, need, "seqshard_viterbi")
+
+
+def _log_model(logA, logpi, logE_slab):
+    logA, logpi, logE = _dev(logA, "logA"), _dev(logpi, "logpi"), _dev(logE_slab, "logE_slab")
+    logA, logpi, dims = _shapes(logA, logE, logpi)
+    return logA.contiguous(), logpi.contiguous(), logE, dims
+
+
+def seqshard_viterbi_reduce(logA, logpi, logE_slab, seq_start, R):
+    """Step 1 of the sequence-sharded Viterbi (include/hmm_engine.h): this rank's time slab logE_slab (k,b,Ls,q) of
+    log-probabilities -> its max-plus operator per sequence, slab_vop (k,b,16,16) int32 (every column has maximum 0)
+    and slab_vbase (k,b,16) int64.  The chunk operators stay in this device's "seqshard_viterbi" workspace (one per
+    stream) for seqshard_viterbi_apply."""
+    logA, logpi, logE, dims = _log_model(logA, logpi, logE_slab)
+    k, b = dims[:2]
+    with torch.cuda.device(logE.device):
+        ws = _seqshard_viterbi_ws(dims, R, logE.device)
+        vop = torch.empty((k, b, 16, 16), dtype=torch.int32, device=logE.device)
+        vbase = torch.empty((k, b, 16), dtype=torch.int64, device=logE.device)
+        _check(lib().hmm_seqshard_viterbi_reduce(logA.data_ptr(), logpi.data_ptr(), logE.data_ptr(), *dims,
+                                                 int(bool(seq_start)), int(R), vop.data_ptr(), vbase.data_ptr(),
+                                                 ws.data_ptr(), ws.numel(), _stream(logE.device)))
+    return vop, vbase
+
+
+def seqshard_viterbi_apply(logA, logpi, logE_slab, all_vops, all_vbases, r):
+    """Step 3: all_vops (k,b,R,16,16) int32 / all_vbases (k,b,R,16) int64 = every rank's slab operators in time order
+    -> (origin (k,b,16) uint8: the state before the slab of the best path into every state at the slab's last
+    position; final_state (k,b) int32 and score (k,b) fp64 of the WHOLE sequences, the same on every rank).  The
+    backpointers stay in the workspace for seqshard_viterbi_path."""
+    logA, logpi, logE, dims = _log_model(logA, logpi, logE_slab)
+    all_vops, all_vbases = _dev(all_vops, "all_vops", torch.int32), _dev(all_vbases, "all_vbases", torch.int64)
+    k, b = dims[:2]
+    R = all_vops.shape[2] if all_vops.dim() == 5 else 0
+    if tuple(all_vops.shape) != (k, b, R, 16, 16) or tuple(all_vbases.shape) != (k, b, R, 16):
+        raise ValueError("all_vops / all_vbases must have shapes (k,b,R,16,16) / (k,b,R,16)")
+    with torch.cuda.device(logE.device):
+        ws = _seqshard_viterbi_ws(dims, R, logE.device)
+        origin = torch.empty((k, b, 16), dtype=torch.uint8, device=logE.device)
+        final_state = torch.empty((k, b), dtype=torch.int32, device=logE.device)
+        score = torch.empty((k, b), dtype=torch.float64, device=logE.device)
+        _check(lib().hmm_seqshard_viterbi_apply(logA.data_ptr(), logpi.data_ptr(), logE.data_ptr(), *dims, int(r == 0),
+                                                all_vops.data_ptr(), all_vbases.data_ptr(), int(R), int(r),
+                                                origin.data_ptr(), final_state.data_ptr(), score.data_ptr(),
+                                                ws.data_ptr(), ws.numel(), _stream(logE.device)))
+    return origin, final_state, score
+
+
+def seqshard_viterbi_path(dims, all_origins, final_state, r):
+    """Step 5: dims = (k, b, Ls, q) of this rank's slab, all_origins (k,b,R,16) uint8 = every rank's origin in time
+    order, final_state (k,b) int32 -> path (k,b,Ls) int32, this slab's piece of the most probable path."""
+    k, b, Ls, q = (int(d) for d in dims)
+    all_origins = _dev(all_origins, "all_origins", torch.uint8)
+    final_state = _dev(final_state, "final_state", torch.int32)
+    R = all_origins.shape[2] if all_origins.dim() == 4 else 0
+    if tuple(all_origins.shape) != (k, b, R, 16) or tuple(final_state.shape) != (k, b):
+        raise ValueError("all_origins / final_state must have shapes (k,b,R,16) / (k,b)")
+    device = all_origins.device
+    with torch.cuda.device(device):
+        ws = _seqshard_viterbi_ws((k, b, Ls, q), R, device)
+        path = torch.empty((k, b, Ls), dtype=torch.int32, device=device)
+        _check(lib().hmm_seqshard_viterbi_path(k, b, Ls, q, all_origins.data_ptr(), final_state.data_ptr(), int(R),
+                                               int(r), path.data_ptr(), ws.data_ptr(), ws.numel(), _stream(device)))
+    return path
 
 
 def loglik_allreduce(comm, partial):

@@ -16,9 +16,24 @@ engine's limit are decided by the cell's eps clamps, which cannot be cut in time
 their slabs to one rank, runs the unsharded call there and returns every rank its own slab of the result
 (point-to-point, nothing is broadcast).
 
+The most probable path is cut the same way (viterbi(), include/hmm_engine.h: hmm_seqshard_viterbi_*).  Integer
+max-plus is exactly associative, so there is no clamp regime, no certificate and no gather_flagged: the path and the
+score are those of the unsharded engine.viterbi, bit for bit.
+
+    reduce      local     the slab's max-plus operator per sequence               (hmm_seqshard_viterbi_reduce)
+    all-gather  RCCL      twice: the operators (k,b,16,16) int32 and their bases (k,b,16) int64 per rank
+    apply       local     hops over the R slab operators, local chunk scan, in-chunk pass with backpointers,
+                          the slab's map "state at its end -> state before it"    (hmm_seqshard_viterbi_apply)
+    all-gather  RCCL      the maps, (k,b,16) bytes per rank
+    path        local     the final state through the later slabs' maps, backward chunk scan, backtrace
+                                                                              (hmm_seqshard_viterbi_path)
+
+Again three collectives, all latency-sized.  The caller produces its slab of emissions with whatever halo its
+emitter needs (the gene emitter's 3-mers read two neighbours on each side); no halo is exchanged here.
+
 `backend` is the compute provider of the local steps: the HIP engine (default), or anything with the same
 three methods (tests/seqshard_ref.py drives the exchange on CPU tensors over gloo with an fp64
-restatement).  There is no CPU compute in this module.
+restatement, tests/seqshard_viterbi_ref.py the same for viterbi() in int64).  There is no CPU compute in this module.
 """
 import torch
 
@@ -125,3 +140,44 @@ def gather_flagged(A, pi, E_slab, out, loglik, needs_unsharded, mode=engine.POST
         out[m, seqs] = piece.to(out.dtype)
         loglik[m, seqs] = ll[0].to(loglik.dtype)
     return out, loglik
+
+
+class ViterbiEngineBackend:
+    """The local steps of viterbi() on the HIP engine (through the C ABI)."""
+
+    def reduce(self, logA, logpi, logE_slab, seq_start, R):
+        return engine.seqshard_viterbi_reduce(logA, logpi, logE_slab, seq_start, R)
+
+    def apply(self, logA, logpi, logE_slab, all_vops, all_vbases, r):
+        return engine.seqshard_viterbi_apply(logA, logpi, logE_slab, all_vops, all_vbases, r)
+
+    def path(self, dims, all_origins, final_state, r):
+        return engine.seqshard_viterbi_path(dims, all_origins, final_state, r)
+
+
+def _all_gather_stacked(x, R, group):
+    """Every rank's `x` in rank order, stacked behind the (k, b) axes: (k,b,...) -> (k,b,R,...), contiguous."""
+    import torch.distributed as dist
+    parts = [torch.empty_like(x) for _ in range(R)]
+    dist.all_gather(parts, x.contiguous(), group=group)
+    return torch.stack(parts, dim=2).contiguous()
+
+
+def viterbi(logA, logpi, logE_slab, group=None, backend=None):
+    """-> (path_slab (k,b,Ls) int32: this rank's piece of the most probable paths, score (k,b) fp64 of the whole
+    sequences, the same on every rank).
+
+    logA (k,q,q), logpi (k,q), logE_slab (k,b,Ls,q) fp32 log-probabilities with engine.viterbi's semantics (Q16 fixed
+    point, lowest-index tie-breaks), q <= 16.  Ranks of `group` hold consecutive time slabs in rank order (rank 0 owns
+    position 0); slab lengths may differ.  The concatenation of the ranks' paths and the score equal engine.viterbi's on
+    the uncut tensor bit for bit."""
+    import torch.distributed as dist
+    backend = backend or ViterbiEngineBackend()
+    R = dist.get_world_size(group)
+    r = dist.get_rank(group)
+    vop, vbase = backend.reduce(logA, logpi, logE_slab, r == 0, R)
+    all_vops = _all_gather_stacked(vop, R, group)
+    all_vbases = _all_gather_stacked(vbase, R, group)
+    origin, final_state, score = backend.apply(logA, logpi, logE_slab, all_vops, all_vbases, r)
+    all_origins = _all_gather_stacked(origin, R, group)
+    return backend.path(tuple(logE_slab.shape), all_origins, final_state, r), score

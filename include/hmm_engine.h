@@ -599,6 +599,62 @@ int hmm_seqshard_posterior(const float *A, const float *pi, const float *E, int 
                            void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * Sequence-sharded Viterbi: the same cut — every rank owns one contiguous TIME slab of every sequence, logE_slab
+ * (k,b,Ls,q) log-probabilities, Ls may differ between ranks — for the most probable path.  Semantics are exactly
+ * hmm_viterbi's (Q(x) = rint(clip(x, -1024, 1024) * 65536), lowest-index tie-breaks, entries equal to the matrix
+ * minimum are absent edges), and so are the results, bit for bit: integer max-plus is exactly associative.
+ * q <= hmm_seqshard_viterbi_max_states() (16 = hmm_scan_max_states()).  Protocol, R ranks, rank r (slabs in time
+ * order, rank r owns positions [t_r, t_{r+1})):
+ *   1. hmm_seqshard_viterbi_reduce(...) -> slab_vop (k,b,16,16) int32, slab_vbase (k,b,16) int64: the slab's operator
+ *                                          per sequence.  slab_vop[j][i] + slab_vbase[i] (i, j < q) is the best Q16
+ *                                          score of any path that is in state i at the position before the slab and in
+ *                                          state j at the slab's last position, the transition into the slab's first
+ *                                          position and all the slab's emissions included; every column i has
+ *                                          maximum 0.  With seq_start = 1 every column holds the same vector, the
+ *                                          maximum over paths from Q(log pi).  Rows and columns from q on are 0.
+ *   2. host: all-gather slab_vop / slab_vbase over the ranks, laid out (k,b,R,16,16) / (k,b,R,16)
+ *   3. hmm_seqshard_viterbi_apply(...)  -> slab_origin (k,b,16) bytes: slab_origin[j] = the state at the position
+ *                                          before the slab of the best path into state j at the slab's last position
+ *                                          (all 0 for seq_start = 1, never read); final_state (k,b), score (k,b): the
+ *                                          WHOLE sequence's lowest-index best last state and its score, the same
+ *                                          integers on every rank.  The backpointers stay in the workspace.
+ *   4. host: all-gather slab_origin, laid out (k,b,R,16)
+ *   5. hmm_seqshard_viterbi_path(...)   -> path (k,b,Ls) int32: this slab's piece of the most probable path
+ * seq_start: 1 on the rank that owns position 0 (r == 0), else 0.  logA (k,q,q), logpi (k,q) as for hmm_viterbi, the
+ * same on every rank and in steps 1 and 3.  The same workspace, from the same size query, must be passed to steps
+ * 1, 3 and 5 with nothing else written to it in between: it holds ALL k models' chunk operators, entering scores,
+ * maps and backpointers (8 bytes per position and sequence).  HMM_OPT_FORCE_DENSE, HMM_OPT_CHUNK and HMM_OPT_SCAN2
+ * act as for hmm_viterbi and must not change between the steps.  Everything runs in order on `stream` (no helper
+ * streams, no batch groups), without host synchronisation: the calls are capturable into a HIP graph.
+ *
+ * hmm_seqshard_viterbi_workspace_bytes: a multiple of 256, non-decreasing in R; 0 for q > 16, R < 1 or a bad shape.
+ * Argument checks, in this order, all before any HIP call:
+ *   1. q > hmm_seqshard_viterbi_max_states()         HMM_ERR_Q_UNSUPPORTED (-2), ahead of everything
+ *   2. R < 1                                         HMM_ERR_BAD_ARGUMENT  (-6)
+ *   3. k, b, Ls or q < 1 (or k * b > 2^24)           HMM_ERR_BAD_SHAPE     (-1)
+ *   4. apply / path: r outside 0 .. R-1; apply: (seq_start != 0) != (r == 0)
+ *                                                    HMM_ERR_BAD_ARGUMENT  (-6)
+ *   5. a NULL pointer among the arguments            HMM_ERR_NULL_POINTER  (-3)
+ *   6. workspace_bytes below the size query, or a workspace not aligned to 256 bytes
+ *                                                    HMM_ERR_WORKSPACE     (-4)
+ */
+int hmm_seqshard_viterbi_max_states(void);
+size_t hmm_seqshard_viterbi_workspace_bytes(int k, int b, int Ls, int q, int R);
+int hmm_seqshard_viterbi_reduce(const float *logA, const float *logpi, const float *logE_slab,
+                                int k, int b, int Ls, int q, int seq_start, int R,
+                                int *slab_vop, long long *slab_vbase,
+                                void *workspace, size_t workspace_bytes, void *stream);
+int hmm_seqshard_viterbi_apply(const float *logA, const float *logpi, const float *logE_slab,
+                               int k, int b, int Ls, int q, int seq_start,
+                               const int *all_vops, const long long *all_vbases, int R, int r,
+                               unsigned char *slab_origin, int *final_state, double *score,
+                               void *workspace, size_t workspace_bytes, void *stream);
+int hmm_seqshard_viterbi_path(int k, int b, int Ls, int q,
+                              const unsigned char *all_origins, const int *final_state, int R, int r,
+                              int32_t *path,
+                              void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Gradient of the log-likelihoods (training).  The reference trains by autograd through the
  * Python time loop (hmm_layer/BaseRNN.py:217-227 over HmmCell.forward,
  * hmm_layer/MsaHmmCell.py:73-106); this entry point returns the same derivatives from one
