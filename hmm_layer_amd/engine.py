@@ -159,14 +159,18 @@ def _check(rc):
         raise EngineError("hmm_engine: %s (code %d)" % (lib().hmm_strerror(rc).decode(), rc))
 
 
-def _dev(t, name, dtype=torch.float32):
+def _dev(t, name, dtype=torch.float32, align=0):
+    """The tensor as the C ABI takes it: on a HIP device, of `dtype`, contiguous.  align: for the few arguments whose
+    kernels need more than element alignment (include/hmm_engine.h, "Memory contract"), a view that starts elsewhere
+    is copied to a fresh tensor."""
     if not torch.is_tensor(t):
         raise TypeError("%s must be a torch.Tensor" % name)
     if not t.is_cuda:
         raise EngineError("%s must live on a HIP device (got %s); the engine has no CPU path" % (name, t.device))
     if t.dtype != dtype:
         raise TypeError("%s must be %s, got %s" % (name, dtype, t.dtype))
-    return t.contiguous()
+    t = t.contiguous()
+    return t.clone() if align and t.data_ptr() % align else t
 
 
 def _shapes(A, E, pi=None):
@@ -767,7 +771,7 @@ def seqshard_posterior(A, pi, E_slab, all_ops, all_exps, r, mode=POST_PROB, eps=
     -> (out (k,b,Ls,q), loglik (k,b) fp64 of the whole sequences, phi (k,b) fp32: this slab's share of
     the floor-transition bound)."""
     A, pi, E = _dev(A, "A"), _dev(pi, "pi"), _dev(E_slab, "E_slab")
-    all_ops, all_exps = _dev(all_ops, "all_ops"), _dev(all_exps, "all_exps", torch.int32)
+    all_ops, all_exps = _dev(all_ops, "all_ops", align=16), _dev(all_exps, "all_exps", torch.int32)
     A, pi, dims = _shapes(A, E, pi)
     k, b = dims[:2]
     R = all_ops.shape[2]
@@ -825,7 +829,7 @@ def seqshard_viterbi_apply(logA, logpi, logE_slab, all_vops, all_vbases, r):
     position; final_state (k,b) int32 and score (k,b) fp64 of the WHOLE sequences, the same on every rank).  The
     backpointers stay in the workspace for seqshard_viterbi_path."""
     logA, logpi, logE, dims = _log_model(logA, logpi, logE_slab)
-    all_vops, all_vbases = _dev(all_vops, "all_vops", torch.int32), _dev(all_vbases, "all_vbases", torch.int64)
+    all_vops, all_vbases = _dev(all_vops, "all_vops", torch.int32, align=16), _dev(all_vbases, "all_vbases", torch.int64)
     k, b = dims[:2]
     R = all_vops.shape[2] if all_vops.dim() == 5 else 0
     if tuple(all_vops.shape) != (k, b, R, 16, 16) or tuple(all_vbases.shape) != (k, b, R, 16):

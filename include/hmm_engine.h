@@ -20,6 +20,26 @@
  * Workspace: the caller owns all memory.  Query hmm_workspace_bytes() and pass a
  * device buffer of at least that size (256-byte aligned) to the call.
  *
+ * Memory contract (tests/test_memory_contract_gpu.py holds every entry point to it with guard bands around every
+ * argument and a workspace of exactly the queried size).  A call
+ *   - reads nothing outside its inputs: of a strided input (emb / nuc with ld) only the columns it names;
+ *   - writes nothing outside its outputs and the first `workspace_bytes` bytes, as the size query returns them, of the
+ *     workspace; of a strided output (demb with ldd) only the columns it names; inputs are never written
+ *     (E with multiply = 1 is an output as well);
+ *   - writes every element of every output it is asked for (a NULL-able output that is NULL is not asked for);
+ *   - does not depend on what the workspace or the outputs held before: a workspace may be reused for any other call,
+ *     of any shape, without clearing it.  The one region kept on purpose is what the sequence-sharded protocols leave
+ *     in the workspace between their own steps.
+ * Alignment of the pointers:
+ *   - workspace: 256 bytes;
+ *   - 16 bytes: E of hmm_gene_emissions, dx of hmm_gene_emissions_grad and of hmm_gene_emissions_grad_wide (whole
+ *     tiles of 16 positions leave as aligned 16-byte pieces), all_ops of hmm_seqshard_posterior and all_vops of
+ *     hmm_seqshard_viterbi_apply (the hops read the gathered operators' rows as aligned 16-byte pieces);
+ *   - every other pointer: the alignment of its element type — 4 bytes for fp32 and int32 tensors (a view such as
+ *     E_all + m * b * L * q of an odd-sized model is fine), 8 for fp64 and int64 (loglik, score, partial, slab_vbase).
+ *     There the kernels reach caller memory through element accesses, 4-byte-aligned vector types and buffer
+ *     descriptors.
+ *
  * Streams: to the caller every call is an ordinary in-order operation on `stream` — it starts
  * after everything enqueued there before it, and everything enqueued after it sees its results.
  * Inside, three calls put independent parts of their work on a per-device helper stream, forked
@@ -284,7 +304,9 @@ int hmm_viterbi_scan(const float *logA, const float *logpi, const float *logE,
  *   state_codon (q) int    table row constraining state j, or -1 (free state: `free_value`, 1/4096)
  *   add                    added to the 3-mer factor (1e-7 when training, else 0, :260-261)
  *   n_mass                 1, or 2 to reproduce the reference's doubled N mass in right 3-mers
- *   E           (b,L,q)    emission probabilities, the engine's input
+ *   E           (b,L,q)    emission probabilities, the engine's input.  16-byte aligned (so is dx of
+ *                          hmm_gene_emissions_grad and _grad_wide): tiles of 16 positions are stored as aligned
+ *                          16-byte pieces.
  */
 int hmm_gene_emissions(const float *x, int b, int L, int s, const float *B, int rows,
                        const int *state_row, const float *codon, int nc, const int *state_codon, int q,
@@ -562,7 +584,8 @@ int hmm_loglik_allreduce(void *comm, double *partial, int k, void *stream);
  * devices.  q <= hmm_scan_max_states().  Protocol, R ranks, rank r (slabs in time order):
  *   1. hmm_seqshard_reduce(...)    -> slab_op (k,b,16,16) fp32, slab_exp (k,b,16) int32: the slab's
  *                                     operator per sequence (column n scaled by 2^-exp[n])
- *   2. host: all-gather slab_op / slab_exp over the ranks and lay them out (k,b,R,16,16) / (k,b,R,16)
+ *   2. host: all-gather slab_op / slab_exp over the ranks and lay them out (k,b,R,16,16) / (k,b,R,16); all_ops
+ *      16-byte aligned
  *   3. hmm_seqshard_posterior(...) -> out (k,b,Ls,q) per `mode`, loglik (k,b) = the WHOLE sequence's,
  *                                     phi_out (k,b) fp32 or NULL: this slab's share of the sequence's
  *                                     floor-transition bound (see hmm_posterior; +inf when A's support is
@@ -612,7 +635,8 @@ int hmm_seqshard_posterior(const float *A, const float *pi, const float *E, int 
  *                                          position and all the slab's emissions included; every column i has
  *                                          maximum 0.  With seq_start = 1 every column holds the same vector, the
  *                                          maximum over paths from Q(log pi).  Rows and columns from q on are 0.
- *   2. host: all-gather slab_vop / slab_vbase over the ranks, laid out (k,b,R,16,16) / (k,b,R,16)
+ *   2. host: all-gather slab_vop / slab_vbase over the ranks, laid out (k,b,R,16,16) / (k,b,R,16); all_vops 16-byte
+ *      aligned
  *   3. hmm_seqshard_viterbi_apply(...)  -> slab_origin (k,b,16) bytes: slab_origin[j] = the state at the position
  *                                          before the slab of the best path into state j at the slab's last position
  *                                          (all 0 for seq_start = 1, never read); final_state (k,b), score (k,b): the
