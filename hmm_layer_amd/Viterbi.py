@@ -9,7 +9,7 @@ results —, ``hmm_viterbi_large`` above: every cell the layer serves, up to 409
 gene models and profile HMMs).
 
 ``viterbi_sharded(E_slab, cell, group)`` decodes sequences that are cut in TIME across the ranks of a process
-group (hmm_layer_amd/seqshard.py: one chromosome-sized sequence on several GPUs), up to 16 states."""
+group (hmm_layer_amd/seqshard.py: one chromosome-sized sequence on several GPUs), up to 64 states."""
 import torch
 
 from . import engine

@@ -40,6 +40,11 @@
 // operators of longer chunks.
 //
 // Every offset into logE, path and the backpointers is 64-bit; everything runs in order on `stream`.
+//
+// VsPlan::seq_start (hmm_viterbi_scan: always 1) says whether the tensor begins at position 0 of its sequences.  A time
+// slab that does not (hmm_seqshard_vscan.inc) has no first observation: its chunk 0 is an ordinary chunk with an
+// operator column per start state, entering scores, a backpointer row at its step 0 and a valid end -> before map.
+// "First chunk of a sequence" is `c == 0 && seq_start` throughout.
 
 #define VS_NEG (-0x40000000)
 #define VS_ET 16          // steps per staged emission tile
@@ -52,6 +57,7 @@ struct VsModel {              // per model, in the workspace
 
 struct VsPlan {
     int k, b, L, q, QT, NB, T, C, G, gsize;
+    int seq_start;            // 1: position 0 of the tensor is position 0 of the sequences
     long long nchains;
     size_t o_mq, o_model, o_vops, o_vrb, o_vmb, o_dstart, o_forig, o_send, o_sfinal;
     size_t o_gvops, o_gvrb, o_gvmb, o_gdstart, o_gforig, o_gsend, o_bp, total;
@@ -79,6 +85,7 @@ static int make_vsplan(int k, int b, int L, int q, VsPlan *v) {
     if ((long long)k * b > (1ll << 24)) return HMM_ERR_BAD_SHAPE;
     if (q > MQ_MAX) return HMM_ERR_Q_UNSUPPORTED;
     v->k = k; v->b = b; v->L = L; v->q = q;
+    v->seq_start = 1;
     v->QT = q <= 32 ? 32 : 64;
     v->NB = k * b;
     v->T = vs_choose_T(v->NB, L);
@@ -231,12 +238,13 @@ __global__ __launch_bounds__(64) void k_vs_reduce(const float *__restrict__ logE
     em.rows = p.L - t0; em.rowb = q * (int)sizeof(float);
     em.act = lane < q; em.voff = em.act ? lane * 4 : 0;
     const int mode = __builtin_amdgcn_readfirstlane(S.mode);
+    const bool first = c == 0 && p.seq_start;
     int mprev, cur;
     long long base;
-    if (mode == 0) vs_reduce_chunk<QT, 0>(em, S, M, xs, es, q, len, c == 0, lane, mprev, base, cur);
-    else if (mode == 3) vs_reduce_chunk<QT, 3>(em, S, M, xs, es, q, len, c == 0, lane, mprev, base, cur);
-    else if (mode == 4) vs_reduce_chunk<QT, 4>(em, S, M, xs, es, q, len, c == 0, lane, mprev, base, cur);
-    else vs_reduce_chunk<QT, 8>(em, S, M, xs, es, q, len, c == 0, lane, mprev, base, cur);
+    if (mode == 0) vs_reduce_chunk<QT, 0>(em, S, M, xs, es, q, len, first, lane, mprev, base, cur);
+    else if (mode == 3) vs_reduce_chunk<QT, 3>(em, S, M, xs, es, q, len, first, lane, mprev, base, cur);
+    else if (mode == 4) vs_reduce_chunk<QT, 4>(em, S, M, xs, es, q, len, first, lane, mprev, base, cur);
+    else vs_reduce_chunk<QT, 8>(em, S, M, xs, es, q, len, first, lane, mprev, base, cur);
     // column `lane`: entries relative to its maximum, base relative to the operator's largest
     const bool act = lane < q;
     const long long mb = vs_wave_max_ll(act ? base : (long long)0x8000000000000000ll);
@@ -254,15 +262,22 @@ __global__ __launch_bounds__(64) void k_vs_reduce(const float *__restrict__ logE
 // G == 0: one block per sequence over its C operators (chunks, or the groups of the two-level scan): records the
 // scores entering operator 1 .. C-1, the final state and the score.  G > 0: one block per (sequence, group):
 // from the scores entering the group (gdstart; group 0 starts the sequence) records those entering each of its chunks.
-template <int QT>
+// seq_start == 0 (a time slab behind the first one): operator 0 is an ordinary operator — the top level starts from
+// the scores entering the slab (gdstart, one row per sequence), records those entering operator 0 as well and, with
+// sfinal == NULL, leaves the sequence's final state and score alone (they are not this slab's to know).
+// SLABS (hmm_seqshard_vscan.inc): the top level over the gathered operators of R time slabs, whose column bases
+// arrive as one int64 per column (mb: [sequence][slab][QT], rb unused): the hop forms the operator's largest base and
+// the 32-bit relative column bases itself.  The scores entering slab r also go to entry[sequence][QT].
+template <int QT, bool SLABS>
 __global__ __launch_bounds__(64) void k_vs_scan(const int *__restrict__ ops, const int *__restrict__ rb,
                                                 const long long *__restrict__ mb, int *__restrict__ dstart,
                                                 const int *__restrict__ gdstart, int *__restrict__ sfinal,
-                                                double *__restrict__ score, int q, int C, int G, int gsize) {
+                                                double *__restrict__ score, int q, int C, int G, int gsize,
+                                                int seq_start, int *__restrict__ entry, int r) {
     const int lane = threadIdx.x, jl = lane & (QT - 1);
     const bool act = lane < q;
     const bool top = G == 0;
-    int seq = blockIdx.x, grp = 0, c_begin = 1, c_end = C;
+    int seq = blockIdx.x, grp = 0, c_begin = 0, c_end = C;
     if (!top) {
         seq = blockIdx.x / G;
         grp = blockIdx.x - seq * G;
@@ -272,12 +287,17 @@ __global__ __launch_bounds__(64) void k_vs_scan(const int *__restrict__ ops, con
     const size_t ch0 = (size_t)seq * C;
     int rel;
     long long base = 0;
-    if (grp == 0) {                                          // the first chunk's columns all hold the score vector
-        rel = act ? ops[(ch0 * QT + jl) * QT] + rb[ch0 * QT] : 0;
-        base = mb[ch0];
+    if (grp == 0 && seq_start) {                             // the first chunk's columns all hold the score vector
+        if constexpr (SLABS) {
+            rel = act ? ops[(ch0 * QT + jl) * QT] : 0;
+            base = mb[ch0 * QT];
+        } else {
+            rel = act ? ops[(ch0 * QT + jl) * QT] + rb[ch0 * QT] : 0;
+            base = mb[ch0];
+        }
         c_begin = 1;
     } else {
-        rel = act ? gdstart[((size_t)seq * G + grp) * QT + jl] : 0;
+        rel = act ? gdstart[(top ? (size_t)seq : (size_t)seq * G + grp) * QT + jl] : 0;
     }
     i4 nv[QT / 4];
     int nrb = 0;
@@ -286,12 +306,21 @@ __global__ __launch_bounds__(64) void k_vs_scan(const int *__restrict__ ops, con
         const i4 *R = reinterpret_cast<const i4 *>(ops + ((ch0 + c) * QT + jl) * QT);
 #pragma unroll
         for (int u = 0; u < QT / 4; ++u) nv[u] = R[u];
-        nrb = rb[(ch0 + c) * QT + jl];
-        nmb = mb[ch0 + c];
+        if constexpr (SLABS) {
+            const long long cb = act ? mb[(ch0 + c) * QT + jl] : (long long)0x8000000000000000ll;
+            nmb = vs_wave_max_ll(cb);
+            nrb = act ? (int)(cb - nmb) : 0;
+        } else {
+            nrb = rb[(ch0 + c) * QT + jl];
+            nmb = mb[ch0 + c];
+        }
     };
     if (c_begin < c_end) fetch(c_begin);
     for (int c = c_begin; c < c_end; ++c) {
         if (lane < QT) dstart[(ch0 + c) * QT + lane] = rel;
+        if constexpr (SLABS) {
+            if (c == r && lane < QT) entry[(size_t)seq * QT + lane] = rel;
+        }
         if (!top && c + 1 == c_end) break;                   // the group's last operator leads out of it
         i4 v[QT / 4];
 #pragma unroll
@@ -311,7 +340,7 @@ __global__ __launch_bounds__(64) void k_vs_scan(const int *__restrict__ ops, con
         rel = act ? best - mx : 0;
         base += cmb + mx;
     }
-    if (top) {
+    if (top && sfinal) {
         const unsigned long long ball = __builtin_amdgcn_ballot_w64(act && rel == 0);
         if (lane == 0) {
             sfinal[seq] = __builtin_ctzll(ball);             // lowest index among the best
@@ -322,7 +351,9 @@ __global__ __launch_bounds__(64) void k_vs_scan(const int *__restrict__ ops, con
 
 // One wave per (sequence, group): W <- V_c (x) W over the group's chunks.  Lane k = start state of the group owns
 // column k of W (through LDS between hops, in registers within one); rows of V_c are wave-uniform.
-template <int QT>
+// COLS64 (hmm_seqshard_vscan.inc, a slab's operator for the exchange): one int64 base per column to gvmb[wave][QT]
+// (0 in the lanes from q on) instead of the 32-bit relative bases and the operator's largest; gvrb is not written.
+template <int QT, bool COLS64>
 __global__ __launch_bounds__(64) void k_vs_compose(const int *__restrict__ vops, const int *__restrict__ vrb,
                                                    const long long *__restrict__ vmb, int *__restrict__ gvops,
                                                    int *__restrict__ gvrb, long long *__restrict__ gvmb, int q, int C,
@@ -357,9 +388,10 @@ __global__ __launch_bounds__(64) void k_vs_compose(const int *__restrict__ vops,
     if (lane < QT) {
         int *W = gvops + wv * QT * QT + lane;
         for (int m = 0; m < QT; ++m) W[m * QT] = (act && m < q) ? wl[m][lane] : VS_NEG;
-        gvrb[wv * QT + lane] = act ? (int)(cb - mbv) : 0;
+        if constexpr (COLS64) gvmb[wv * QT + lane] = act ? cb : 0;
+        else gvrb[wv * QT + lane] = act ? (int)(cb - mbv) : 0;
     }
-    if (lane == 0) gvmb[wv] = mbv;
+    if (!COLS64 && lane == 0) gvmb[wv] = mbv;
 }
 
 // ------------------------------------------------------------------ apply: true scores, backpointers
@@ -402,7 +434,8 @@ __global__ __launch_bounds__(64) void k_vs_apply(const float *__restrict__ logE,
     em.rows = p.L - t0; em.rowb = q * (int)sizeof(float);
     em.act = act; em.voff = act ? j * 4 : 0;
     unsigned char *bpr = bp + ((size_t)row * p.L + t0) * 64;
-    int d = act ? (c == 0 ? 0 : dstart[(size_t)chain * p.QT + j]) : MQ_NEG;
+    const bool first = c == 0 && p.seq_start;
+    int d = act ? (first ? 0 : dstart[(size_t)chain * p.QT + j]) : MQ_NEG;
     int og = j;
     float r[VS_ET];
     vs_fetch(em, 0, r);
@@ -415,7 +448,7 @@ __global__ __launch_bounds__(64) void k_vs_apply(const float *__restrict__ logE,
         for (int u = 0; u < nst; ++u) {
             const int e = es[u][j];
             int arg;
-            if (c == 0 && tile == 0 && u == 0) {            // the sequence's first position: no transition into it
+            if (first && tile == 0 && u == 0) {             // the sequence's first position: no transition into it
                 d = act ? M.p0[j] + e : MQ_NEG;
                 arg = j;
             } else if constexpr (D == 0) {
@@ -480,7 +513,7 @@ __global__ void k_vs_bwd_compose(const unsigned char *__restrict__ forig, unsign
     const int seq = (int)(wv / G), grp = (int)(wv - (long long)seq * G);
     const int c0 = grp * gsize, c1 = min(C, c0 + gsize);
     int s = j;
-    for (int c = c1 - 1; c >= c0; --c) s = forig[((size_t)seq * C + c) * 64 + s] & 63;    // (chunk 0's map is never used)
+    for (int c = c1 - 1; c >= c0; --c) s = forig[((size_t)seq * C + c) * 64 + s] & 63;    // (chunk 0's map: read for a later time slab only)
     gforig[(size_t)wv * 64 + j] = (unsigned char)s;
 }
 
@@ -514,14 +547,53 @@ __global__ __launch_bounds__(64) void k_vs_backtrace(const unsigned char *__rest
 
 // ------------------------------------------------------------------ host entry
 template <int QT>
+static void vs_launch_apply(const float *logE, const VsPlan &v, char *ws, hipStream_t st) {
+    const MqModel *cmq = (const MqModel *)(ws + v.o_mq);
+    const VsModel *cm = (const VsModel *)(ws + v.o_model);
+    const int *cd = (const int *)(ws + v.o_dstart);
+    unsigned char *forig = (unsigned char *)(ws + v.o_forig), *bp = (unsigned char *)(ws + v.o_bp);
+    const dim3 chains((unsigned)v.nchains), wave(64);
+    hipLaunchKernelGGL((k_vs_apply<QT, 4>), chains, wave, 0, st, logE, cmq, cm, cd, forig, bp, v);
+    hipLaunchKernelGGL((k_vs_apply<QT, 8>), chains, wave, 0, st, logE, cmq, cm, cd, forig, bp, v);
+    hipLaunchKernelGGL((k_vs_apply<QT, 0>), chains, wave, 0, st, logE, cmq, cm, cd, forig, bp, v);
+}
+
+// the groups' maps (two levels): every chunk of a group composed, its first one included
+static void vs_launch_group_maps(const VsPlan &v, char *ws, hipStream_t st) {
+    const long long ngrp = (long long)v.NB * v.G;
+    hipLaunchKernelGGL(k_vs_bwd_compose, dim3((unsigned)((ngrp * 64 + 255) / 256)), dim3(256), 0, st,
+                       (const unsigned char *)(ws + v.o_forig), (unsigned char *)(ws + v.o_gforig), v.NB, v.C, v.G, v.gsize);
+}
+
+// from the state at the tensor's last position (sfinal): the state at every chunk end, then every chunk's backtrace
+static void vs_launch_backward(const VsPlan &v, char *ws, int32_t *path, bool two, hipStream_t st) {
+    const unsigned char *forig = (const unsigned char *)(ws + v.o_forig);
+    const int *sfinal = (const int *)(ws + v.o_sfinal);
+    int *send = (int *)(ws + v.o_send);
+    const int NB = v.NB, C = v.C, G = v.G;
+    const dim3 wave(64);
+    if (!two) {
+        hipLaunchKernelGGL(k_vs_scan_bwd, dim3((NB + 63) / 64), wave, 0, st, forig, sfinal, send, NB, C);
+    } else {
+        const unsigned ngrp = (unsigned)((long long)NB * G);
+        int *gsend = (int *)(ws + v.o_gsend);
+        hipLaunchKernelGGL(k_vs_scan_bwd, dim3((NB + 63) / 64), wave, 0, st, (const unsigned char *)(ws + v.o_gforig),
+                           sfinal, gsend, NB, G);
+        hipLaunchKernelGGL(k_vs_bwd_inner, dim3((ngrp + 63) / 64), wave, 0, st, forig, (const int *)gsend, send, NB, C, G,
+                           v.gsize);
+    }
+    hipLaunchKernelGGL(k_vs_backtrace, dim3((unsigned)v.nchains), wave, 0, st, (const unsigned char *)(ws + v.o_bp),
+                       (const int *)send, path, v);
+}
+
+template <int QT>
 static void vs_run(const float *logA, const float *logpi, const float *logE, const VsPlan &v, char *ws, int32_t *path,
                    double *score, hipStream_t st) {
     MqModel *mq = (MqModel *)(ws + v.o_mq);
     VsModel *models = (VsModel *)(ws + v.o_model);
     int *vops = (int *)(ws + v.o_vops), *vrb = (int *)(ws + v.o_vrb), *dstart = (int *)(ws + v.o_dstart);
     long long *vmb = (long long *)(ws + v.o_vmb);
-    unsigned char *forig = (unsigned char *)(ws + v.o_forig), *bp = (unsigned char *)(ws + v.o_bp);
-    int *send = (int *)(ws + v.o_send), *sfinal = (int *)(ws + v.o_sfinal);
+    int *sfinal = (int *)(ws + v.o_sfinal);
     const int q = v.q, C = v.C, G = v.G, gs = v.gsize, NB = v.NB;
     const dim3 chains((unsigned)v.nchains), wave(64);
     const bool two = G > 0 && opt(HMM_OPT_SCAN2) != 0;
@@ -532,36 +604,21 @@ static void vs_run(const float *logA, const float *logpi, const float *logE, con
     const VsModel *cm = models;
     hipLaunchKernelGGL(k_vs_reduce<QT>, chains, wave, 0, st, logE, cmq, cm, vops, vrb, vmb, v);
     if (!two) {
-        hipLaunchKernelGGL(k_vs_scan<QT>, dim3(NB), wave, 0, st, (const int *)vops, (const int *)vrb, (const long long *)vmb,
-                           dstart, (const int *)nullptr, sfinal, score, q, C, 0, 0);
+        hipLaunchKernelGGL((k_vs_scan<QT, false>), dim3(NB), wave, 0, st, (const int *)vops, (const int *)vrb,
+                           (const long long *)vmb, dstart, (const int *)nullptr, sfinal, score, q, C, 0, 0, 1, (int *)nullptr, 0);
     } else {
         int *gvops = (int *)(ws + v.o_gvops), *gvrb = (int *)(ws + v.o_gvrb), *gdstart = (int *)(ws + v.o_gdstart);
         long long *gvmb = (long long *)(ws + v.o_gvmb);
-        hipLaunchKernelGGL(k_vs_compose<QT>, dim3(ngrp), wave, 0, st, (const int *)vops, (const int *)vrb,
+        hipLaunchKernelGGL((k_vs_compose<QT, false>), dim3(ngrp), wave, 0, st, (const int *)vops, (const int *)vrb,
                            (const long long *)vmb, gvops, gvrb, gvmb, q, C, G, gs);
-        hipLaunchKernelGGL(k_vs_scan<QT>, dim3(NB), wave, 0, st, (const int *)gvops, (const int *)gvrb,
-                           (const long long *)gvmb, gdstart, (const int *)nullptr, sfinal, score, q, G, 0, 0);
-        hipLaunchKernelGGL(k_vs_scan<QT>, dim3(ngrp), wave, 0, st, (const int *)vops, (const int *)vrb,
-                           (const long long *)vmb, dstart, (const int *)gdstart, sfinal, score, q, C, G, gs);
+        hipLaunchKernelGGL((k_vs_scan<QT, false>), dim3(NB), wave, 0, st, (const int *)gvops, (const int *)gvrb,
+                           (const long long *)gvmb, gdstart, (const int *)nullptr, sfinal, score, q, G, 0, 0, 1, (int *)nullptr, 0);
+        hipLaunchKernelGGL((k_vs_scan<QT, false>), dim3(ngrp), wave, 0, st, (const int *)vops, (const int *)vrb,
+                           (const long long *)vmb, dstart, (const int *)gdstart, sfinal, score, q, C, G, gs, 1, (int *)nullptr, 0);
     }
-    const int *cd = dstart;
-    hipLaunchKernelGGL((k_vs_apply<QT, 4>), chains, wave, 0, st, logE, cmq, cm, cd, forig, bp, v);
-    hipLaunchKernelGGL((k_vs_apply<QT, 8>), chains, wave, 0, st, logE, cmq, cm, cd, forig, bp, v);
-    hipLaunchKernelGGL((k_vs_apply<QT, 0>), chains, wave, 0, st, logE, cmq, cm, cd, forig, bp, v);
-    if (!two) {
-        hipLaunchKernelGGL(k_vs_scan_bwd, dim3((NB + 63) / 64), wave, 0, st, (const unsigned char *)forig,
-                           (const int *)sfinal, send, NB, C);
-    } else {
-        unsigned char *gforig = (unsigned char *)(ws + v.o_gforig);
-        int *gsend = (int *)(ws + v.o_gsend);
-        hipLaunchKernelGGL(k_vs_bwd_compose, dim3((unsigned)(((long long)ngrp * 64 + 255) / 256)), dim3(256), 0, st,
-                           (const unsigned char *)forig, gforig, NB, C, G, gs);
-        hipLaunchKernelGGL(k_vs_scan_bwd, dim3((NB + 63) / 64), wave, 0, st, (const unsigned char *)gforig,
-                           (const int *)sfinal, gsend, NB, G);
-        hipLaunchKernelGGL(k_vs_bwd_inner, dim3((ngrp + 63) / 64), wave, 0, st, (const unsigned char *)forig,
-                           (const int *)gsend, send, NB, C, G, gs);
-    }
-    hipLaunchKernelGGL(k_vs_backtrace, chains, wave, 0, st, (const unsigned char *)bp, (const int *)send, path, v);
+    vs_launch_apply<QT>(logE, v, ws, st);
+    if (two) vs_launch_group_maps(v, ws, st);
+    vs_launch_backward(v, ws, path, two, st);
 }
 
 extern "C" int hmm_viterbi_scan_max_states(void) { return MQ_MAX; }

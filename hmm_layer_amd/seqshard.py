@@ -22,6 +22,7 @@ score are those of the unsharded engine.viterbi, bit for bit.
 
     reduce      local     the slab's max-plus operator per sequence               (hmm_seqshard_viterbi_reduce)
     all-gather  RCCL      twice: the operators (k,b,16,16) int32 and their bases (k,b,16) int64 per rank
+                          (17 to 64 states: hmm_seqshard_vscan_*, seqshard_vscan.py, tiles of 32 or 64 instead of 16)
     apply       local     hops over the R slab operators, local chunk scan, in-chunk pass with backpointers,
                           the slab's map "state at its end -> state before it"    (hmm_seqshard_viterbi_apply)
     all-gather  RCCL      the maps, (k,b,16) bytes per rank
@@ -163,16 +164,26 @@ def _all_gather_stacked(x, R, group):
     return torch.stack(parts, dim=2).contiguous()
 
 
+def viterbi_backend(q):
+    """The engine backend that serves q states: hmm_seqshard_viterbi_* up to 16, hmm_seqshard_vscan_* for 17 to 64."""
+    if q <= 16:
+        return ViterbiEngineBackend()
+    if q > 64:
+        raise ValueError("sequence-sharded Viterbi covers q <= 64 states, got %d" % q)
+    from .seqshard_vscan import VscanEngineBackend
+    return VscanEngineBackend()
+
+
 def viterbi(logA, logpi, logE_slab, group=None, backend=None):
     """-> (path_slab (k,b,Ls) int32: this rank's piece of the most probable paths, score (k,b) fp64 of the whole
     sequences, the same on every rank).
 
     logA (k,q,q), logpi (k,q), logE_slab (k,b,Ls,q) fp32 log-probabilities with engine.viterbi's semantics (Q16 fixed
-    point, lowest-index tie-breaks), q <= 16.  Ranks of `group` hold consecutive time slabs in rank order (rank 0 owns
-    position 0); slab lengths may differ.  The concatenation of the ranks' paths and the score equal engine.viterbi's on
-    the uncut tensor bit for bit."""
+    point, lowest-index tie-breaks), q <= 64 (backend None: the engine's, by q — viterbi_backend).  Ranks of `group`
+    hold consecutive time slabs in rank order (rank 0 owns position 0); slab lengths may differ.  The concatenation of
+    the ranks' paths and the score equal engine.viterbi's on the uncut tensor bit for bit."""
     import torch.distributed as dist
-    backend = backend or ViterbiEngineBackend()
+    backend = backend or viterbi_backend(int(logE_slab.shape[-1]))
     R = dist.get_world_size(group)
     r = dist.get_rank(group)
     vop, vbase = backend.reduce(logA, logpi, logE_slab, r == 0, R)

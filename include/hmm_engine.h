@@ -34,7 +34,8 @@
  *   - workspace: 256 bytes;
  *   - 16 bytes: E of hmm_gene_emissions, dx of hmm_gene_emissions_grad and of hmm_gene_emissions_grad_wide (whole
  *     tiles of 16 positions leave as aligned 16-byte pieces), all_ops of hmm_seqshard_posterior and all_vops of
- *     hmm_seqshard_viterbi_apply (the hops read the gathered operators' rows as aligned 16-byte pieces);
+ *     hmm_seqshard_viterbi_apply and hmm_seqshard_vscan_apply (the hops read the gathered operators' rows as aligned
+ *     16-byte pieces);
  *   - every other pointer: the alignment of its element type — 4 bytes for fp32 and int32 tensors (a view such as
  *     E_all + m * b * L * q of an odd-sized model is fine), 8 for fp64 and int64 (loglik, score, partial, slab_vbase).
  *     There the kernels reach caller memory through element accesses, 4-byte-aligned vector types and buffer
@@ -677,6 +678,67 @@ int hmm_seqshard_viterbi_path(int k, int b, int Ls, int q,
                               const unsigned char *all_origins, const int *final_state, int R, int r,
                               int32_t *path,
                               void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Sequence-sharded Viterbi for up to 64 states: the protocol of hmm_seqshard_viterbi_* with hmm_viterbi_scan's q x q
+ * max-plus operators in tiles of QT = hmm_seqshard_vscan_tile(q) = 32 (q <= 32) or 64 states; every q from 1 to
+ * hmm_seqshard_vscan_max_states() (64) is served.  Semantics and results are hmm_viterbi's, bit for bit.  R ranks,
+ * rank r owns positions [t_r, t_{r+1}) of every sequence, logE_slab (k,b,Ls,q), Ls may differ between ranks:
+ *   1. hmm_seqshard_vscan_reduce(...) -> slab_vop (k,b,QT,QT) int32, slab_vbase (k,b,QT) int64: the slab's operator per
+ *                                        sequence.  slab_vop[j][i] + slab_vbase[i] (i, j < q) is the best Q16 score of
+ *                                        any path that is in state i at the position before the slab and in state j at
+ *                                        the slab's last position, the transition into the slab's first position and
+ *                                        all the slab's emissions included; every column i < q has maximum 0.  With
+ *                                        seq_start = 1 every column holds the same vector, the maximum over paths from
+ *                                        Q(log pi).  Only the leading q x q block and the first q bases are defined;
+ *                                        the padding is written on every call: -2^30 in the rows and columns of slab_vop
+ *                                        from q on, 0 in the bases from q on.
+ *   2. host: all-gather slab_vop / slab_vbase over the ranks, laid out (k,b,R,QT,QT) / (k,b,R,QT); all_vops 16-byte
+ *      aligned (the hops read the operators' rows as aligned 16-byte pieces)
+ *   3. hmm_seqshard_vscan_apply(...)  -> slab_origin (k,b,QT) bytes: slab_origin[j] = the state at the position before
+ *                                        the slab of the best path into state j at the slab's last position (all 0 for
+ *                                        seq_start = 1, never read then; 0 from q on); final_state (k,b), score (k,b):
+ *                                        the WHOLE sequence's lowest-index best last state and its score, the same
+ *                                        integers on every rank.  The backpointers stay in the workspace.
+ *   4. host: all-gather slab_origin, laid out (k,b,R,QT)
+ *   5. hmm_seqshard_vscan_path(...)   -> path (k,b,Ls) int32: this slab's piece of the most probable path
+ * seq_start: 1 on the rank that owns position 0 (r == 0), else 0.  logA (k,q,q), logpi (k,q) as for hmm_viterbi, the
+ * same on every rank and in steps 1 and 3.  The same workspace, from the same size query, must be passed to steps
+ * 1, 3 and 5 with nothing else written to it in between: it holds ALL k models' chunk operators, entering scores,
+ * maps and backpointers (64 bytes per position and sequence).  HMM_OPT_FORCE_DENSE, HMM_OPT_CHUNK and HMM_OPT_SCAN2
+ * act as for hmm_viterbi_scan and must not change between the steps.  Everything runs in order on `stream`, without
+ * host synchronisation: the calls are capturable into a HIP graph.  Every offset into logE_slab, path and the
+ * backpointers is 64-bit.
+ *
+ * hmm_seqshard_vscan_workspace_bytes: a multiple of 256, non-decreasing in R; 0 for q > 64, R < 1 or a bad shape.
+ * hmm_seqshard_vscan_tile: 32 or 64; 0 for q < 1 or q > 64.
+ * Argument checks, in this order, all before any HIP call:
+ *   1. q > hmm_seqshard_vscan_max_states()           HMM_ERR_Q_UNSUPPORTED (-2), ahead of everything
+ *   2. R < 1                                         HMM_ERR_BAD_ARGUMENT  (-6)
+ *   3. k, b, Ls or q < 1, k * b > 2^24, or more than 2^31 - 1 chunks
+ *                                                    HMM_ERR_BAD_SHAPE     (-1)
+ *   4. apply / path: r outside 0 .. R-1; apply: (seq_start != 0) != (r == 0)
+ *                                                    HMM_ERR_BAD_ARGUMENT  (-6)
+ *   5. a NULL pointer among the arguments            HMM_ERR_NULL_POINTER  (-3)
+ *   6. workspace_bytes below the size query, or a workspace not aligned to 256 bytes
+ *                                                    HMM_ERR_WORKSPACE     (-4)
+ */
+int hmm_seqshard_vscan_max_states(void);
+int hmm_seqshard_vscan_tile(int q);
+size_t hmm_seqshard_vscan_workspace_bytes(int k, int b, int Ls, int q, int R);
+int hmm_seqshard_vscan_reduce(const float *logA, const float *logpi, const float *logE_slab,
+                              int k, int b, int Ls, int q, int seq_start, int R,
+                              int *slab_vop, long long *slab_vbase,
+                              void *workspace, size_t workspace_bytes, void *stream);
+int hmm_seqshard_vscan_apply(const float *logA, const float *logpi, const float *logE_slab,
+                             int k, int b, int Ls, int q, int seq_start,
+                             const int *all_vops, const long long *all_vbases, int R, int r,
+                             unsigned char *slab_origin, int *final_state, double *score,
+                             void *workspace, size_t workspace_bytes, void *stream);
+int hmm_seqshard_vscan_path(int k, int b, int Ls, int q,
+                            const unsigned char *all_origins, const int *final_state, int R, int r,
+                            int32_t *path,
+                            void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Gradient of the log-likelihoods (training).  The reference trains by autograd through the
