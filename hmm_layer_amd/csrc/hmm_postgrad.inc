@@ -403,6 +403,19 @@ int hmm_posterior_grad(const float *A, const float *pi, const float *E, int k, i
     if (!A || !pi || !E || !grad_out || !dA || !dpi || !dE || !workspace) return HMM_ERR_NULL_POINTER;
     char *ws = (char *)workspace;
     hipStream_t st = (hipStream_t)stream;
+    if (q == 1) {
+        // gamma = 1 identically, whatever A, pi and E: every gradient is exactly zero.  The sweeps return rounding
+        // noise instead: alpha_hat = sf * v_rcp_f32(sf) is 1 only to an ulp, the centring terms G (1 - alpha_hat) do
+        // not cancel, and over b * L positions dA collects 1e-6 per unit of |G| (measured: 1.08e-6 at b = 3, L = 203).
+        PgPlan pp;
+        make_pgplan(k, b, L, q, &pp);
+        if (workspace_bytes < pp.total || ((uintptr_t)workspace & 255)) return HMM_ERR_WORKSPACE;
+        if (hipMemsetAsync(dA, 0, (size_t)k * sizeof(float), st) != hipSuccess ||
+            hipMemsetAsync(dpi, 0, (size_t)k * sizeof(float), st) != hipSuccess ||
+            hipMemsetAsync(dE, 0, (size_t)k * b * L * sizeof(float), st) != hipSuccess)
+            return HMM_ERR_LAUNCH;
+        return HMM_OK;
+    }
     if (pc_wanted(k, b, L, q)) {
         PcPlan pc;
         int rc = make_pcplan(k, b, L, q, &pc);

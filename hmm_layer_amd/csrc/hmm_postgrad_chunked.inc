@@ -81,6 +81,7 @@ static bool pc_wanted(int k, int b, int L, int q) {
     const int o = opt(HMM_OPT_PGCHUNK);
     const int W = pc_width(q);
     if (o == 0 || W == 0) return false;
+    if (q == 1) return false;                                // hmm_posterior_grad returns exact zeros: nothing to cut into chunks
     if ((long long)L * q * (long long)sizeof(float) >= (1ll << 31) - 4096) return false;   // 32-bit row offsets
     if ((long long)k * b > (1ll << 30) / 64) return false;
     const int T = pc_chunk_len(k, b, L), C = (L + T - 1) / T;

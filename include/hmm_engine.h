@@ -836,13 +836,15 @@ int hmm_loglik_grad_large(const float *A, const float *pi, const float *E,
  *   mode      HMM_POST_PROB (out = gamma) or HMM_POST_LOG (out = log gamma)
  *   grad_out  (k,b,L,q) : d loss / d out
  *   dA (k,q,q), dpi (k,q), dE (k,b,L,q) : d loss / d A, pi, E; clamped entries receive nothing
- * Deterministic (fixed summation order).
+ * Deterministic (fixed summation order).  q = 1: the posterior is identically 1 and every gradient exactly zero; the
+ * call returns zeros without running a sweep (hmm_posterior_grad_serial_count then reports k * b), also for
+ * non-finite inputs, which the sweeps of q >= 2 propagate as NaN.
  *
  * For q <= 16 and up to 4096 sequences the sweeps run per chunk of the scan plan, in parallel (the
  * adjoint recursions are affine in the adjoint vector: every chunk's map is measured, the maps are
  * scanned, the sweeps rerun from the true entering vectors; HMM_OPT_PGCHUNK).  Which sequences that
  * path may serve is decided on the device as for hmm_posterior — per model by the support of A, per
- * sequence by the floor-transition bound F = eps * sum_t 1 / <alpha_hat_t, R_t> <= 1e-6 — and in log
+ * sequence by the floor-transition bound F = eps * sum_t 1 / <alpha_hat_t, R_t> <= 2e-6 — and in log
  * mode additionally by how much of the upstream gradient sits on states whose posterior is so small
  * that floor paths can matter for THEM: sum |G| min(1, F / gamma) <= 1e-4 sum |G|.  The remaining
  * sequences are redone by whole-sequence sweeps in the same call.  The compiled 29-state two-copy

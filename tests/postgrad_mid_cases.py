@@ -77,7 +77,7 @@ def gene_model(copies):
     return A, pi
 
 
-def forward_clamp_model(rng, q):
+def forward_clamp_model(rng, q, edge=1e-20):
     """tests/test_posterior_grad_large_gpu.py::test_clamped_predicted_state: state D = q - 1 is entered by a PRESENT
     edge 0 -> D of weight 1e-20 alone and emits with probability 1 (build()), so the forward cell clamps its predicted
     mass at every position t >= 1.  One departure from that test: pi[D] is not 0.  With pi[D] = 0 the state sits on the
@@ -87,7 +87,7 @@ def forward_clamp_model(rng, q):
     D = q - 1
     A = rng.random((q, q)) ** 2 + 1e-2
     A[:, D] = 0.0
-    A[0, D] = 1e-20
+    A[0, D] = edge
     A[D, :] = 0.0
     A[D, 0] = 1.0
     A /= A.sum(-1, keepdims=True)
@@ -124,9 +124,10 @@ def build_model(rng, name, q):
     return rand_model(rng, q, sparse=name == "sparse", dead=3, tiny_pi=2)
 
 
-def forward_backward64(A, pi, E, eps=EPS):
+def forward_backward64(A, pi, E, eps=EPS, parts=False):
     """The recursion of oracle/torch64.posterior restated in numpy fp64 with its intermediates: gamma (b,L,q) and how
-    often each clamp is active: forward predicted state <= eps (t >= 1), A bh <= eps, pi <= eps, E <= eps."""
+    often each clamp is active: forward predicted state <= eps (t >= 1), A bh <= eps, pi <= eps, E <= eps.
+    parts=True: also alpha_hat and Rb (b,L,q), whose products are gamma before it is normalised."""
     A, pi, E = np.asarray(A, np.float64), np.asarray(pi, np.float64), np.asarray(E, np.float64)
     b, L, q = E.shape
     Ec = np.maximum(E, eps)
@@ -152,8 +153,8 @@ def forward_backward64(A, pi, E, eps=EPS):
         sb = Ec[:, t] * R
         bh = sb / sb.sum(-1, keepdims=True)
     g = ah * Rb
-    return g / g.sum(-1, keepdims=True), dict(forward=n_fwd, backward=n_bwd, pi=int((pi <= eps).sum()) * b,
-                                              E=int((E <= eps).sum()))
+    count = dict(forward=n_fwd, backward=n_bwd, pi=int((pi <= eps).sum()) * b, E=int((E <= eps).sum()))
+    return (g / g.sum(-1, keepdims=True), count) + ((ah, Rb) if parts else ())
 
 
 def build(spec):

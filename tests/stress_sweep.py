@@ -80,9 +80,12 @@ def run(ncase, seed, verbose=True):
           m = A > 0
           e3 = max((np.abs(dA.cpu().numpy()[0] - rA)[m].max() if m.any() else 0.0) / max(np.abs(rA).max(), 1e-30),
                    np.abs(dE.cpu().numpy()[0] - rE).max() / max(np.abs(rE).max(), 1e-30))
-      if L <= 100 and not clampy:                       # gradients of the posteriors against fp64 autograd
-          Gup = rng.standard_normal((b, L, q)).astype(np.float32)
-          mode = engine.POST_LOG if rng.random() < 0.5 else engine.POST_PROB
+      if L <= 100:                                      # gradients of the posteriors against fp64 autograd
+          # (clamped cases draw from a generator of their own, so that the main stream, and with it every case,
+          # is what it was when they were left out)
+          grng = np.random.default_rng([seed, case]) if clampy else rng
+          Gup = grng.standard_normal((b, L, q)).astype(np.float32)
+          mode = engine.POST_LOG if grng.random() < 0.5 else engine.POST_PROB
           pA, ppi, pE = engine.posterior_grad(t(A)[None], t(pi)[None], t(E)[None], t(Gup)[None], mode=mode)
           qA, qpi, qE, _ = torch64.posterior_grad(A, pi, E, Gup, log=(mode == engine.POST_LOG))
           # (with q = 1 the posterior is identically 1 and its gradient 0: absolute floor on the scale: fp32 noise of a few 1e-6 against upstream gradients of order 1)
