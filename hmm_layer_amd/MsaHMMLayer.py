@@ -86,6 +86,32 @@ def _state_posterior_log_probs_impl(inputs, cell, reverse_cell=None, bidirection
     return _with_prior(cell, post, return_prior)
 
 
+def state_posterior_log_probs_sharded(E_slab, cell, group=None, no_loglik=False):
+    """This rank's time slab of emission probabilities E_slab (k, b, Ls, q) on a HIP device -> (log posteriors of the
+    slab (k,b,Ls,q) — with no_loglik the normaliser is left in, as in state_posterior_log_probs —, loglik (k,b) fp64
+    of the WHOLE sequences).  The counterpart of Viterbi.viterbi_sharded for the posteriors, for models of up to 64
+    states; inference only.
+
+    Ranks of `group` hold consecutive slabs in rank order (rank 0 owns position 0; slab lengths may differ).  A and pi
+    are taken from the cell exactly as state_posterior_log_probs takes them.  Sequences that the eps clamps decide
+    (seqshard.posterior's needs_unsharded) are recomputed unsharded on rank 0 of the group and every rank gets its own
+    slab of them back (seqshard.gather_flagged), so what is returned is final.  The caller produces E_slab with
+    whatever halo its emitter needs; nothing but the slab operators, the certificates and the flagged sequences is
+    exchanged here."""
+    from . import seqshard
+    if cell.epsilon != engine.EPS:
+        raise ValueError("the sequence-sharded posterior runs with the engine's epsilon %g (cell: %g)"
+                         % (engine.EPS, cell.epsilon))
+    cell.recurrent_init()
+    with torch.no_grad():
+        E = E_slab.detach().to(torch.float32).contiguous()
+        A = cell.A.detach().to(E.device, torch.float32).contiguous()
+        pi = cell.init_dist.detach().to(E.device, torch.float32).reshape(cell.num_models, cell.max_num_states).contiguous()
+        mode = engine.POST_LOG_NO_LL if no_loglik else engine.POST_LOG
+        out, loglik, flagged = seqshard.posterior(A, pi, E, mode=mode, group=group)
+        return seqshard.gather_flagged(A, pi, E, out, loglik, flagged, mode=mode, group=group)
+
+
 def _wants_grad(inputs, cell):
     if not torch.is_grad_enabled():
         return False

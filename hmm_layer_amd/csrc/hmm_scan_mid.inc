@@ -63,10 +63,14 @@ struct WsMid {
 // ---- what differs between the widths on the host: how the model check and the reduce stage are launched
 struct Scan32 {
     static constexpr int NT = 2, W = Rows<NT>::W;
-    static void check(const float *A, const MidPlan &pp, float eps, char *ws, hipStream_t st) {
+    // exact_mode: the routing mode the verdict is formed under (default: the option's); elig: where it goes (default:
+    // the plan's elig[k]).  The sequence-sharded calls ask twice: HMM_EXACT_OFF for the scan, HMM_EXACT_AUTO for the
+    // model's primitivity.
+    static void check(const float *A, const MidPlan &pp, float eps, char *ws, hipStream_t st, int exact_mode = -1,
+                      int *elig = nullptr) {
         const WsMid w(pp, ws);
-        launch(k32_check, dim3(pp.p.k), dim3(64), 0, st, A, w.elig, pp.p.q, opt(HMM_OPT_EXACT), eps, w.nex,
-               opt(HMM_OPT_FORCE_DENSE) == 1 ? 1 : 0);
+        launch(k32_check, dim3(pp.p.k), dim3(64), 0, st, A, elig ? elig : w.elig, pp.p.q,
+               exact_mode < 0 ? opt(HMM_OPT_EXACT) : exact_mode, eps, w.nex, opt(HMM_OPT_FORCE_DENSE) == 1 ? 1 : 0);
     }
     // the compiled sparse topology first, then the dense reduce for the models outside it
     static void reduce(const float *A, const float *E, const MidPlan &pp, float eps, char *ws, hipStream_t st) {
@@ -85,9 +89,12 @@ struct Scan32 {
 
 struct Scan64 {
     static constexpr int NT = 4, W = Rows<NT>::W;
-    static void check(const float *A, const MidPlan &pp, float eps, char *ws, hipStream_t st) {
+    // (exact_mode given — the sequence-sharded calls —: nseq = 0 keeps the sparse models' routing rule out of it)
+    static void check(const float *A, const MidPlan &pp, float eps, char *ws, hipStream_t st, int exact_mode = -1,
+                      int *elig = nullptr) {
         const WsMid w(pp, ws);
-        launch(k64_check, dim3(pp.p.k), dim3(64), 0, st, A, w.elig, pp.p.q, opt(HMM_OPT_EXACT), eps, w.nex, pp.p.NB,
+        launch(k64_check, dim3(pp.p.k), dim3(64), 0, st, A, elig ? elig : w.elig, pp.p.q,
+               exact_mode < 0 ? opt(HMM_OPT_EXACT) : exact_mode, eps, w.nex, exact_mode < 0 ? pp.p.NB : 0,
                opt(HMM_OPT_FORCE_DENSE) == 1 ? 1 : 0);
     }
     static void reduce(const float *A, const float *E, const MidPlan &pp, float eps, char *ws, hipStream_t st) {
@@ -110,7 +117,7 @@ static void scan_reduce_scan(const float *A, const float *pi, const float *E, co
     S::check(A, pp, eps, ws, st);
     S::reduce(A, E, pp, eps, ws, st);
     launch(scan<S::NT>, dim3(pp.p.NB), dim3(128), 0, st, pi, w.ops, w.exps, w.prefix, w.llpre, w.suffix, w.lsuf, w.loglik,
-           w.elig, pp.p, eps);
+           w.elig, pp.p, eps, nullptr, nullptr, nullptr, nullptr);
 }
 
 // need[] from the certificate sums phi (or null: the reduces' marks only); one kernel for both widths

@@ -11,7 +11,8 @@
 //            X <- diag(E_t) A^T X = NT^3 16x16x16 block products, columns rescaled by exact powers of two —
 //            k_reduce for 16 states, NT^3 times over: 2 q^3 flop per position.  The compiled 29-state topology
 //            has its own sparse reduce (k_reduce_sparse_wide<TopoGene29>: 32 lanes per chain, 45 structural fma's)
-//   scan     scan<NT>: chunk-level prefix / suffix hops over W x W operators, one wave per direction
+//   scan     scan<NT>: chunk-level prefix / suffix hops over W x W operators, one wave per direction (from given entry
+//            vectors for a time slab of a sequence-sharded call; compose<NT> forms a slab's operator: hmm_seqshard_mid.inc)
 //   apply    forward<NT> / backward<NT>: NT tile rows per chain (a W-state vector is NT tile rows; a step's
 //            mat-vec is NT^2 block products), the cell's exact step, alpha_hat checkpoints every BLK steps, the
 //            clamp flags of psi in the sign bits (backward_body in hmm_engine.hip), posteriors staged in LDS
@@ -299,7 +300,7 @@ __device__ __forceinline__ ChainTile make_chain_tile(const float *E, const Plan 
     const int c = (int)(tl.chain - seq * p.C);
     const long long seq0 = c0 / p.C;
     const int cc0 = (int)(c0 - seq0 * p.C);
-    tl.first = c == 0;
+    tl.first = c == 0 && p.seq_start;        // (a later time slab's chunk 0 is an ordinary chunk: hmm_seqshard_mid_*)
     tl.len = tl.valid ? min(p.T, p.L - c * p.T) : 0;
     const long long row0 = seq0 * p.L + (long long)cc0 * p.T;
     const long long row = seq * p.L + (long long)c * p.T;
@@ -509,7 +510,11 @@ __global__ __launch_bounds__(128) void scan(const float *__restrict__ pi, const 
                                            const int *__restrict__ exps, float *__restrict__ prefix,
                                            double *__restrict__ llpre, float *__restrict__ suffix,
                                            double *__restrict__ lsuf, double *__restrict__ loglik,
-                                           const int *__restrict__ elig, Plan p, float eps) {
+                                           const int *__restrict__ elig, Plan p, float eps,
+                                           const float *__restrict__ entry_pre, const double *__restrict__ entry_ll,
+                                           const float *__restrict__ entry_suf, const double *__restrict__ entry_ls) {
+    // entry_pre / entry_ll / entry_suf / entry_ls (null: the start distribution and ones): the vectors entering a time
+    // slab from the slabs before / after it ([seq][W], hmm_seqshard_mid_*), as k_scan takes them for 16 states
     constexpr int W = Rows<NT>::W;
     constexpr bool PRE = Rows<NT>::SCAN_PREFETCH;
     const int seq = blockIdx.x;
@@ -522,9 +527,10 @@ __global__ __launch_bounds__(128) void scan(const float *__restrict__ pi, const 
     const bool act = lane < q;
     const int n = lane & (W - 1);
     if (dir == 0) {
-        const float praw = act ? pi[(size_t)m * q + lane] : 0.f;
-        float a = act ? fmaxf(praw, eps) : 0.f;
-        double ll = 0.0;
+        // (a given entry vector is taken as it is: the clamp belongs to pi only)
+        const float praw = act ? (entry_pre ? entry_pre[(size_t)seq * W + lane] : pi[(size_t)m * q + lane]) : 0.f;
+        float a = entry_pre ? praw : (act ? fmaxf(praw, eps) : 0.f);
+        double ll = entry_ll ? entry_ll[seq] : 0.0;
         if (lane < W) prefix[chain0 * W + lane] = praw;
         if (lane == 0) llpre[chain0] = 0.0;
         f4 rw[W / 4];                                        // row n of operator c
@@ -564,8 +570,8 @@ __global__ __launch_bounds__(128) void scan(const float *__restrict__ pi, const 
         }
         if (lane == 0) loglik[seq] = ll;
     } else {
-        float v = act ? 1.f : 0.f;
-        double lb = 0.0;
+        float v = act ? (entry_suf ? entry_suf[(size_t)seq * W + lane] : 1.f) : 0.f;
+        double lb = entry_ls ? entry_ls[seq] : 0.0;
         float col[PRE ? W : 1];                              // PRE: column n of the next operator
         int xe = 0;
         auto fetch = [&](int c) {
@@ -602,6 +608,141 @@ __global__ __launch_bounds__(128) void scan(const float *__restrict__ pi, const 
             lb += (double)emax * LN2;
         }
     }
+}
+
+// ---- compose: k_scan_compose at width W.  One wave per (sequence, group): X <- Op_c X over the group's operators
+// (chunks c0 .. c1 - 1 of ops[seq][p.C]), X the identity at the start and held as reduce_dense holds it (X[cb].t[r]:
+// lane (g, n) has rows 16 r + 4g .. + 3 of column 16 cb + n, the column scaled by 2^-ex[cb]).  The hops carry no
+// clamp, so operators compose exactly up to rounding; the sequence-sharded posterior (hmm_seqshard_mid_*) forms a time
+// slab's operator this way, in two levels for long slabs.  Per hop and column: the rows are aligned to a common
+// exponent (their own plus the exponent of the operator column they meet; the shift clamped at -300), multiplied, and
+// the column sum brought back into [0.5, 1) by an exact power of two.  A column without a positive entry stays zero
+// (emax = 0), and the factor stays finite for a sum in the denormal range (the exponent clamped at -100, as in
+// reduce_dense).  Rows, columns and exponents from q on are written as 0.  The next operator is in flight during a hop.
+template <int NT>
+__global__ __launch_bounds__(256) void compose(const float *__restrict__ ops, const int *__restrict__ exps,
+                                               float *__restrict__ gops, int *__restrict__ gexps, Plan p) {
+    constexpr int W = Rows<NT>::W;
+    const long long wv = (long long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (wv >= (long long)p.NB * p.G) return;
+    const int lane = threadIdx.x & 63, g = lane >> 4, n = lane & 15;
+    const int q = p.q;
+    const int seq = (int)(wv / p.G), grp = (int)(wv - (long long)seq * p.G);
+    const int c0 = grp * p.gsize, c1 = min(p.C, c0 + p.gsize);
+    XT<NT> X[NT];
+#pragma unroll
+    for (int cb = 0; cb < NT; ++cb)
+#pragma unroll
+        for (int r = 0; r < NT; ++r) {
+            const int col = 16 * cb + n, row = 16 * r + 4 * g;
+            const bool on = col < q;
+            X[cb].t[r] = (f4){on && row + 0 == col ? 1.f : 0.f, on && row + 1 == col ? 1.f : 0.f,
+                              on && row + 2 == col ? 1.f : 0.f, on && row + 3 == col ? 1.f : 0.f};
+        }
+    int ex[NT] = {};
+    const size_t chb = (size_t)seq * p.C;
+    // A-operand: lane (g, i = n) supplies Op[16 r + i][16 c + 4g + kk]; en[r]: exponents of the contraction rows
+    AT<NT> an;
+    i4 en[NT];
+    auto fetch = [&](int c) {
+        const float *op = ops + (chb + c) * W * W;
+        const int *oe = exps + (chb + c) * W;
+#pragma unroll
+        for (int r = 0; r < NT; ++r) {
+#pragma unroll
+            for (int cc = 0; cc < NT; ++cc) an.a[r][cc] = *reinterpret_cast<const f4 *>(op + (16 * r + n) * W + 16 * cc + 4 * g);
+            const i4 e = *reinterpret_cast<const i4 *>(oe + 16 * r + 4 * g);
+            const int s0 = 16 * r + 4 * g;                   // (the pad lanes carry no exponent: the sparse reduce's mark)
+            en[r] = (i4){s0 + 0 < q ? e.x : 0, s0 + 1 < q ? e.y : 0, s0 + 2 < q ? e.z : 0, s0 + 3 < q ? e.w : 0};
+        }
+    };
+    fetch(c0);
+    for (int c = c0; c < c1; ++c) {
+        const AT<NT> a = an;
+        i4 e[NT];
+#pragma unroll
+        for (int r = 0; r < NT; ++r) e[r] = en[r];
+        if (c + 1 < c1) fetch(c + 1);
+#pragma unroll
+        for (int cb = 0; cb < NT; ++cb) {
+            int we = -(1 << 28);
+#pragma unroll
+            for (int r = 0; r < NT; ++r) {
+                const f4 x = X[cb].t[r];
+                we = x.x > 0.f ? max(we, __builtin_amdgcn_frexp_expf(x.x) + e[r].x) : we;
+                we = x.y > 0.f ? max(we, __builtin_amdgcn_frexp_expf(x.y) + e[r].y) : we;
+                we = x.z > 0.f ? max(we, __builtin_amdgcn_frexp_expf(x.z) + e[r].z) : we;
+                we = x.w > 0.f ? max(we, __builtin_amdgcn_frexp_expf(x.w) + e[r].w) : we;
+            }
+            int emax = col_max_i(we);
+            emax = emax == -(1 << 28) ? 0 : emax;
+            XT<NT> w;
+#pragma unroll
+            for (int r = 0; r < NT; ++r) {
+                const f4 x = X[cb].t[r];
+                w.t[r] = (f4){__builtin_amdgcn_ldexpf(x.x, max(e[r].x - emax, -300)),
+                              __builtin_amdgcn_ldexpf(x.y, max(e[r].y - emax, -300)),
+                              __builtin_amdgcn_ldexpf(x.z, max(e[r].z - emax, -300)),
+                              __builtin_amdgcn_ldexpf(x.w, max(e[r].w - emax, -300))};
+            }
+            const XT<NT> d = matvec<NT>(a, w);
+            // bring the column sum back into [0.5, 1): exact power of two
+            const int xe = max(__builtin_amdgcn_frexp_expf(sum<NT>(d)), -100);
+            const float sc = __builtin_amdgcn_ldexpf(1.0f, -xe);
+#pragma unroll
+            for (int r = 0; r < NT; ++r) X[cb].t[r] = d.t[r] * sc;
+            ex[cb] += emax + xe;
+        }
+    }
+    float *o = gops + (size_t)wv * W * W;
+#pragma unroll
+    for (int cb = 0; cb < NT; ++cb) {
+        const int col = 16 * cb + n;
+#pragma unroll
+        for (int r = 0; r < NT; ++r) {
+            const int row = 16 * r + 4 * g;
+            o[(row + 0) * W + col] = col < q && row + 0 < q ? X[cb].t[r].x : 0.f;
+            o[(row + 1) * W + col] = col < q && row + 1 < q ? X[cb].t[r].y : 0.f;
+            o[(row + 2) * W + col] = col < q && row + 2 < q ? X[cb].t[r].z : 0.f;
+            o[(row + 3) * W + col] = col < q && row + 3 < q ? X[cb].t[r].w : 0.f;
+        }
+        if (g == 0) gexps[(size_t)wv * W + col] = col < q ? ex[cb] : 0;
+    }
+}
+
+// entry vectors of slab r out of the global hops' per-slab vectors [seq][R] (k_seqshard_pick at width W)
+__global__ __launch_bounds__(256) void k_mid_pick(const float *__restrict__ gpre, const double *__restrict__ gll,
+                                                  const float *__restrict__ gsuf, const double *__restrict__ gls,
+                                                  float *__restrict__ pre, double *__restrict__ ll,
+                                                  float *__restrict__ suf, double *__restrict__ ls, int NB, int R, int r,
+                                                  int W) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)NB * W) return;
+    const long long seq = i / W;
+    const int n = (int)(i - seq * W);
+    pre[i] = gpre[((size_t)seq * R + r) * W + n];
+    suf[i] = gsuf[((size_t)seq * R + r) * W + n];
+    if (n == 0) { ll[seq] = gll[(size_t)seq * R + r]; ls[seq] = gls[(size_t)seq * R + r]; }
+}
+
+// phi_out[seq] = the time slab's share of the sequence's clamp-born posterior mass: psi of backward<NT> summed over
+// the slab's chunks, a whole 1 for every chain a reduce marked (where the marks live: k_scan_select); +inf when the
+// model's support is not primitive (prim[m] == 0: the model check under HMM_EXACT_AUTO)
+__global__ __launch_bounds__(256) void k_mid_phi(const float *__restrict__ psi, const int *__restrict__ elig,
+                                                 const int *__restrict__ prim, const int *__restrict__ exps,
+                                                 const int *__restrict__ risk, float *__restrict__ phi_out, Plan p,
+                                                 int W) {
+    const int seq = blockIdx.x * 256 + threadIdx.x;
+    if (seq >= p.NB) return;
+    const int m = seq / p.b;
+    const bool dense = elig_dense(elig[m]);
+    float s = 0.f;
+    for (int c = 0; c < p.C; ++c) {
+        const size_t chain = (size_t)seq * p.C + c;
+        s += psi[chain];
+        if (dense ? risk[chain] != 0 : exps[chain * W + W - 1] != 0) s += 1.f;
+    }
+    phi_out[seq] = prim[m] == 0 ? __builtin_inff() : s;
 }
 
 // ---- apply, forward.  LOGA = false, CERT = false: alpha_hat entering every BLK-step block -> ckpt

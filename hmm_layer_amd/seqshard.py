@@ -7,6 +7,7 @@ runs one level up, across devices, for batches too small to be cut by sequence (
 
     reduce      local     the slab's operator per sequence, 1.1 KB            (hmm_seqshard_reduce)
     all-gather  RCCL      twice: the operators (k,b,16,16) fp32 and their exponents (k,b,16) int32 per rank
+                          (17 to 64 states: hmm_seqshard_mid_*, seqshard_mid.py, tiles of 32 or 64 instead of 16)
     finish      local     hops over the R slab operators, local chunk scan, apply kernels
                                                                               (hmm_seqshard_posterior)
     all-reduce  RCCL      k*b floats: the sequences' clamp-born posterior mass, summed over ranks
@@ -57,20 +58,31 @@ class EngineBackend:
 
 
 def stack_slab_operators(ops, exps):
-    """Per-rank results in time order, each (k,b,16,16) / (k,b,16) -> the layout the finish step reads:
-    (k,b,R,16,16) / (k,b,R,16), contiguous."""
+    """Per-rank results in time order, each (k,b,QT,QT) / (k,b,QT) — QT = 16 up to 16 states, 32 or 64 above
+    (seqshard_mid.tile) — -> the layout the finish step reads: (k,b,R,QT,QT) / (k,b,R,QT), contiguous."""
     return torch.stack(list(ops), dim=2).contiguous(), torch.stack(list(exps), dim=2).contiguous()
+
+
+def posterior_backend(q):
+    """The engine backend that serves q states: hmm_seqshard_* up to 16, hmm_seqshard_mid_* for 17 to 64."""
+    if q <= 16:
+        return EngineBackend()
+    if q > 64:
+        raise ValueError("sequence-sharded posteriors cover q <= 64 states, got %d" % q)
+    from .seqshard_mid import MidEngineBackend
+    return MidEngineBackend()
 
 
 def posterior(A, pi, E_slab, mode=engine.POST_PROB, group=None, backend=None):
     """-> (out (k,b,Ls,q), loglik (k,b) of the whole sequences, needs_unsharded (k,b) bool).
 
     Ranks of `group` hold consecutive time slabs in rank order (rank 0 owns position 0); slab lengths
-    may differ.  Sequences flagged in `needs_unsharded` (summed clamp-born posterior mass above 2e-6, or a
+    may differ; q <= 64 (backend None: the engine's, by q — posterior_backend).  Sequences flagged in
+    `needs_unsharded` (summed clamp-born posterior mass above 2e-6, or a
     model whose support is not primitive) are decided by the eps clamps and have to be recomputed by
     the unsharded call on one device (gather_flagged); everything else is final."""
     import torch.distributed as dist
-    backend = backend or EngineBackend()
+    backend = backend or posterior_backend(int(E_slab.shape[-1]))
     R = dist.get_world_size(group)
     r = dist.get_rank(group)
     op, ex = backend.reduce(A, E_slab, r == 0, R)
@@ -96,7 +108,7 @@ def gather_flagged(A, pi, E_slab, out, loglik, needs_unsharded, mode=engine.POST
     sequences (slab lengths may differ), it runs the unsharded call and sends every rank ITS OWN slab of the
     result back; the log-likelihoods (a few doubles) are broadcast.  In place on `out` / `loglik`."""
     import torch.distributed as dist
-    backend = backend or EngineBackend()
+    backend = backend or posterior_backend(int(E_slab.shape[-1]))
     R, r = dist.get_world_size(group), dist.get_rank(group)
     flagged = needs_unsharded.nonzero(as_tuple=False).tolist()          # one host sync for the whole call
     if not flagged:

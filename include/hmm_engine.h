@@ -33,7 +33,7 @@
  * Alignment of the pointers:
  *   - workspace: 256 bytes;
  *   - 16 bytes: E of hmm_gene_emissions, dx of hmm_gene_emissions_grad and of hmm_gene_emissions_grad_wide (whole
- *     tiles of 16 positions leave as aligned 16-byte pieces), all_ops of hmm_seqshard_posterior and all_vops of
+ *     tiles of 16 positions leave as aligned 16-byte pieces), all_ops of hmm_seqshard_posterior and hmm_seqshard_mid_posterior, all_vops of
  *     hmm_seqshard_viterbi_apply and hmm_seqshard_vscan_apply (the hops read the gathered operators' rows as aligned
  *     16-byte pieces);
  *   - every other pointer: the alignment of its element type — 4 bytes for fp32 and int32 tensors (a view such as
@@ -739,6 +739,61 @@ int hmm_seqshard_vscan_path(int k, int b, int Ls, int q,
                             const unsigned char *all_origins, const int *final_state, int R, int r,
                             int32_t *path,
                             void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Sequence-sharded posteriors for 17 to 64 states: the protocol of hmm_seqshard_reduce / hmm_seqshard_posterior on
+ * the chunked scan that serves hmm_posterior in this range, with operators in tiles of QT = hmm_seqshard_mid_tile(q)
+ * = 32 (17..32 states) or 64 (33..64).  Every rank owns one contiguous TIME slab of every sequence, E_slab
+ * (k,b,Ls,q), Ls may differ between ranks.  R ranks, rank r (slabs in time order):
+ *   1. hmm_seqshard_mid_reduce(...)    -> slab_op (k,b,QT,QT) fp32, slab_exp (k,b,QT) int32: the slab's operator per
+ *                                         sequence.  slab_op[i][k] * 2^slab_exp[k] (i, k < q) is the product of the
+ *                                         slab's step matrices: i the state at the slab's last position, k the state
+ *                                         before the slab (with seq_start = 1 the first position takes no
+ *                                         transition).  Every column k < q sums to a value in [0.5, 1), or is all
+ *                                         zero.  The padding is written on every call: 0 in the rows and columns of
+ *                                         slab_op from q on and in slab_exp from q on.  Never NaN or inf.
+ *   2. host: all-gather slab_op / slab_exp over the ranks and lay them out (k,b,R,QT,QT) / (k,b,R,QT); all_ops
+ *      16-byte aligned (the hops read the operators' rows as aligned 16-byte pieces)
+ *   3. hmm_seqshard_mid_posterior(...) -> out (k,b,Ls,q) per `mode` (HMM_POST_*), loglik (k,b) or NULL = the WHOLE
+ *                                         sequence's, the same bits on every rank, phi_out (k,b) fp32 or NULL: this
+ *                                         slab's share of the sequence's floor-transition bound (psi of hmm_posterior
+ *                                         summed over the slab's chunks, plus 1 for every chunk whose reduce left its
+ *                                         mark: operator columns through the denormal range, or an observation that
+ *                                         every state survives at the emission floor only; +inf when A's support is
+ *                                         not primitive).  The host sums phi over ranks; above 2e-6 the sequence needs
+ *                                         the unsharded call (the serial kernels cannot be cut in time).
+ * seq_start: 1 on the rank that owns position 0 (r == 0), else 0.  The same workspace (same size query) must be passed
+ * to steps 1 and 3 with nothing else written to it in between: the chunk operators and the model verdicts stay in it.
+ * The range served is 17 <= q <= 64 (hmm_seqshard_mid_max_states() = 64; up to 16 states: hmm_seqshard_*), every
+ * k * b <= 2^24 and every Ls >= 1: hmm_posterior's routing rules for 33..64 states (at most 96 sequences, at least 256
+ * positions) do not apply here.  HMM_OPT_CHUNK and HMM_OPT_FORCE_DENSE act as for hmm_posterior and must not change
+ * between the steps; HMM_OPT_EXACT is ignored: these calls always run the scan.  Everything runs in order on
+ * `stream`, without host synchronisation: the calls are capturable into a HIP graph.
+ *
+ * hmm_seqshard_mid_workspace_bytes: a multiple of 256, non-decreasing in R; 0 for q outside 17..64, R < 1 or a bad
+ * shape.  hmm_seqshard_mid_tile: 32 or 64; 0 for q outside 17..64.
+ * Argument checks, in this order, all before any HIP call:
+ *   1. q > 64, or q < 17                             HMM_ERR_Q_UNSUPPORTED (-2), ahead of everything
+ *   2. R < 1                                         HMM_ERR_BAD_ARGUMENT  (-6)
+ *   3. k, b or Ls < 1, or k * b > 2^24               HMM_ERR_BAD_SHAPE     (-1)
+ *   4. hmm_seqshard_mid_posterior only: r outside 0 .. R-1, or (seq_start != 0) != (r == 0), then a mode outside
+ *      HMM_POST_PROB .. HMM_POST_LOG_NO_LL           HMM_ERR_BAD_ARGUMENT  (-6)
+ *   5. a NULL pointer among A, E, slab_op, slab_exp, workspace (reduce) or A, pi, E, all_ops, all_exps, out,
+ *      workspace (posterior; loglik and phi_out may be NULL)
+ *                                                    HMM_ERR_NULL_POINTER  (-3)
+ *   6. workspace_bytes below the size query, or a workspace not aligned to 256 bytes
+ *                                                    HMM_ERR_WORKSPACE     (-4)
+ */
+int hmm_seqshard_mid_max_states(void);
+int hmm_seqshard_mid_tile(int q);
+size_t hmm_seqshard_mid_workspace_bytes(int k, int b, int Ls, int q, int R);
+int hmm_seqshard_mid_reduce(const float *A, const float *E_slab, int k, int b, int Ls, int q, float eps, int seq_start,
+                            int R, float *slab_op, int *slab_exp,
+                            void *workspace, size_t workspace_bytes, void *stream);
+int hmm_seqshard_mid_posterior(const float *A, const float *pi, const float *E_slab, int k, int b, int Ls, int q,
+                               float eps, int seq_start, const float *all_ops, const int *all_exps, int R, int r,
+                               int mode, float *out, double *loglik, float *phi_out,
+                               void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Gradient of the log-likelihoods (training).  The reference trains by autograd through the
