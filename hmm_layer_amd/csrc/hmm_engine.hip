@@ -77,7 +77,14 @@ typedef int i4 __attribute__((ext_vector_type(4)));
                        // four hops in flight changed nothing in k_scan_inner and cost k_scan_compose 50 -> 73 us
 #endif
 #define SCAN2_MIN_C 32  // chunks per sequence from which the chunk-level scan runs in two levels
-#define MAX_T 512      // longest chunk (512 beat 1024 and 256 on b=1024 x L=1e5: more apply waves, short scan)
+#define MAX_T 512      // longest chunk: the ceiling of choose_T.  Where choose_T stops at it and the apply kernels need more
+                       // than one round of resident blocks, round_T picks the chunk of the <= 16-state plans below it
+// What the round-aware chunk rule (round_T) takes the machine to hold, as constants so that a plan stays a pure function
+// of the shape (hmm_chunk_len and hmm_workspace_bytes are called without a device); hmm_plan_capacity returns them and
+// tests/test_chunk_rounds_gpu.py holds them against the occupancy query and the CU count of the device.
+#define PLAN_CUS 256          // compute units of an MI355X
+#define PLAN_APPLY_BPC 2      // resident 4-wave blocks per CU of k_forward<true,...,16> / k_backward<0,...,16> (LDS: 66 KB each)
+#define PLAN_REDUCE_BPC 4     // ... of k_reduce_sparse<TopoGene15> (128 VGPRs, 34 KB of LDS)
 #define LN2 0.69314718055994530942
 
 // ---- tuning / test options.  Explicit process-wide settings (hmm_set_option); the HMM_ENGINE_*
@@ -151,13 +158,48 @@ static int choose_T(long long NB, int L) {
     return (int)t;
 }
 
+// The apply kernels' blocks at chunk length T: 16 (sequence, chunk) pairs per wave, 4 waves per block (apply_grid).
+static long long plan_apply_blocks(int k, int b, int L, int T) {
+    const long long C = (L + T - 1) / T;
+    return ((long long)k * (((long long)b * C + 15) / 16) + 3) / 4;
+}
+// Modelled cost of a pass at chunk length T, in units of 0.8 ns.  Measured (profiles/rounds_sweep.txt, every multiple of
+// 16 from 256 to 512 at six shapes): k_forward and k_backward take T steps times the blocks the fullest CU serves,
+// ceil(blocks / PLAN_CUS), at ~650 ns per step for the pair — a CU's two resident blocks share its rate, so the quantum
+// is one block per CU, half a round of resident blocks; b = 1024 x L = 1e5: 13 x 512 at T = 512, 14 x 448 at 448.  Every
+// chunk costs the reduce and the scans ~0.8 ns for its operator (1/800 of a step).  The sparse reduce itself shows no
+// such steps in T (1.36 +- 0.01 ms from 12.25 to 23 rounds of its resident blocks), so it has no term here.
+#define PLAN_STEP_W 800
+static long long plan_cost(int k, int b, int L, int T) {
+    const long long per_cu = (plan_apply_blocks(k, b, L, T) + PLAN_CUS - 1) / PLAN_CUS;
+    return PLAN_STEP_W * per_cu * T + (long long)k * b * ((L + T - 1) / T);
+}
+// The chunk length of the <= 16-state plans.  choose_T's, except where that is MAX_T and the apply kernels need more
+// than one round of resident blocks: there the cheapest multiple of 16 from MAX_T down to half of it, never below
+// choose_T's T^3 = 2.25 L floor; ties go to the longer chunk.  Smaller problems have fewer blocks than the machine holds
+// and choose_T has already sized their chunks for that.  HMM_OPT_CHUNK forces T as before.
+static int round_T(int k, int b, int L) {
+    const int t0 = choose_T((long long)k * b, L);
+    const int forced = opt(HMM_OPT_CHUNK);
+    if (forced >= 16 && forced <= MAX_T && forced % 16 == 0) return t0;
+    // one round of resident blocks: 64 (sequence, chunk) pairs to the block (choose_T's 32 768 pairs)
+    if (t0 != MAX_T || (long long)k * b * ((L + t0 - 1) / t0) <= 64ll * PLAN_CUS * PLAN_APPLY_BPC) return t0;
+    int lo = 16;
+    while ((long long)lo * lo * lo * 4 < 9ll * L && lo < MAX_T) lo += 16;
+    if (lo < t0 / 2) lo = t0 / 2;
+    int best = t0;
+    for (int t = t0 - 16; t >= lo; t -= 16)
+        if (plan_cost(k, b, L, t) < plan_cost(k, b, L, best)) best = t;
+    return best;
+}
+
 static int make_plan(int op, int k, int b, int L, int q, Plan *p, int T_fixed = 0) {
     if (k < 1 || b < 1 || L < 1 || q < 1) return HMM_ERR_BAD_SHAPE;
     if (q > QP) return HMM_ERR_Q_UNSUPPORTED;
     if ((long long)k * b > (1ll << 30) / 64) return HMM_ERR_BAD_SHAPE;
     p->k = k; p->b = b; p->L = L; p->q = q;
     p->NB = k * b;
-    p->T = T_fixed ? T_fixed : choose_T(p->NB, L);
+    p->T = T_fixed ? T_fixed : round_T(k, b, L);
     p->C = (L + p->T - 1) / p->T;
     p->nsub = p->T / SUB;
     p->nchains = (long long)p->NB * p->C;
@@ -2756,6 +2798,36 @@ int hmm_chunk_len(int k, int b, int L, int q) {
     Plan p;
     int rc = make_plan(HMM_OP_LOGLIK, k, b, L, q, &p);
     return rc ? rc : p.T;
+}
+
+int hmm_plan_capacity(int which) {
+    switch (which) {
+        case HMM_PLAN_CUS: return PLAN_CUS;
+        case HMM_PLAN_FORWARD_BLOCKS:
+        case HMM_PLAN_BACKWARD_BLOCKS: return PLAN_APPLY_BPC;
+        case HMM_PLAN_REDUCE_BLOCKS: return PLAN_REDUCE_BPC;
+        default: return HMM_ERR_BAD_ARGUMENT;
+    }
+}
+
+int hmm_plan_capacity_device(int which) {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return HMM_ERR_NO_DEVICE;
+    hipError_t e;
+    switch (which) {
+        case HMM_PLAN_CUS: e = hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); break;
+        case HMM_PLAN_FORWARD_BLOCKS:
+            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_forward<true, false, false, false, HMM_POST_BLOCK>, 256, 0);
+            break;
+        case HMM_PLAN_BACKWARD_BLOCKS:
+            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_backward<0, false, false, HMM_POST_BLOCK>, 256, 0);
+            break;
+        case HMM_PLAN_REDUCE_BLOCKS:
+            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_reduce_sparse<TopoGene15>, 256, 0);
+            break;
+        default: return HMM_ERR_BAD_ARGUMENT;
+    }
+    return e == hipSuccess ? n : HMM_ERR_NO_DEVICE;
 }
 
 size_t hmm_workspace_bytes(int op, int k, int b, int L, int q) {

@@ -60,7 +60,8 @@ struct VPlan {
 };
 
 static int make_vplan(int b, int L, int q, VPlan *v) {      // one model at a time
-    int rc = make_plan(HMM_OP_LOGLIK, 1, b, L, q, &v->p);
+    // choose_T's chunk, not the posterior plans' round-aware one: that rule is fitted to k_forward / k_backward
+    int rc = make_plan(HMM_OP_LOGLIK, 1, b, L, q, &v->p, choose_T(b, L));
     if (rc) return rc;
     const Plan &p = v->p;
     size_t off = 0;

@@ -51,6 +51,8 @@ _SIGNATURES = {
     "hmm_scan_max_states": (_I, []),
     "hmm_largeq_tile_cols": (_I, [_I, _I]),
     "hmm_chunk_len": (_I, [_I] * 4),
+    "hmm_plan_capacity": (_I, [_I]),
+    "hmm_plan_capacity_device": (_I, [_I]),
     "hmm_workspace_bytes": (_SZ, [_I] * 5),
     "hmm_forward": (_I, _FORWARD),
     "hmm_backward": (_I, [_P, _P, _I, _I, _I, _I, _F, _P, _P, _SZ, _P]),
@@ -227,6 +229,27 @@ def _stream(device):
 
 def chunk_len(k, b, L, q):
     return lib().hmm_chunk_len(k, b, L, q)
+
+
+def plan_capacity():
+    """What the chunk rule takes the machine to hold (constants of the build) ->
+    dict(cus, forward_blocks_per_cu, backward_blocks_per_cu, reduce_blocks_per_cu).  No device needed."""
+    return _plan_capacity(lib().hmm_plan_capacity)
+
+
+def plan_capacity_device(device=None):
+    """The same read from the device: its compute units and the occupancy query's blocks per compute unit."""
+    with torch.cuda.device(device if device is not None else torch.cuda.current_device()):
+        return _plan_capacity(lib().hmm_plan_capacity_device)
+
+
+def _plan_capacity(fn):
+    out = {}
+    for which, name in enumerate(("cus", "forward_blocks_per_cu", "backward_blocks_per_cu", "reduce_blocks_per_cu")):
+        out[name] = int(fn(which))
+        if out[name] < 0:
+            _check(out[name])
+    return out
 
 
 def largeq_tile_cols(b, q):

@@ -130,8 +130,25 @@ int hmm_scan_max_states(void);
 int hmm_viterbi_max_states(void);
 int hmm_grad_max_states(void);
 
-/* Time-chunk length the engine will use for (k*b, L): a multiple of 16; 0 for the serial large-q path. */
+/* Time-chunk length the engine will use for (k, b, L): a multiple of 16; 0 for the serial large-q path.  A pure
+ * function of the shape (and of HMM_OPT_CHUNK): the forward, backward, log-likelihood and posterior plans of a shape
+ * all use it, and so do the gradient plans built on them.  Where the older rule stops at its ceiling of 512 and the
+ * forward / backward kernels need more than one round of resident blocks, it is the multiple of 16 in [256, 512] at
+ * which the blocks fill the compute units most evenly; hmm_viterbi's plan keeps the older
+ * rule there (512). */
 int hmm_chunk_len(int k, int b, int L, int q);
+
+/* Diagnostics: what that rule takes the machine to hold, constants of the build (no device needed):
+ * compute units (256), resident 4-wave blocks per compute unit of the posterior's forward and backward kernels (2)
+ * and of the sparse 15-state chunk reduce (4).  HMM_ERR_BAD_ARGUMENT for another `which`. */
+#define HMM_PLAN_CUS             0
+#define HMM_PLAN_FORWARD_BLOCKS  1
+#define HMM_PLAN_BACKWARD_BLOCKS 2
+#define HMM_PLAN_REDUCE_BLOCKS   3
+int hmm_plan_capacity(int which);
+/* The same read from the current device: its compute units, the occupancy query's blocks per compute unit for the
+ * three kernels.  HMM_ERR_NO_DEVICE without one. */
+int hmm_plan_capacity_device(int which);
 
 /* Column width (64, 80 or 96) of the GEMM tile the serial large-q path uses for a batch of b
  * sequences per model and q > 64 states (the instantiation is chosen per shape so that the 256 CUs
