@@ -638,6 +638,18 @@ __global__ __launch_bounds__(64) void k_topo_check(const float *__restrict__ A, 
 #define HMM_RS_ORDER2 1    // sparse reduce, unit-weight wave of one model: second-order recurrence on the live states
                            // (the pass-through states' incoming weight folded into the staged emission)
 #endif
+#ifndef HMM_RS_QUADROW
+#define HMM_RS_QUADROW 0   // sparse reduce, second-order step with 16 lanes per chain: a lane reads 4 floats of a step's row,
+                           // the four lanes of a DPP quad hold the row between them (quad_mul / quad_fmac): one 16-byte LDS
+                           // read per step where a lane that reads the whole row for itself takes four.  Bit-identical
+                           // results, a quarter of the LDS reads, 19 % fewer vector instructions per tile with the gate
+                           // below, and slower: 1.40 ms against 1.35 with the gate alone, 1.61 against 1.41 without it
+                           // (the compiler pads every use of an asm result by the next instruction with an s_nop)
+#endif
+#ifndef HMM_RS_SUMGATE
+#define HMM_RS_SUMGATE 1   // sparse reduce, same path: the column sum only where the largest live entry of some column
+                           // is below the rescale threshold (A/B: 1.33-1.42 -> 1.28-1.37 ms, faster in each of six rounds)
+#endif
 #ifndef HMM_RS_ROW128
 #define HMM_RS_ROW128 1    // sparse reduce: read a staged row's last three floats together with the pad float: a 16-byte
                            // LDS read takes 4 LDS cycles per wave, a 12-byte one 8 (A/B: 1.47-1.51 -> 1.37-1.43 ms)
@@ -660,6 +672,46 @@ template <class T> struct RsCfg {
     typedef float Lds[2][CPW][SP_TILE * W + 16];
 };
 
+// HMM_RS_QUADROW.  Lane kc of a chain holds floats 4(kc&3) .. 4(kc&3)+3 of a staged row in `r`: float j is component
+// j&3 of quad lane j>>2, the same in all four quads of the chain.  A VOP2 instruction takes it from there as its DPP
+// source operand, so row[j] * v and acc + row[j] * v stay ONE instruction each, the same multiply / fma on the same
+// numbers as with the row in the lane's own registers.  (The compiler folds __builtin_amdgcn_update_dpp into a
+// multiply but not into a v_fmac: it keeps a v_mov_b32_dpp in front of each.)  The hardware wants two instructions
+// between a VALU write of a register and its use as DPP source, and the compiler does not look inside the asm string:
+// the row registers are written by the LDS read alone and never copied (reduce_sparse_wave keeps two sets and unrolls
+// the step pair).  The other two operands are ordinary reads.  What the compiler does do is pad a use of an asm result
+// by the very next instruction with an s_nop 0 (it cannot rule out a partial write), 24 per 16-step tile: see
+// HMM_RS_QUADROW's A/B.
+// All four lanes of a quad are active wherever these run: lanes leave the step loop a whole chain at a time.
+#define RS_QUAD_OP(op, ql, ...) \
+    asm(op " %0, %1, %2 quad_perm:[" #ql "," #ql "," #ql "," #ql "] row_mask:0xf bank_mask:0xf" : __VA_ARGS__)
+__device__ __forceinline__ float quad_mul(const f4 &r, int j, float v) {            // row[j] * v
+    float d;
+    switch (j >> 2) {
+    case 0: RS_QUAD_OP("v_mul_f32_dpp", 0, "=v"(d) : "v"(r[j & 3]), "v"(v)); break;
+    case 1: RS_QUAD_OP("v_mul_f32_dpp", 1, "=v"(d) : "v"(r[j & 3]), "v"(v)); break;
+    case 2: RS_QUAD_OP("v_mul_f32_dpp", 2, "=v"(d) : "v"(r[j & 3]), "v"(v)); break;
+    default: RS_QUAD_OP("v_mul_f32_dpp", 3, "=v"(d) : "v"(r[j & 3]), "v"(v)); break;
+    }
+    return d;
+}
+__device__ __forceinline__ float quad_fmac(const f4 &r, int j, float v, float acc) { // fma(row[j], v, acc)
+    switch (j >> 2) {
+    case 0: RS_QUAD_OP("v_fmac_f32_dpp", 0, "+v"(acc) : "v"(r[j & 3]), "v"(v)); break;
+    case 1: RS_QUAD_OP("v_fmac_f32_dpp", 1, "+v"(acc) : "v"(r[j & 3]), "v"(v)); break;
+    case 2: RS_QUAD_OP("v_fmac_f32_dpp", 2, "+v"(acc) : "v"(r[j & 3]), "v"(v)); break;
+    default: RS_QUAD_OP("v_fmac_f32_dpp", 3, "+v"(acc) : "v"(r[j & 3]), "v"(v)); break;
+    }
+    return acc;
+}
+// a row as the step takes it: Q floats of the lane's own, or the quad's four registers
+__device__ __forceinline__ float row_mul(const f4 &r, int j, float v) { return quad_mul(r, j, v); }
+__device__ __forceinline__ float row_fma(const f4 &r, int j, float v, float acc) { return quad_fmac(r, j, v, acc); }
+template <int N> __device__ __forceinline__ float row_mul(const float (&r)[N], int j, float v) { return r[j] * v; }
+template <int N> __device__ __forceinline__ float row_fma(const float (&r)[N], int j, float v, float acc) {
+    return fmaf(r[j], v, acc);
+}
+
 // UNIT: every single-out-edge state of T has weight 1 on its edge (TOPO_UNIT, for all of the wave's chains)
 //       With UNI as well, and pass-through states in T, the wave runs the second-order recurrence (HMM_RS_ORDER2).
 // UNI:  all chains of the wave belong to one model (always, unless k > 1 and the wave straddles two): the
@@ -675,6 +727,8 @@ __device__ __forceinline__ void reduce_sparse_wave(const float *__restrict__ A, 
     // states and ONE model per wave, whose incoming weights are folded into the staged emissions
     constexpr bool O2 = HMM_RS_ORDER2 && UNIT && UNI && n_passthrough<T>() > 0;
     static_assert(!O2 || passthrough_between_live<T>(), "a pass-through state between two live states");
+    // QR: a step's emission row in the four lanes of a quad (HMM_RS_QUADROW); GATE: the column sum on demand
+    constexpr bool QR = HMM_RS_QUADROW && O2 && W == 16, GATE = HMM_RS_SUMGATE && O2 && W == 16;
     auto live = [](int j) constexpr { return !O2 || !passthrough<T>(j); };
     const int lane = threadIdx.x & 63, cl = lane / W, kc = lane % W;
     const int t0 = c * p.T;
@@ -775,7 +829,12 @@ __device__ __forceinline__ void reduce_sparse_wave(const float *__restrict__ A, 
     // a pass-through state p, pend[p] is e'_p of the last row taken and its entry is pend[p] * xb[src(p)], formed
     // only at the column's end.  A column that STARTS in pass-through state p is a unit of mass in flight: this
     // lane alone sees pend[p] = 1 in front of its first step, with xb[src(p)] = 1.
+    // QR: the last row taken is the quad's row registers rq[] and there is no pend[] in the loop; a chunk's first
+    // two steps, where one lane's weights differ from its neighbours', take a per-lane copy (tile_steps).
+    // Everything below that works with "the last row" (`pw`: pass-through weights) or "this step's row" (`e`) takes
+    // it in either form, row_mul / row_fma.
     float x[Q], pend[Q], xb[O2 ? Q : 1];
+    f4 rq[2] = {f4{0.f, 0.f, 0.f, 0.f}, f4{0.f, 0.f, 0.f, 0.f}};      // QR: rows of the even / the odd steps
     auto flight_src = [&](int i) {       // O2: this lane's start state is a pass-through state fed by state i
         bool f = false;
 #pragma unroll
@@ -783,13 +842,15 @@ __device__ __forceinline__ void reduce_sparse_wave(const float *__restrict__ A, 
             if (passthrough<T>(pp) && pt_src<T>(pp) == i) f = f || (kc == pp);
         return f;
     };
+    // (QR: the unit column is set up where the chunk's first tile begins, tile_steps_quad: constants here, so that
+    // no per-lane value has to be kept from this point through the prologue and both tile loops)
 #pragma unroll
     for (int j = 0; j < Q; ++j) {
-        x[j] = (j == kc) ? 1.f : 0.f;
+        x[j] = (!QR && j == kc) ? 1.f : 0.f;
         pend[j] = 1.f;
         if constexpr (O2) {
             pend[j] = x[j];
-            xb[j] = flight_src(j) ? 1.f : 0.f;
+            xb[j] = (!QR && flight_src(j)) ? 1.f : 0.f;
         }
     }
     int ex = 0;
@@ -820,35 +881,60 @@ __device__ __forceinline__ void reduce_sparse_wave(const float *__restrict__ A, 
     };
 
     // finalise and store this lane's operator column (called once, at the lane's last step)
-    auto entry = [&](int j) {            // entry j of the column as it stands
-        if constexpr (O2) return live(j) ? x[j] : pend[j] * xb[pt_src<T>(j)];
-        else return deferred(j) ? x[j] * pend[j] : x[j];
+    auto entry = [&](const auto &pw, int j) {            // entry j of the column as it stands
+        if constexpr (O2) {
+            if (live(j)) return x[j];
+            return row_mul(pw, j, xb[pt_src<T>(j)]);
+        } else {
+            return deferred(j) ? x[j] * pw[j] : x[j];
+        }
     };
-    auto column_sum = [&]() {
+    auto column_sum = [&](const auto &pw) {
         float s = 0.f;
         if constexpr (O2) {
 #pragma unroll
             for (int j = 0; j < Q; ++j) if (live(j)) s += x[j];
 #pragma unroll
-            for (int j = 0; j < Q; ++j) if (!live(j)) s = fmaf(pend[j], xb[pt_src<T>(j)], s);
+            for (int j = 0; j < Q; ++j) if (!live(j)) s = row_fma(pw, j, xb[pt_src<T>(j)], s);
         } else {
 #pragma unroll
-            for (int j = 0; j < Q; ++j) s += entry(j);
+            for (int j = 0; j < Q; ++j) s += entry(pw, j);
         }
         return s;
     };
-    auto finish = [&]() {
-        cs = kc < Q ? column_sum() : 0.f;            // (the running sum may be a step old)
-        rescale();
+    auto finish = [&](const auto &pw) {
+        const float fs = column_sum(pw);             // (the running sum may be a step old)
         float *o = ops + (size_t)chain * W * W;
+        bool frisk;
+        int fex;
+        if constexpr (QR) {
+            // rescale()'s arithmetic on a copy: a lane that has stored its column needs none of its state again, and a
+            // wave with a sequence's tail calls this after every step, where each variable written would be one more
+            // value to merge (the kernel is held to 128 registers)
+            const float fcs = kc < Q ? fs : 0.f;
+            frisk = risk || (kc < Q && fcs < 0x1p-100f);
+            const int xe = max(__builtin_amdgcn_frexp_expf(fcs), -100);
+            const float sc = __builtin_amdgcn_ldexpf(1.0f, -xe);
+            fex = ex + xe;
 #pragma unroll
-        for (int j = 0; j < Q; ++j) o[j * W + kc] = (kc < Q) ? entry(j) : 0.f;
+            for (int j = 0; j < Q; ++j) {            // (the pad lane takes part: it is a quad's source lane)
+                const float ent = live(j) ? x[j] * sc : row_mul(pw, j, xb[pt_src<T>(j)] * sc);
+                o[j * W + kc] = (kc < Q) ? ent : 0.f;
+            }
+        } else {
+            cs = kc < Q ? fs : 0.f;
+            rescale();
+            frisk = risk;
+            fex = ex;
+#pragma unroll
+            for (int j = 0; j < Q; ++j) o[j * W + kc] = (kc < Q) ? entry(pw, j) : 0.f;
+        }
 #pragma unroll
         for (int j = Q; j < W; ++j) o[j * W + kc] = 0.f;
         static_assert(Q < W, "the exponent row's last lane is a pad lane");
-        const unsigned long long rb = __builtin_amdgcn_ballot_w64(risk) >> (W == 64 ? 0 : W * cl);
+        const unsigned long long rb = __builtin_amdgcn_ballot_w64(frisk) >> (W == 64 ? 0 : W * cl);
         const bool chain_risk = (W == 64 ? rb : (rb & ((1ull << (W & 63)) - 1ull))) != 0ull;
-        exps[(size_t)chain * W + kc] = (kc < Q) ? ex : ((kc == W - 1 && chain_risk) ? 1 : 0);
+        exps[(size_t)chain * W + kc] = (kc < Q) ? fex : ((kc == W - 1 && chain_risk) ? 1 : 0);
     };
     // one recurrence step on the column: x <- max(E,eps) * (A^T x): exactly linear.  (Rounds 1-2 added
     // eps * sum(x) to every state, a per-column stand-in for the cell's clamp of the state mixture; on the
@@ -869,10 +955,20 @@ __device__ __forceinline__ void reduce_sparse_wave(const float *__restrict__ A, 
     // 15-state model: 7 multiplies + 8 fma's + 7 emission multiplies = 22 per step for 30, and no pass-through
     // value inside the loop.  The true column sum is sum_live x_j(t) + sum_p e'_p(t) x_src(p)(t-1): the same number
     // as before, so threshold, risk mark and the argument above stand; x and xb take the same power of two.
-    auto step = [&](const float (&e)[Q], auto sumc) {
+    //
+    // pw: the last row taken (pend[], or the quad's registers of the step before), e: this step's row in the same form.
+    // GATE.  The sum is formed only to ask whether some column of the wave has fallen below 2^-40, and every entry is
+    // a product of non-negative numbers: each rounded add or fma of the sum returns at least its non-negative addend
+    // (rounding is monotonic and the addend is a float), so the sum as computed is at least the largest live entry.
+    // Where that is 2^-40 or more in every column the test below cannot fire and the sum is not formed; cs then
+    // stays stale, and it is read by rescale() alone, after being set on the slow path or in finish().  Rescale points,
+    // exponents and the risk mark are therefore the ungated ones.  A dead column only costs speed: a lane whose live
+    // entries are all exactly zero sends its wave through the full sum every time (and, as before, never rescales it).
+    auto step = [&](auto &pw, const auto &e, auto sumc) {
         constexpr bool SUM = decltype(sumc)::value;
         float y[Q];
         float s = 0.f;
+        bool need = true;
         if constexpr (O2) {
 #pragma unroll
             for (int j = 0; j < Q; ++j) {
@@ -885,19 +981,29 @@ __device__ __forceinline__ void reduce_sparse_wave(const float *__restrict__ A, 
                     for (int ed = T::start[j]; ed < T::start[j + 1]; ++ed) {
                         const int i = T::src[ed];
                         if (live(i) != (pass == 0)) continue;
-                        const float w = live(i) ? a[ed] : pend[i];
-                        const float v = live(i) ? x[i] : xb[pt_src<T>(i)];
-                        acc = any ? fmaf(w, v, acc) : w * v;
+                        if (live(i)) acc = any ? fmaf(a[ed], x[i], acc) : a[ed] * x[i];
+                        else if (any) acc = row_fma(pw, i, xb[pt_src<T>(i)], acc);
+                        else acc = row_mul(pw, i, xb[pt_src<T>(i)]);
                         any = true;
                     }
                 y[j] = acc;
             }
 #pragma unroll
             for (int j = 0; j < Q; ++j) {
-                if (live(j)) { xb[j] = x[j]; x[j] = y[j] * e[j]; }
-                else pend[j] = e[j];
+                if (live(j)) { xb[j] = x[j]; x[j] = row_mul(e, j, y[j]); }
+                else if constexpr (!std::is_same<typename std::decay<decltype(e)>::type, f4>::value) pw[j] = e[j];
             }
-            if (SUM) s = column_sum();
+            if constexpr (SUM && GATE) {
+                float mx = 0.f;
+                bool anym = false;
+#pragma unroll
+                for (int j = 0; j < Q; ++j)
+                    if (live(j)) { mx = anym ? fmaxf(mx, x[j]) : x[j]; anym = true; }
+                // 0 counts as small; the pad lanes (kc >= Q, all-zero columns) are masked out of the ballot
+                constexpr unsigned long long COLS = ((1ull << (Q & 15)) - 1ull) * 0x0001000100010001ull;   // W == 16
+                need = (__builtin_amdgcn_ballot_w64(!(mx >= 0x1p-40f)) & COLS) != 0ull;
+            }
+            if (SUM && need) s = column_sum(e);
         } else {
 #pragma unroll
             for (int j = 0; j < Q; ++j) {
@@ -905,7 +1011,7 @@ __device__ __forceinline__ void reduce_sparse_wave(const float *__restrict__ A, 
 #pragma unroll
                 for (int ed = T::start[j]; ed < T::start[j + 1]; ++ed) {
                     const int i = T::src[ed];
-                    const float w = deferred(i) ? pend[i] : a[ed];           // weight 1: the pending emission instead
+                    const float w = deferred(i) ? pw[i] : a[ed];             // weight 1: the pending emission instead
                     acc = (ed == T::start[j]) ? w * x[i] : fmaf(w, x[i], acc);
                 }
                 y[j] = acc;
@@ -913,11 +1019,11 @@ __device__ __forceinline__ void reduce_sparse_wave(const float *__restrict__ A, 
 #pragma unroll
             for (int j = 0; j < Q; ++j) {
                 if (SUM) s = fmaf(y[j], e[j], s);
-                if (deferred(j)) { x[j] = y[j]; pend[j] = e[j]; }
+                if (deferred(j)) { x[j] = y[j]; pw[j] = e[j]; }
                 else x[j] = y[j] * e[j];
             }
         }
-        if (SUM) {
+        if (SUM && need) {
             // (32-lane rows — the 29-state model: a column that loses more than 2^-45 between two sums has met an
             // observation that everything survives at the emission floor only; such sequences go to the serial kernels,
             // k_scan_select, on top of the certificates of the 32-state apply kernels)
@@ -991,7 +1097,7 @@ __device__ __forceinline__ void reduce_sparse_wave(const float *__restrict__ A, 
             // (O2: the staged value of a pass-through state carries its incoming weight: the row itself instead)
             float e0 = 1.f;
             if constexpr (O2) { if (first && mine && kc < Q) e0 = fmaxf(E[(chain / p.C) * (long long)p.L * Q + kc], eps); }
-            step(c, std::true_type());
+            step(pend, c, std::true_type());
             if (first) {
                 if constexpr (!O2) e0 = tp[kc < Q ? kc : 0];
 #pragma unroll
@@ -1006,9 +1112,9 @@ __device__ __forceinline__ void reduce_sparse_wave(const float *__restrict__ A, 
                 rescale();
             }
         } else {
-            step(c, std::integral_constant<bool, !HMM_RS_SUM2>());
+            step(pend, c, std::integral_constant<bool, !HMM_RS_SUM2>());
         }
-        if (CHECK) { if (__builtin_amdgcn_ballot_w64(tile * SP_TILE == last) != 0) { if (tile * SP_TILE == last) finish(); } }
+        if (CHECK) { if (__builtin_amdgcn_ballot_w64(tile * SP_TILE == last) != 0) { if (tile * SP_TILE == last) finish(pend); } }
         // steps 1 .. SP_TILE - 1: the odd ones (the tile's last one among them) form the column sum
         auto one = [&](int sidx, auto sumc) {
             if constexpr (AHEAD) {
@@ -1018,10 +1124,10 @@ __device__ __forceinline__ void reduce_sparse_wave(const float *__restrict__ A, 
             } else {
                 ldrow(tp + sidx * W, c);
             }
-            step(c, sumc);
+            step(pend, c, sumc);
             if (CHECK) {
                 const int t = tile * SP_TILE + sidx;
-                if (__builtin_amdgcn_ballot_w64(t == last) != 0) { if (t == last) finish(); }
+                if (__builtin_amdgcn_ballot_w64(t == last) != 0) { if (t == last) finish(pend); }
             }
         };
 #pragma unroll
@@ -1030,20 +1136,92 @@ __device__ __forceinline__ void reduce_sparse_wave(const float *__restrict__ A, 
             if (sidx + 1 < SP_TILE) one(sidx + 1, std::integral_constant<bool, !HMM_RS_SUM2>());
         }
     };
+    // QR: the same tile with the row in the quad.  Step s reads its row into rq[s & 1] and takes the pass-through
+    // weights from rq[(s & 1) ^ 1], the row of the step before; SP_TILE is even, so a tile's last row waits in rq[1]
+    // for the next tile's step 0.  The two sets are written by the LDS reads alone (no copy: see quad_mul).
+    // A chunk's first two steps run in the per-lane form on whole rows: a column that starts on a pass-through state
+    // is a unit of mass in flight that one lane alone sees in front of step 0 (and, on a sequence's first chunk, with
+    // weight e0 in front of step 1), which no staged row can express.  For every other lane the per-lane weights of
+    // step 1 are row 0's values, the numbers the quad would hold.
+    auto tile_steps_quad = [&](auto checked, int tile, int buf) {
+        constexpr bool CHECK = decltype(checked)::value;
+        static_assert(SP_TILE % 2 == 0 && SP_TILE >= 4, "two row sets, rotated by the step pair");
+        const float *tp = &ldsw[buf][cl][0];
+        const float *qp = tp + 4 * (kc & 3);             // (the pad lane: floats 12-15, as lane 11)
+        auto ldquad = [&](int sidx) { return *reinterpret_cast<const f4 *>(qp + sidx * W); };
+        auto done = [&](int sidx, const auto &pw) {
+            if (CHECK) {
+                const int t = tile * SP_TILE + sidx;
+                if (__builtin_amdgcn_ballot_w64(t == last) != 0) { if (t == last) finish(pw); }
+            }
+        };
+        if (tile == 0) {
+            float c[Q], pl[Q];
+#pragma unroll
+            for (int j = 0; j < Q; ++j) {                // the unit column kc, in flight if kc is a pass-through state
+                pl[j] = (j == kc) ? 1.f : 0.f;
+                if (live(j)) { x[j] = pl[j]; xb[j] = flight_src(j) ? 1.f : 0.f; }
+            }
+            ldrow(tp, c);
+            float e0 = 1.f;
+            if (first && mine && kc < Q) e0 = fmaxf(E[(chain / p.C) * (long long)p.L * Q + kc], eps);
+            step(pl, c, std::true_type());
+            if (first) {           // step 0 of a sequence's first chunk has no transition: X = diag(E_0), see tile_steps
+#pragma unroll
+                for (int j = 0; j < Q; ++j) {
+                    x[j] = ((j == kc) ? 1.f : 0.f) * e0;
+                    pl[j] = x[j];
+                    xb[j] = flight_src(j) ? 1.f : 0.f;
+                }
+                cs = (kc < Q) ? e0 : 0.f;
+                ex = 0;
+                rescale();
+            }
+            done(0, pl);
+            ldrow(tp + W, c);
+            step(pl, c, std::true_type());
+            done(1, pl);
+            rq[1] = ldquad(1);
+        } else {
+            rq[0] = ldquad(0);
+            step(rq[1], rq[0], std::integral_constant<bool, !HMM_RS_SUM2>());
+            done(0, rq[0]);
+            rq[1] = ldquad(1);
+            step(rq[0], rq[1], std::true_type());
+            done(1, rq[1]);
+        }
+        // steps 2 .. SP_TILE - 1: the odd ones (the tile's last one among them) form the column sum, or its gate
+#pragma unroll
+        for (int sidx = 2; sidx < SP_TILE; sidx += 2) {
+            rq[0] = ldquad(sidx);
+            step(rq[1], rq[0], std::integral_constant<bool, !HMM_RS_SUM2>());
+            done(sidx, rq[0]);
+            rq[1] = ldquad(sidx + 1);
+            step(rq[0], rq[1], std::true_type());
+            done(sidx + 1, rq[1]);
+        }
+    };
+    auto run_tile = [&](auto checked, int tile) {
+        if constexpr (QR) tile_steps_quad(checked, tile, tile & 1);
+        else tile_steps(checked, tile, tile & 1);
+    };
     fetch(0);
     if (ragged) {
         for (int tile = 0; tile < ntiles; ++tile) {
             stage(tile & 1);
             if (tile + 1 < ntiles) fetch(tile + 1);
-            tile_steps(std::true_type(), tile, tile & 1);
+            run_tile(std::true_type(), tile);
         }
     } else {
         for (int tile = 0; tile < ntiles; ++tile) {
             stage(tile & 1);
             if (tile + 1 < ntiles) fetch(tile + 1);
-            tile_steps(std::false_type(), tile, tile & 1);
+            run_tile(std::false_type(), tile);
         }
-        if (mine) finish();
+        if (mine) {
+            if constexpr (QR) finish(rq[1]);
+            else finish(pend);
+        }
     }
 }
 

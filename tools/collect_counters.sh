@@ -3,6 +3,7 @@
 # `timeout`), for the bench's posterior pipeline, the Viterbi pass (config 4) and the large-q path (config 5 shape).
 # Run on the GPU box from the repo root:
 #   bash tools/collect_counters.sh [tag] ["bench viterbi largeq"]   ->  gpurun_out/counters_<tag>.json
+# PMC_GROUPS="1 2" runs only those counter groups (the SQ ones) of the list below.
 # SQ counters: SQ_WAVE_CYCLES / SQ_WAIT_* / SQ_ACTIVE_INST_* count quad-cycles summed over waves,
 # SQ_VALU_MFMA_BUSY_CYCLES and SQ_BUSY_CYCLES count cycles (MI355X_MICROARCH.md, "rocprofv3 PMC slots").
 set -u
@@ -17,9 +18,12 @@ run_groups() {   # run_groups <name> <python args...>
   while read -r GROUP; do
     [ -z "$GROUP" ] && continue
     i=$((i+1))
+    case " ${PMC_GROUPS:-$i} " in *" $i "*) ;; *) continue ;; esac
     timeout -k 10 200 rocprofv3 --kernel-trace --pmc $GROUP --output-format csv -d "$OUT/${name}_g$i" -- \
         python3 "$@" > "$OUT/${name}_g$i.log" 2>&1
-    echo "$name group $i ($GROUP) rc=$?"
+    local rc=$?
+    echo "$name group $i ($GROUP) rc=$rc"
+    [ $rc -eq 0 ] || { echo "stopping: nothing more runs on the GPU after a failed pass"; exit $rc; }
   done <<'GROUPS'
 SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAVES
 SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS

@@ -1,6 +1,8 @@
 """A/B of compile-time variants of the engine in one process on BASELINE config 3:
    python ab_build.py "" "HMM_RS_WPE=4" "HMM_SUB=16;HMM_RS_WPE=4" ...
-Each argument is a ';'-separated list of -D defines; per-kernel times come from the HIP-event profile."""
+Each argument is a ';'-separated list of -D defines; per-kernel times come from the HIP-event profile.
+AB_LIBDIR=DIR keeps variant i in DIR/libhmm_v<i>.so and builds it only if it is not there yet (build once, run
+several processes; the caller keeps DIR in step with the arguments)."""
 import sys, os, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from hmm_layer_amd import build as hb, engine
@@ -11,8 +13,9 @@ b, L, q = 1024, 100000, 15
 variants = sys.argv[1:] or [""]
 paths = []
 for i, defs in enumerate(variants):
-    path = "/tmp/libhmm_v%d.so" % i
-    hb.build(out=path, defines=[x for x in defs.split(";") if x])
+    path = os.path.join(os.environ.get("AB_LIBDIR", "/tmp"), "libhmm_v%d.so" % i)
+    if not (os.environ.get("AB_LIBDIR") and os.path.exists(path)):
+        hb.build(out=path, defines=[x for x in defs.split(";") if x])
     paths.append(path)
 A, pi = gene15(dev)
 E = torch.rand((1, b, L, q), device=dev) * 0.9 + 0.05
