@@ -112,6 +112,31 @@ def state_posterior_log_probs_sharded(E_slab, cell, group=None, no_loglik=False)
         return seqshard.gather_flagged(A, pi, E, out, loglik, flagged, mode=mode, group=group)
 
 
+def _posterior_probs_host(A, pi, E, eps):
+    """State posteriors (k,b,L,q) fp32 and loglik (k,b) fp64 of tensors that are NOT on a HIP device: the cell's
+    recursion (both clamps at eps, MsaHmmCell.py:87-88) one position at a time in fp64 torch ops.  It exists so that
+    posterior_decode's semantics can be pinned without a GPU; nothing on a HIP device ever comes here."""
+    A, pi, E = A.double(), pi.double(), E.double().clamp_min(eps)
+    k, b, L, q = E.shape
+    alpha = torch.empty_like(E)
+    loglik = torch.zeros((k, b), dtype=torch.float64, device=E.device)
+    x = pi.clamp_min(eps).unsqueeze(1).expand(k, b, q)
+    for t in range(L):
+        x = (x if t == 0 else torch.matmul(x, A).clamp_min(eps)) * E[:, :, t]
+        s = x.sum(-1, keepdim=True)
+        x = x / s
+        alpha[:, :, t] = x
+        loglik += torch.log(s[..., 0])
+    gamma = torch.empty_like(E)
+    r = torch.ones((k, b, q), dtype=torch.float64, device=E.device)
+    for t in range(L - 1, -1, -1):
+        g = alpha[:, :, t] * r
+        gamma[:, :, t] = g / g.sum(-1, keepdim=True)
+        bh = E[:, :, t] * r
+        r = torch.matmul(bh / bh.sum(-1, keepdim=True), A.transpose(1, 2)).clamp_min(eps)
+    return gamma.to(torch.float32), loglik
+
+
 def _wants_grad(inputs, cell):
     if not torch.is_grad_enabled():
         return False
@@ -218,6 +243,23 @@ class MsaHmmLayer(nn.Module):
             return probs, autograd.loglik(A, pi, E, eps=self.cell.epsilon)
         A, pi, E = _engine_inputs(inputs, self.cell, end_hints, training)
         return engine.posterior(A, pi, E, mode=engine.POST_PROB, eps=self.cell.epsilon)
+
+    def posterior_decode(self, inputs, state_class=None, num_classes=None, end_hints=None):
+        """Posterior decoding -> (label (k,b,L) uint8, conf (k,b,L) fp32, loglik (k,b) fp64): per position the class
+        with the largest posterior and that posterior.  state_class maps every state to a class (a sequence or an
+        integer tensor; None: every state its own class); a class posterior is the sum over its states, ties go to
+        the lowest class.  On a HIP device one engine call (engine.posterior_decode: the (k,b,L,q) posterior is never
+        written for models of up to 16 states); elsewhere the same reduction of a step-at-a-time posterior.
+        Inference only."""
+        if _wants_grad(inputs, self.cell):
+            raise ValueError("posterior_decode is inference only (labels carry no gradient): call it under "
+                             "torch.no_grad(), or train through state_posterior_log_probs")
+        A, pi, E = _engine_inputs(inputs, self.cell, end_hints, False)
+        if E.is_cuda:
+            return engine.posterior_decode(A, pi, E, state_class, num_classes, eps=self.cell.epsilon)
+        table, C = engine.class_table(state_class, num_classes, E.shape[-1])
+        gamma, loglik = _posterior_probs_host(A, pi, E, self.cell.epsilon)
+        return (*engine.decode_posterior(gamma, table, C), loglik)
 
     # -- likelihood aggregation -----------------------------------------------------------
     def apply_sequence_weights(self, loglik, indices, aggregate=False):

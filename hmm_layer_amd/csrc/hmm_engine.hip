@@ -1737,6 +1737,66 @@ __device__ __forceinline__ void flush_rows(const OutStage &o, int lane, int row0
     __builtin_amdgcn_wave_barrier();
 }
 
+// ---- decoded output (hmm_posterior_decode): the output policy of backward_body.  NoDecode writes the staged rows
+// themselves (flush_rows); Decode collapses every staged gamma row to (class with the largest posterior, that
+// posterior) and writes 1 + 4 bytes per position instead of 4 q.  The rows are staged exactly as for the full
+// output — the same values in the same LDS segment — and lane i of a flush takes row i % nrows of chain i / nrows:
+// it reads the row's q floats back (rows are q floats apart, so the lanes of an odd q are on distinct banks), sums
+// the states of every class in increasing state index, and stores one byte and one float.  Consecutive lanes hold
+// consecutive positions of a chain, so a store instruction writes runs of nrows label bytes / nrows floats per chain;
+// every lane addresses its own byte, so a chunk that starts at any byte offset and a ragged last group need nothing
+// special.  The class table travels in the kernel arguments as a 0 / 1 weight per (class, state): a class sum is one
+// scalar load of the class's 16 weights and 16 fused multiply-adds with a scalar operand (fma(v, 1, sum) is sum + v
+// rounded once, fma(v, 0, sum) is sum), with no per-state test anywhere — testing a packed table on the scalar unit
+// cost four scalar instructions per (class, state) and more time than the smaller output saved.
+struct NoDecode {
+    static constexpr bool on = false;
+};
+struct alignas(64) Decode {
+    static constexpr bool on = true;
+    float w[QP][QP];             // w[c][s] = 1 where state s belongs to class c, else 0
+    unsigned char *label;        // (k,b,L)
+    float *conf;                 // (k,b,L) or null
+    int ncls;                    // number of classes; 0: the identity map (no sums)
+};
+
+// Decode's flush: the chain table holds ROW offsets from `rowbase` (the wave's first row in the (k,b,L) outputs)
+__device__ __forceinline__ void decode_rows(const OutStage &o, const Decode &d, long long rowbase, int lane, int row0,
+                                            int nrows) {
+    const float inv = 1.0f / (float)nrows;
+    const int *tab = reinterpret_cast<const int *>(o.seg + 16 * OUT_STRIDE);
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll 1                                                       // (one row's values in registers at a time)
+    for (int pc = lane; pc < 16 * nrows; pc += 64) {
+        const int c = (int)(((float)pc + 0.5f) * inv);                 // pc / nrows, exact for these ranges
+        const int r = pc - c * nrows;
+        if (r >= tab[16 + c] - row0) continue;                         // (a chain's ragged end; chains the wave does not own)
+        const float *row = o.seg + c * OUT_STRIDE + r * o.q;
+        float v[QP];
+#pragma unroll
+        for (int s = 0; s < QP; ++s) v[s] = s < o.q ? row[s] : 0.f;
+        float best = v[0];
+        int lab = 0;
+        if (d.ncls == 0) {
+#pragma unroll
+            for (int s = 1; s < QP; ++s)
+                if (v[s] > best) { best = v[s]; lab = s; }            // strict: the lowest index wins a tie
+        } else {
+#pragma unroll 1
+            for (int cl = 0; cl < d.ncls; ++cl) {
+                float sum = 0.f;                                       // states in increasing index
+#pragma unroll
+                for (int s = 0; s < QP; ++s) sum = __builtin_fmaf(v[s], d.w[cl][s], sum);
+                if (cl == 0 || sum > best) { best = sum; lab = cl; }
+            }
+        }
+        const long long at = rowbase + tab[c] + row0 + r;
+        __builtin_nontemporal_store((unsigned char)lab, d.label + at);
+        if (d.conf) __builtin_nontemporal_store(best, d.conf + at);
+    }
+    __builtin_amdgcn_wave_barrier();
+}
+
 __device__ __forceinline__ f4 log4(f4 v) {
     f4 r = {__logf(v.x), __logf(v.y), __logf(v.z), __logf(v.w)};
     return r;
@@ -2085,20 +2145,28 @@ __global__ __launch_bounds__(256) void k_forward(const float *__restrict__ A, co
 // weighed at the chunk's FIRST position with alpha_hat there, one forward step from the chunk scan's prefix vector
 // (prev): psi[chain] = <alpha_hat, Gv> / <alpha_hat, R> there, or the clamp-born share of the backward vector
 // itself where the chunk hands over to the one before, if that is larger (log beta is a statement about that vector).
-template <int MODE, int KIND, bool CERT3 = false, int BS = SUB>
+// DEC: the output policy (MODE 0): NoDecode stores the gamma rows, Decode their class labels (decode_rows); everything
+// up to the staged rows is shared.
+template <int MODE, int KIND, bool CERT3 = false, int BS = SUB, class DEC = NoDecode>
 __device__ __forceinline__ void backward_body(const float *__restrict__ A, const float *__restrict__ E, f4 Rv, double lbb0,
                                               float llf, const float *__restrict__ ck, size_t ckb,
                                               float *__restrict__ out, float *__restrict__ psi, const Tile &tl, int m,
                                               float *seg, const Plan &p, float eps, f4 *Rend = nullptr,
-                                              const float *prev = nullptr, double *lbb_end = nullptr) {
+                                              const float *prev = nullptr, double *lbb_end = nullptr,
+                                              const DEC &dec = DEC()) {
+    static_assert(!DEC::on || MODE == 0, "labels are decoded from the probability output");
+    static_assert(HMM_OUT_ROWS % BS == 0, "a flush group holds whole blocks (HMM_OUT_ROWS / BS divides the block index)");
     const int lane = threadIdx.x & 63, g = lane >> 4, n = lane & 15;
     const int q = p.q;
     float af[4], ab[4];
     load_A(A + (size_t)m * q * q, q, g, n, af, ab);
     const Bounds bd = make_bounds(g, q, eps);
     const int rowb = q * (int)sizeof(float);
-    const OutStage os = make_outstage(seg, reinterpret_cast<char *>(out + (tl.baseE - E)), q, lane,
-                                      tl.voff - g * 16, tl.len);
+    // (Decode: the chain table in rows, not bytes, and the wave's first row in place of a base pointer)
+    const OutStage os = DEC::on ? make_outstage(seg, nullptr, q, lane, (tl.voff - g * 16) / rowb, tl.len)
+                                : make_outstage(seg, reinterpret_cast<char *>(out + (tl.baseE - E)), q, lane,
+                                                tl.voff - g * 16, tl.len);
+    const long long rowbase = DEC::on ? (long long)(tl.baseE - E) / q : 0;
     constexpr bool PSI = HMM_PSI && KIND == KIND_SCAN && MODE != 3;
 
     double lbb = lbb0;                                                // log scale of beta after the current block
@@ -2188,7 +2256,9 @@ __device__ __forceinline__ void backward_body(const float *__restrict__ A, const
         if (MODE == 3) lbb += (double)lacc;
         if (j % (HMM_OUT_ROWS / BS) == 0) {                 // the group's earliest block is done: rows j*BS .. (top group: fewer)
             const int top = p.nsub - j;
-            flush_rows(os, lane, j * BS, (top < (HMM_OUT_ROWS / BS) ? top : (HMM_OUT_ROWS / BS)) * BS);
+            const int nrows = (top < (HMM_OUT_ROWS / BS) ? top : (HMM_OUT_ROWS / BS)) * BS;
+            if constexpr (DEC::on) decode_rows(os, dec, rowbase, lane, j * BS, nrows);
+            else flush_rows(os, lane, j * BS, nrows);
         }
     };
 
@@ -2274,6 +2344,30 @@ __global__ __launch_bounds__(256) void k_backward(const float *__restrict__ A, c
     backward_body<MODE, EXACT ? KIND_EXACT : KIND_SCAN, CERT3, BS>(A, E, R0, lbb0, llf, ck, ckpt_block(p), out, psi, tl, m, seg,
                                                                p, eps, &re, CERT3 ? prefix + (size_t)tl.chain * QP : nullptr);
     if (!EXACT && rstart && tl.valid) *reinterpret_cast<f4 *>(rstart + (size_t)tl.chain * QP + 4 * g) = re;
+}
+
+// k_backward<0, false, false, BS> with the Decode output policy (hmm_posterior_decode)
+// (two blocks per compute unit, as k_backward<0> reaches on its own: at 16 steps per block the kernel sits at the edge
+// of the 256 registers that allows, and the decode flush must not tip it over)
+template <int BS>
+__global__ __launch_bounds__(256, 2) void k_backward_decode(const float *__restrict__ A, const float *__restrict__ E,
+                                                         const float *__restrict__ ckpt, const float *__restrict__ suffix,
+                                                         float *__restrict__ psi, float *__restrict__ rstart, Routing rt,
+                                                         Plan p, float eps, long long nwaves, const Decode dec) {
+    const long long wave = (long long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (wave >= nwaves) return;
+    const int lane = threadIdx.x & 63, g = lane >> 4, n = lane & 15;
+    int m; long long wc0;
+    Tile tl = make_tile(E, p, wave, g, n, &m, &wc0);
+    if (!route_tile<false>(tl, m, g, rt, eps)) return;
+    __shared__ __attribute__((aligned(16))) float ostage[4 * OUT_SEG];
+    float *seg = ostage + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * OUT_SEG;
+    const f4 R0 = *reinterpret_cast<const f4 *>(suffix + (size_t)tl.chain * QP + 4 * g);
+    const float *ck = ckpt + ckpt_origin(tl, p, g, n);
+    f4 re;
+    backward_body<0, KIND_SCAN, false, BS, Decode>(A, E, R0, 0.0, 0.f, ck, ckpt_block(p), nullptr, psi, tl, m, seg, p, eps,
+                                                   &re, nullptr, nullptr, dec);
+    if (rstart && tl.valid) *reinterpret_cast<f4 *>(rstart + (size_t)tl.chain * QP + 4 * g) = re;
 }
 
 // ---- the per-sequence verdict, one wave per sequence.
@@ -2588,16 +2682,21 @@ __device__ __forceinline__ void window_walk(Pol &pol, const float *__restrict__ 
 
 // MODE 0..2: the posterior's output modes; MODE 4: the log-likelihood alone (hmm_forward without log alpha)
 // MODE 5: log alpha (hmm_forward): forward half only, writing log alpha of every position walked
-template <int MODE>
+template <int MODE, class DEC = NoDecode>
 struct PostWindows {
     static constexpr bool BACKWARD = MODE < 4, CKPT = MODE < 4, LOGA = MODE == 5;
     float *out;
     float llf;
+    const DEC *dec = nullptr;   // Decode: the kernel's own argument (the weights stay in the argument segment)
     __device__ __forceinline__ float *loga() const { return LOGA ? out : nullptr; }
     __device__ __forceinline__ void begin(int, int, float ll_scan) { llf = ll_scan; }
     __device__ __forceinline__ void backward(const float *A, const float *E, const Tile &tl, int m, f4 R, const float *ck,
                                              const Plan &pw, float eps, float *seg, f4 *re) {
-        backward_body<MODE >= 4 ? 0 : MODE, KIND_WIN>(A, E, R, 0.0, llf, ck, (size_t)QP, out, nullptr, tl, m, seg, pw, eps, re);
+        if constexpr (DEC::on)
+            backward_body<0, KIND_WIN, false, SUB, DEC>(A, E, R, 0.0, llf, ck, (size_t)QP, out, nullptr, tl, m, seg, pw, eps,
+                                                        re, nullptr, nullptr, *dec);
+        else
+            backward_body<MODE >= 4 ? 0 : MODE, KIND_WIN>(A, E, R, 0.0, llf, ck, (size_t)QP, out, nullptr, tl, m, seg, pw, eps, re);
     }
     __device__ __forceinline__ void finish(int, int, bool) {}
 };
@@ -2619,6 +2718,24 @@ __global__ __launch_bounds__(256) void k_window_posterior(const float *__restric
     pol.out = out;
     window_walk(pol, A, E, prefix, llpre, suffix, xend, rstart, ckpt, loglik, wtab, wlist, wcnt, flags, dfix, p, eps, ext0, seg,
                 wshift);
+}
+
+// k_window_posterior<0> with the Decode output policy (hmm_posterior_decode)
+__global__ __launch_bounds__(256) void k_window_decode(const float *__restrict__ A, const float *__restrict__ E,
+                                                       const float *__restrict__ prefix, const double *__restrict__ llpre,
+                                                       const float *__restrict__ suffix, const float *__restrict__ xend,
+                                                       const float *__restrict__ rstart, float *__restrict__ ckpt,
+                                                       double *__restrict__ loglik, int *__restrict__ wtab,
+                                                       const int *__restrict__ wlist, int *__restrict__ wcnt,
+                                                       int *__restrict__ flags, double *__restrict__ dfix, Plan p, float eps,
+                                                       int ext0, const Decode dec) {
+    __shared__ __attribute__((aligned(16))) float ostage[4 * OUT_SEG];
+    float *seg = ostage + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * OUT_SEG;
+    PostWindows<0, Decode> pol;
+    pol.out = nullptr;
+    pol.dec = &dec;
+    window_walk(pol, A, E, prefix, llpre, suffix, xend, rstart, ckpt, loglik, wtab, wlist, wcnt, flags, dfix, p, eps, ext0, seg,
+                nullptr);
 }
 
 // log beta (hmm_backward) of the sequences k_exact_select gave windows: the backward half alone.  What is born in a
@@ -2854,6 +2971,28 @@ __global__ __launch_bounds__(256) void k_exact_posterior(const float *__restrict
     if (tl.valid && g == 0) loglik[tl.chain] = ll;
     __threadfence();
     backward_body<MODE, KIND_EXACT>(A, E, ones4(p.q, g), 0.0, (float)ll, ck, ckpt_block(p), out, nullptr, tl, m, seg, p, eps);
+}
+
+// k_exact_posterior<0> with the Decode output policy (hmm_posterior_decode)
+__global__ __launch_bounds__(256) void k_exact_decode(const float *__restrict__ A, const float *__restrict__ pi,
+                                                      const float *__restrict__ E, float *__restrict__ ckpt,
+                                                      double *__restrict__ loglik, Routing rt, Plan p, float eps,
+                                                      long long nwaves, const Decode dec) {
+    const long long wave = (long long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (wave >= nwaves) return;
+    const int lane = threadIdx.x & 63, g = lane >> 4, n = lane & 15;
+    int m; long long wc0;
+    Tile tl = make_tile(E, p, wave, g, n, &m, &wc0);
+    if (!route_tile<true>(tl, m, g, rt, eps)) return;
+    __shared__ __attribute__((aligned(16))) float ostage[4 * OUT_SEG];
+    float *seg = ostage + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * OUT_SEG;
+    float *ck = ckpt + ckpt_origin(tl, p, g, n);
+    const double ll = forward_body<true, false, KIND_EXACT>(A, E, ld_state4(pi + (size_t)m * p.q, p.q, g), 0.0, ck,
+                                                            ckpt_block(p), nullptr, tl, m, seg, p, eps);
+    if (tl.valid && g == 0) loglik[tl.chain] = ll;
+    __threadfence();
+    backward_body<0, KIND_EXACT, false, SUB, Decode>(A, E, ones4(p.q, g), 0.0, 0.f, ck, ckpt_block(p), nullptr, nullptr, tl, m,
+                                                     seg, p, eps, nullptr, nullptr, nullptr, dec);
 }
 
 // ------------------------------------------------------------------ small kernels
@@ -3120,6 +3259,29 @@ static int posterior_impl(const float *A, const float *pi, const float *E, int k
 int hmm_posterior(const float *A, const float *pi, const float *E, int k, int b, int L, int q, float eps,
                   int mode, float *out, double *loglik, void *workspace, size_t workspace_bytes, void *stream) {
     return posterior_impl(A, pi, E, k, b, L, q, eps, mode, out, loglik, workspace, workspace_bytes, stream, nullptr);
+}
+
+int hmm_posterior_decode_max_states(void) { return QP; }
+
+int hmm_posterior_decode(const float *A, const float *pi, const float *E, int k, int b, int L, int q, float eps,
+                         const int *state_class, int num_classes, unsigned char *label, float *conf, double *loglik,
+                         void *workspace, size_t workspace_bytes, void *stream) {
+    if (k < 1 || b < 1 || L < 1 || q < 1) return HMM_ERR_BAD_SHAPE;
+    if (q > QP) return HMM_ERR_Q_UNSUPPORTED;
+    Route r;
+    int rc = make_route(HMM_OP_POSTERIOR, k, b, L, q, &r);
+    if (rc) return rc;
+    if (!A || !pi || !E || !label || !workspace) return HMM_ERR_NULL_POINTER;
+    if (num_classes < 1 || num_classes > QP || (!state_class && num_classes != q)) return HMM_ERR_BAD_ARGUMENT;
+    Decode dec{};
+    dec.label = label; dec.conf = conf; dec.ncls = state_class ? num_classes : 0;
+    for (int s = 0; s < q && state_class; ++s) {               // the table is read here, once, and travels by value
+        if (state_class[s] < 0 || state_class[s] >= num_classes) return HMM_ERR_BAD_ARGUMENT;
+        dec.w[state_class[s]][s] = 1.f;
+    }
+    if ((rc = check_ws(r.total, workspace, workspace_bytes))) return rc;
+    return s16_posterior(A, pi, E, r.G, eps, HMM_POST_PROB, nullptr, loglik, (char *)workspace, (hipStream_t)stream,
+                         nullptr, &dec);
 }
 
 // one device counter -> the host, added to *sum

@@ -265,8 +265,11 @@ static int s16_backward(const float *A, const float *E, const Plan &p, float eps
 
 // The apply stage of the posterior, after run_reduce_scan on the same plan: forward (checkpoints), backward (out), then
 // the serial kernels for what is routed (allow_exact; not for a time slab of a sequence-sharded call).
+// dec (hmm_posterior_decode; mode HMM_POST_PROB, no `out`): the same launches with the backward, window and
+// whole-sequence kernels in their Decode form.
 static int s16_apply(const float *A, const float *pi, const float *E, const Plan &p, float eps, int mode, char *ws,
-                     float *out, double *loglik, hipStream_t st, Profile *pr, bool allow_exact = true) {
+                     float *out, double *loglik, hipStream_t st, Profile *pr, bool allow_exact = true,
+                     const Decode *dec = nullptr) {
     Plan px;
     int rc = make_xplan(p, &px);
     if (rc) return rc;
@@ -290,10 +293,21 @@ static int s16_apply(const float *A, const float *pi, const float *E, const Plan
         auto *kern = wide ? k_backward<0, false, false, HMM_POST_BLOCK>
                      : mode == HMM_POST_PROB ? k_backward<0, false>
                      : mode == HMM_POST_LOG ? k_backward<1, false> : k_backward<2, false>;
-        launch(kern, apply_grid(p), dim3(256), 0, st, A, E, w.ckpt, w.suffix, w.lsuf, w.loglik, out, w.phi, w.rstart, rt,
-               pb, eps, nw, nullptr);
+        if (dec)
+            launch(wide ? k_backward_decode<HMM_POST_BLOCK> : k_backward_decode<SUB>, apply_grid(p), dim3(256), 0, st, A, E,
+                   w.ckpt, w.suffix, w.phi, w.rstart, rt, pb, eps, nw, *dec);
+        else
+            launch(kern, apply_grid(p), dim3(256), 0, st, A, E, w.ckpt, w.suffix, w.lsuf, w.loglik, out, w.phi, w.rstart,
+                   rt, pb, eps, nw, nullptr);
     }
-    if (allow_exact) {
+    if (allow_exact && dec) {
+        Timed t(pr, HMM_KERNEL_EXACT, st);
+        s16_select(p, w, rt, st);
+        launch(k_window_decode, win_grid(p), dim3(256), 0, st, A, E, w.prefix, w.llpre, w.suffix, w.xend, w.rstart, w.ckpt,
+               w.loglik, w.wtab, w.wlist, w.wcnt, w.flags, w.dfix, p, eps, win_margin(p), *dec);
+        launch(k_exact_decode, apply_grid(px), dim3(256), 0, st, A, pi, E, w.ckpt, w.loglik, routing_flagged(rt, w), px, eps,
+               apply_waves(px), *dec);
+    } else if (allow_exact) {
         // the serial kernels: per model as k_topo_check decided, per sequence from the clamp-born mass the
         // backward kernel just summed; their waves exit at once when nothing is routed
         Timed t(pr, HMM_KERNEL_EXACT, st);
@@ -315,7 +329,8 @@ static int s16_apply(const float *A, const float *pi, const float *E, const Plan
 
 // The posterior of every batch group: reduce + scan, then the apply stage.
 static int s16_posterior(const float *A, const float *pi, const float *E, const Groups &G, float eps, int mode,
-                         float *out, double *loglik, char *ws, hipStream_t st, Profile *pr) {
+                         float *out, double *loglik, char *ws, hipStream_t st, Profile *pr,
+                         const Decode *dec = nullptr) {
     int rc = HMM_OK;
 #ifdef HMM_GROUPS_SERIAL
     hipStream_t *hs = nullptr;
@@ -332,9 +347,14 @@ static int s16_posterior(const float *A, const float *pi, const float *E, const 
             (void)hipEventRecord(*reduced, s0);
             if (rc == HMM_OK) (void)hipStreamWaitEvent(s1, *reduced, 0);
         }
+        Decode dg = dec ? *dec : Decode();                   // this group's rows of the decoded outputs
+        if (dec) {
+            dg.label += (size_t)G.b0[g] * p.L;
+            if (dg.conf) dg.conf += (size_t)G.b0[g] * p.L;
+        }
         if (rc == HMM_OK)
-            rc = s16_apply(A, pi, E + row, p, eps, mode, ws + G.off[g], out + row, loglik ? loglik + G.b0[g] : nullptr,
-                           s1, pr);
+            rc = s16_apply(A, pi, E + row, p, eps, mode, ws + G.off[g], dec ? nullptr : out + row,
+                           loglik ? loglik + G.b0[g] : nullptr, s1, pr, true, dec ? &dg : nullptr);
     };
     if (!hs) {
         // single group (or no helper streams available): everything in order on the caller's stream

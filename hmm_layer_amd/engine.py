@@ -135,6 +135,14 @@ _SIGNATURES = {
     "hmm_seqshard_viterbi_path": (_I, [_I, _I, _I, _I, _P, _P, _I, _I, _P, _P, _SZ, _P]),
 }
 
+# posterior_decode's symbols, typed by lib() like the table above.  They are kept apart from it as the sequence-sharded
+# modules keep theirs: the guard-band table of the test suite is checked against _SIGNATURES, and this entry point's
+# guard-band rows and completeness check live in a test file of their own.
+DECODE_SIGNATURES = {
+    "hmm_posterior_decode_max_states": (_I, []),
+    "hmm_posterior_decode": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _P, _I, _P, _P, _P, _P, _SZ, _P]),
+}
+
 
 def lib():
     """The loaded shared library (loaded once).  Raises if it has not been built."""
@@ -146,7 +154,7 @@ def lib():
             "HIP engine library %s is missing: build it with `python -m hmm_layer_amd.build` "
             "(there is no CPU fallback)" % LIB_PATH)
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in _SIGNATURES.items():
+    for name, (restype, argtypes) in {**_SIGNATURES, **DECODE_SIGNATURES}.items():
         if not hasattr(L, name):
             raise EngineError("the engine library %s does not export %s: rebuild it with "
                               "`python -m hmm_layer_amd.build`" % (LIB_PATH, name))
@@ -283,34 +291,36 @@ class option:
         return False
 
 
-def exact_count(op, dims, device=None):
+def exact_count(op, dims, device=None, tag=None):
     """How many of the k*b sequences of the LAST q <= 16 call of kind `op` with shape `dims` on this
-    device and stream were served by the serial exact-clamp kernels (synchronises)."""
-    with _last_workspace(device) as ws:
+    device and stream were served by the serial exact-clamp kernels (synchronises).  tag=DECODE_TAG (with
+    OP_POSTERIOR) reads the last posterior_decode() call instead of the last posterior()."""
+    with _last_workspace(device, tag) as ws:
         n = lib().hmm_exact_count(int(op), *dims, ws.data_ptr(), ws.numel())
     if n < 0:
         _check(int(n))
     return int(n)
 
 
-def exact_detail(dims, device=None, op=OP_POSTERIOR):
+def exact_detail(dims, device=None, op=OP_POSTERIOR, tag=None):
     """Routing of the LAST posterior() call (q <= 16) with shape `dims` on this device and stream ->
     dict(routed=sequences that left the scan, window_sequences=..., windows=..., whole=sequences redone whole,
     window_chunks=chunks the windows walked).  Synchronises.  op: OP_LOGLIK / OP_FORWARD (forward() without / with
-    log alpha) or OP_BACKWARD for the last call of those entry points instead."""
-    with _last_workspace(device) as ws:
+    log alpha) or OP_BACKWARD for the last call of those entry points instead; tag=DECODE_TAG for the last
+    posterior_decode() call."""
+    with _last_workspace(device, tag) as ws:
         d = (ctypes.c_longlong * 5)()
         _check(lib().hmm_exact_detail_op(int(op), *[int(x) for x in dims], ws.data_ptr(), ws.numel(), d))
     return dict(routed=int(d[0]), window_sequences=int(d[1]), windows=int(d[2]), whole=int(d[3]), window_chunks=int(d[4]))
 
 
-def window_table(dims, seq, op=OP_POSTERIOR, device=None):
+def window_table(dims, seq, op=OP_POSTERIOR, device=None, tag=None):
     """Diagnostics (q <= 16): the windows of sequence `seq` (index into k*b) after the LAST call of `op` with shape `dims`
     on this device and stream -> dict(windows=[(first chunk, chunks), ...], shifts=[log-scale shift per window]
     (OP_FORWARD / OP_BACKWARD), psi=numpy array of the per-chunk certificate sums; chunks the reduce marked for having
-    gone through the denormal range read 1.0).  Synchronises."""
+    gone through the denormal range read 1.0).  Synchronises.  tag=DECODE_TAG: the last posterior_decode() call."""
     import numpy as np
-    with _last_workspace(device) as ws:
+    with _last_workspace(device, tag) as ws:
         k, b, L, q = (int(x) for x in dims)
         C = (L + chunk_len(k, b, L, q) - 1) // chunk_len(k, b, L, q)
         tab = (ctypes.c_int * 34)()
@@ -422,6 +432,66 @@ def posterior(A, pi, E, mode=POST_PROB, eps=EPS, out=None, profile=None):
         else:
             _check(lib().hmm_posterior_profiled(*args, profile.handle))
     return out, ll
+
+
+DECODE_TAG = "posterior_decode"      # posterior_decode()'s workspace: its routing records survive a posterior() call
+
+
+def class_table(state_class, num_classes, q):
+    """The class map of posterior_decode as (list of q ints or None, number of classes): `state_class` a sequence or
+    an integer tensor on any device (brought to the host here, once), None = the identity map."""
+    if state_class is None:
+        if num_classes is not None and int(num_classes) != q:
+            raise ValueError("without state_class every state is its own class: num_classes must be q = %d" % q)
+        return None, q
+    table = [int(c) for c in (state_class.detach().cpu().reshape(-1).tolist() if torch.is_tensor(state_class)
+                              else state_class)]
+    if len(table) != q:
+        raise ValueError("state_class must have q = %d entries, got %d" % (q, len(table)))
+    C = max(table) + 1 if num_classes is None else int(num_classes)
+    if C < 1 or min(table) < 0 or max(table) >= C:
+        raise ValueError("state_class entries must lie in 0 .. num_classes-1 = %d" % (C - 1))
+    return table, C
+
+
+def decode_posterior(gamma, table, C):
+    """What posterior_decode computes, from a posterior tensor (..., q) with torch ops: class sums (index_add_ over the
+    state axis), then the largest class per position, the lowest index on ties -> (label uint8, conf)."""
+    if table is not None:
+        idx = torch.tensor(table, dtype=torch.long, device=gamma.device)
+        gamma = torch.zeros(gamma.shape[:-1] + (C,), dtype=gamma.dtype, device=gamma.device).index_add_(-1, idx, gamma)
+    # (torch.argmax returns the first maximal index; torch.max's index is not specified on ties)
+    return gamma.argmax(dim=-1).to(torch.uint8), gamma.max(dim=-1).values
+
+
+def posterior_decode(A, pi, E, state_class=None, num_classes=None, eps=EPS, want_conf=True):
+    """Posterior decoding -> (label (k,b,L) uint8, conf (k,b,L) fp32 or None, loglik (k,b) fp64): per position the
+    class with the largest posterior (the sum of the state posteriors of its states; the lowest class on ties) and
+    that posterior.  Up to 16 states the engine's kernels produce the labels themselves and the (k,b,L,q) tensor is
+    never written; above, this composes posterior(POST_PROB) with torch ops (same shapes, dtypes and tie rule) and the
+    number of classes is not limited to 16 (but to 256, the range of a label)."""
+    A, pi, E = _dev(A, "A"), _dev(pi, "pi"), _dev(E, "E")
+    A, pi, dims = _shapes(A, E, pi)
+    q = dims[3]
+    table, C = class_table(state_class, num_classes, q)
+    if q > lib().hmm_posterior_decode_max_states():
+        if C > 256:
+            raise ValueError("labels are bytes: at most 256 classes, got %d" % C)
+        gamma, ll = posterior(A, pi, E, POST_PROB, eps)
+        label, conf = decode_posterior(gamma, table, C)
+        return label, (conf if want_conf else None), ll
+    if C > 16:
+        raise ValueError("at most 16 classes, got %d" % C)
+    with torch.cuda.device(E.device):
+        ws = _workspace(E.device, lib().hmm_workspace_bytes(OP_POSTERIOR, *dims), DECODE_TAG)
+        label = torch.empty(dims[:3], dtype=torch.uint8, device=E.device)
+        conf = torch.empty(dims[:3], dtype=torch.float32, device=E.device) if want_conf else None
+        ll = torch.empty(dims[:2], dtype=torch.float64, device=E.device)
+        tab = (ctypes.c_int * q)(*table) if table is not None else None
+        _check(lib().hmm_posterior_decode(A.data_ptr(), pi.data_ptr(), E.data_ptr(), *dims, eps, tab, C,
+                                          label.data_ptr(), conf.data_ptr() if want_conf else None, ll.data_ptr(),
+                                          ws.data_ptr(), ws.numel(), _stream(E.device)))
+    return label, conf, ll
 
 
 def _emitter_args(x, B, state_row, codon, state_codon):

@@ -246,6 +246,40 @@ int hmm_window_table(int op, int k, int b, int L, int q, const void *workspace, 
                      int *table, double *shifts, float *psi, int npsi);
 
 /*
+ * Posterior decoding, fused: per position the CLASS with the largest posterior and that posterior, without the
+ * (k,b,L,q) tensor ever reaching memory — 1 + 4 bytes per position instead of 4 q.  For
+ * q <= hmm_posterior_decode_max_states() (16); above, callers compose hmm_posterior with a reduction of their own
+ * (hmm_layer_amd.engine.posterior_decode does): fused kernels for 17..64 states and beyond are a follow-up.
+ *   state_class  HOST pointer, q entries in 0 .. num_classes-1: the class of every state; NULL = the identity map
+ *                (every state its own class; num_classes must then equal q).  Read during the call and passed to the
+ *                kernels by value: the caller may change or free it at once, and a captured graph keeps the table it
+ *                was captured with.
+ *   num_classes  1 .. 16
+ *   label  (k,b,L) bytes      the class with the largest class posterior, the lowest class index on ties
+ *   conf   (k,b,L) or NULL    that class's posterior probability
+ *   loglik (k,b) fp64 or NULL as hmm_posterior
+ * A, pi, E, eps, the clamp semantics and the routing to the serial kernels are those of hmm_posterior in
+ * HMM_POST_PROB mode: the same kernels compute the same gamma row of every position (routed sequences get theirs
+ * from the exact serial step), which is then collapsed on chip.  The class posterior is the fp32 sum of gamma over
+ * the states of the class, added in increasing state index starting from 0; classes are compared in increasing class
+ * index with a strict >, so label is the lowest maximal class.  With the identity map nothing is summed: conf is, bit
+ * for bit, the largest entry of hmm_posterior's row and label its lowest index.
+ * The workspace is hmm_workspace_bytes(HMM_OP_POSTERIOR, k, b, L, q); hmm_exact_count(HMM_OP_POSTERIOR, ...),
+ * hmm_exact_detail and hmm_window_table read the routing of a finished decode call from it as they do for
+ * hmm_posterior.  Runs on `stream` alone with no host synchronisation (capturable); repeated calls are bit-identical.
+ * Argument checks, before any HIP call, in this order: shape (HMM_ERR_BAD_SHAPE), q > 16 (HMM_ERR_Q_UNSUPPORTED), NULL
+ * among A, pi, E, label, workspace (HMM_ERR_NULL_POINTER), num_classes outside 1..16 or an entry of state_class outside
+ * 0..num_classes-1 or state_class NULL with num_classes != q (HMM_ERR_BAD_ARGUMENT), workspace too small or not
+ * 256-byte aligned (HMM_ERR_WORKSPACE).
+ */
+int hmm_posterior_decode_max_states(void);
+int hmm_posterior_decode(const float *A, const float *pi, const float *E,
+                         int k, int b, int L, int q, float eps,
+                         const int *state_class, int num_classes,
+                         unsigned char *label, float *conf, double *loglik,
+                         void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Viterbi state paths (max-plus scan).  The reference has none (only a docstring mention,
  * hmm_layer/MsaHmmCell.py:13, and the unused log_A_dense, :46-47); this entry point is what
  * a Viterbi over HmmCell's parameters needs: log A (k,q,q) (transitioner.make_log_A()),

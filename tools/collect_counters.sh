@@ -1,6 +1,7 @@
 #!/bin/bash
 # Per-kernel PMC counters, one rocprofv3 --pmc pass per counter group (kernel-trace only, each pass bounded by
-# `timeout`), for the bench's posterior pipeline, the Viterbi pass (config 4) and the large-q path (config 5 shape).
+# `timeout`), for the bench's posterior pipeline, the Viterbi pass (config 4), the large-q path (config 5 shape) and
+# ("decode") hmm_posterior next to hmm_posterior_decode at the headline shape.
 # Run on the GPU box from the repo root:
 #   bash tools/collect_counters.sh [tag] ["bench viterbi largeq"]   ->  gpurun_out/counters_<tag>.json
 # PMC_GROUPS="1 2" runs only those counter groups (the SQ ones) of the list below.
@@ -40,6 +41,7 @@ for W in $WHAT; do
     bench) run_groups bench "$R/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --no-variants --no-accuracy ;;
     viterbi) run_groups viterbi "$R/tools/experiments/vit_prof.py" ;;
     largeq) run_groups largeq "$R/tools/experiments/largeq_time.py" ;;
+    decode) run_groups decode "$R/tools/experiments/posterior_decode_time.py" --calls g15-1024-100000-uniform ;;
   esac
 done
 python3 "$R/tools/pmc_aggregate.py" "$OUT" "$R/gpurun_out/counters_$TAG.json"
