@@ -249,8 +249,9 @@ class MsaHmmLayer(nn.Module):
         with the largest posterior and that posterior.  state_class maps every state to a class (a sequence or an
         integer tensor; None: every state its own class); a class posterior is the sum over its states, ties go to
         the lowest class.  On a HIP device one engine call (engine.posterior_decode: the (k,b,L,q) posterior is never
-        written for models of up to 16 states); elsewhere the same reduction of a step-at-a-time posterior.
-        Inference only."""
+        written for models of up to 64 states with the identity map or at most 16 classes — the multi-copy gene
+        models of 29 / 43 / 57 states included —; other models compose the posterior with torch ops); elsewhere the
+        same reduction of a step-at-a-time posterior.  Inference only."""
         if _wants_grad(inputs, self.cell):
             raise ValueError("posterior_decode is inference only (labels carry no gradient): call it under "
                              "torch.no_grad(), or train through state_posterior_log_probs")

@@ -3234,7 +3234,7 @@ static int posterior_impl(const float *A, const float *pi, const float *E, int k
             // the chunked scan for the models it serves, the serial kernels for the rest and for the sequences the
             // certificate flags (all decided on the device)
             (r.path == PATH_MID32 ? scan_posterior<Scan32> : scan_posterior<Scan64>)(A, pi, E, r.mp, eps, mode, out, wm,
-                                                                                     st);
+                                                                                     st, nullptr);
             ll = WsMid(r.mp, wm).loglik;
             need = WsMid(r.mp, wm).need;
             [[fallthrough]];
@@ -3282,6 +3282,52 @@ int hmm_posterior_decode(const float *A, const float *pi, const float *E, int k,
     if ((rc = check_ws(r.total, workspace, workspace_bytes))) return rc;
     return s16_posterior(A, pi, E, r.G, eps, HMM_POST_PROB, nullptr, loglik, (char *)workspace, (hipStream_t)stream,
                          nullptr, &dec);
+}
+
+int hmm_posterior_decode_mid_max_states(void) { return MQ_MAX; }
+
+// hmm_posterior's workspace, then the parking region of the serial walk: k b L q floats, addressed like `out`
+static size_t decode_mid_park(const Route &r) { return align_up(r.total); }
+
+size_t hmm_posterior_decode_mid_workspace_bytes(int k, int b, int L, int q) {
+    Route r;
+    if (q <= QP || q > MQ_MAX || make_route(HMM_OP_POSTERIOR, k, b, L, q, &r)) return 0;
+    return decode_mid_park(r) + (size_t)k * b * L * q * sizeof(float);
+}
+
+int hmm_posterior_decode_mid(const float *A, const float *pi, const float *E, int k, int b, int L, int q, float eps,
+                             const int *state_class, int num_classes, unsigned char *label, float *conf,
+                             double *loglik, void *workspace, size_t workspace_bytes, void *stream) {
+    if (k < 1 || b < 1 || L < 1 || q < 1) return HMM_ERR_BAD_SHAPE;
+    if (q <= QP || q > MQ_MAX) return HMM_ERR_Q_UNSUPPORTED;
+    Route r;
+    int rc = make_route(HMM_OP_POSTERIOR, k, b, L, q, &r);
+    if (rc) return rc;
+    if (!A || !pi || !E || !label || !workspace) return HMM_ERR_NULL_POINTER;
+    if (num_classes < 1 || (state_class ? num_classes > QP : num_classes != q)) return HMM_ERR_BAD_ARGUMENT;
+    DecodeMid dec{};
+    dec.label = label; dec.conf = conf; dec.ncls = state_class ? num_classes : 0;
+    for (int s = 0; s < q && state_class; ++s) {               // the table is read here, once, and travels by value
+        if (state_class[s] < 0 || state_class[s] >= num_classes) return HMM_ERR_BAD_ARGUMENT;
+        dec.mask[state_class[s]] |= 1ull << s;
+    }
+    const size_t o_park = decode_mid_park(r);
+    if ((rc = check_ws(o_park + (size_t)k * b * L * q * sizeof(float), workspace, workspace_bytes))) return rc;
+    char *ws = (char *)workspace;
+    hipStream_t st = (hipStream_t)stream;
+    char *wm = ws + r.lp.total;                              // MID*: the chunked scan's region
+    double *ll = ws_at<double>(ws, r.lp.o_ll);
+    const int *need = nullptr;
+    if (r.path != PATH_MQ) {
+        (r.path == PATH_MID32 ? scan_posterior<Scan32> : scan_posterior<Scan64>)(A, pi, E, r.mp, eps, HMM_POST_PROB,
+                                                                                 nullptr, wm, st, &dec);
+        ll = WsMid(r.mp, wm).loglik;
+        need = WsMid(r.mp, wm).need;
+    }
+    mq_posterior2_decode(A, pi, E, k, b, L, q, eps, ws_at<float>(ws, o_park), ll, dec, st, need,
+                         ws_at<MqSp>(ws, r.lp.o_sp));
+    if (loglik) launch(k_copy_loglik, dim3((r.lp.NB + 255) / 256), dim3(256), 0, st, ll, loglik, r.lp.NB);
+    return check_launch();
 }
 
 // one device counter -> the host, added to *sum

@@ -38,6 +38,79 @@ template <int D> __device__ __forceinline__ float mq_sum(float v) { return D ? m
 template <int D> __device__ __forceinline__ float mq_logacc(float S) { return D ? __builtin_amdgcn_logf(S) : __logf(S); }
 template <int D> __device__ __forceinline__ double mq_logscale() { return D ? MQ_LN2 : 1.0; }
 
+// ---- decoded output for 17..64 states (hmm_posterior_decode_mid): the output policy of the posterior kernels of this
+// file (k_mq_posterior2) and of the chunked scan (backward<NT, 0> in hmm_scan_rows.inc).  NoDecode (hmm_engine.hip)
+// writes the gamma rows; DecodeMid collapses every gamma row, staged in LDS, to (class with the largest posterior, that
+// posterior): 1 + 4 bytes per position instead of 4 q.  A 16 x 64 weight table does not fit the argument segment next
+// to the other arguments, so the class table travels as sixteen 64-bit membership masks by value (a captured graph
+// keeps its table) and every block expands it once into a 0 / 1 weight per (class, state) in LDS (mid_weights).  A
+// class sum is then broadcast LDS reads and fma(v, w, sum) over ALL states in increasing index: fma(v, 1, sum) is
+// sum + v rounded once and fma(v, 0, sum) is sum, the bits of adding the members alone (DESIGN 4).
+struct alignas(8) DecodeMid {
+    static constexpr bool on = true;
+    unsigned long long mask[QP];     // bit s of mask[c]: state s belongs to class c
+    unsigned char *label;            // (k,b,L)
+    float *conf;                     // (k,b,L) or null
+    int ncls;                        // number of classes; 0: the identity map (no sums)
+};
+#define MID_WT_FLOATS (QP * MQ_MAX)
+
+// wt[c * 64 + s] for the whole block; every thread of the block calls this before any of them leaves
+__device__ __forceinline__ void mid_weights(const DecodeMid &d, float *wt) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
+#pragma unroll
+    for (int c = 0; c < QP; ++c)                                           // (constant indices: the masks stay arguments)
+        if (c % nw == wv) wt[c * MQ_MAX + lane] = ((d.mask[c] >> lane) & 1ull) ? 1.f : 0.f;
+    __syncthreads();
+}
+
+// One staged gamma row (q floats in LDS) -> label[at], conf[at]: the ONE collapse routine of both kernels.  W: the row
+// width the weights are walked over (a multiple of PIECE; states from q on read as 0 and weigh 0); PIECE: how many
+// values of the row are in registers at a time — the whole row where the registers are there (each value is read
+// once), 16 where they are not (the row is read again for every class).  Identity map: the largest entry and its
+// lowest index, nothing summed.
+template <int W, int PIECE>
+__device__ __forceinline__ void collapse_row(const float *row, int q, const DecodeMid &d, const float *wt, long long at) {
+    static_assert(W % PIECE == 0 && PIECE % 4 == 0 && W <= MQ_MAX, "whole pieces of a row of up to 64 states");
+    float best = row[0];
+    int lab = 0;
+    if (d.ncls == 0) {
+#pragma unroll 4
+        for (int s = 1; s < q; ++s) {
+            const float v = row[s];
+            if (v > best) { best = v; lab = s; }                          // strict: the lowest index wins a tie
+        }
+    } else {
+        float v[PIECE];
+        auto load = [&](int s0) {
+#pragma unroll
+            for (int u = 0; u < PIECE; ++u) v[u] = s0 + u < q ? row[s0 + u] : 0.f;
+        };
+        if constexpr (PIECE == W) load(0);
+#pragma unroll 1
+        for (int cl = 0; cl < d.ncls; ++cl) {
+            float sum = 0.f;                                               // states in increasing index
+#pragma unroll
+            for (int s0 = 0; s0 < W; s0 += PIECE) {
+                if (PIECE != W && s0 >= q) break;                          // (uniform)
+                if constexpr (PIECE != W) load(s0);
+                const f4 *w4 = reinterpret_cast<const f4 *>(wt + cl * MQ_MAX + s0);
+#pragma unroll
+                for (int u = 0; u < PIECE / 4; ++u) {
+                    const f4 w = w4[u];
+                    sum = __builtin_fmaf(v[4 * u + 0], w.x, sum);
+                    sum = __builtin_fmaf(v[4 * u + 1], w.y, sum);
+                    sum = __builtin_fmaf(v[4 * u + 2], w.z, sum);
+                    sum = __builtin_fmaf(v[4 * u + 3], w.w, sum);
+                }
+            }
+            if (cl == 0 || sum > best) { best = sum; lab = cl; }          // strict: the lowest class wins a tie
+        }
+    }
+    __builtin_nontemporal_store((unsigned char)lab, d.label + at);
+    if (d.conf) __builtin_nontemporal_store(best, d.conf + at);
+}
+
 // Row prefetch of the one-wave-per-sequence kernels: MQ_PF rows of a (L, q) slab in flight, one dword per lane and
 // row, through a buffer descriptor that covers exactly the rows wanted — rows outside [t1 bounds] fall outside
 // the descriptor and read 0, so there is NO branch around the loads.  (With the loads under `if (t + MQ_PF < L)` the
@@ -385,16 +458,41 @@ __global__ __launch_bounds__(64) void k_mq_backward(const float *__restrict__ A,
 // t < m, Rb_t for t >= m); after one barrier each finds the other's vector there and overwrites it
 // with gamma_t.  Same arithmetic as k_mq_forward + k_mq_backward, half the latency (the sweeps are
 // dependent chains: 105 -> ~55 ms for q = 29, b = 1024, L = 1e5).
-template <int QB, int D = 0>
-__global__ __launch_bounds__(128) void k_mq_posterior2(const float *__restrict__ A, const float *__restrict__ pi,
-                                                       const float *__restrict__ E, int b, int L, int q, float eps,
-                                                       float *__restrict__ out, double *__restrict__ ll, int mode,
-                                                       const int *__restrict__ need = nullptr,
-                                                       const MqSp *__restrict__ sp = nullptr) {
+//
+// DEC = DecodeMid (hmm_posterior_decode_mid, mode 0): there is no `out`.  The vectors are parked in `out` all the same
+// — the caller hands the workspace's parking region, k b L q floats addressed like the output —, and in place of the
+// gamma store each wave stages its rows in a wave-private LDS ring of MQ_RING rows (lds: the block's weight table,
+// then the two rings; rows q | 1 floats apart, so that the lanes of a drain are on distinct banks).  The ring fills
+// by whole blocks of MQ_PF steps from empty, so it is full exactly after MQ_RING / MQ_PF blocks: it is drained there,
+// BETWEEN two blocks (where the fewest registers are live), with all MQ_RING rows in it, and once more at the end
+// with the 0 .. MQ_RING - 1 rows that are left (the last whole blocks and the ragged tail of up to MQ_PF - 1 steps).
+// In a drain lane r collapses row r (collapse_row).  Wave 0's rows ascend from L / 2, wave 1's descend from
+// L / 2 - 1.  Every instruction up to the gamma value is shared with the NoDecode form.
+#define MQ_RING 64
+static_assert(MQ_RING % MQ_PF == 0, "the ring is full after a whole number of step blocks");
+template <int QB, int D, class DEC>
+__device__ __forceinline__ void mq_posterior2_body(const float *__restrict__ A, const float *__restrict__ pi,
+                                                   const float *__restrict__ E, int b, int L, int q, float eps,
+                                                   float *__restrict__ out, double *__restrict__ ll, int mode,
+                                                   const int *__restrict__ need, const MqSp *__restrict__ sp,
+                                                   const DEC &dec, float *lds) {
     const int row = blockIdx.x, m = row / b, j = threadIdx.x & 63;
     if (need && !need[row]) return;                          // block-uniform: before the barriers
     if (!mq_sp_mine<D>(sp, m, 2)) return;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int rstride = q | 1;
+    float *ring = DEC::on ? lds + MID_WT_FLOATS + wv * MQ_RING * rstride : nullptr;
+    int cnt = 0, tfirst = 0;                                 // rows in the ring, the position of its row 0
+    auto drain = [&]() {
+        if constexpr (DEC::on) {
+            __builtin_amdgcn_wave_barrier();
+            if (j < cnt)
+                collapse_row<MQ_MAX, 4>(ring + j * rstride, q, dec, lds,
+                                         (long long)row * L + (wv == 0 ? tfirst + j : tfirst - j));
+            __builtin_amdgcn_wave_barrier();
+            cnt = 0;
+        }
+    };
     const bool act = j < q;
     const float *Am = A + (size_t)m * q * q;
     const float *Er = E + (size_t)row * L * q;
@@ -418,8 +516,14 @@ __global__ __launch_bounds__(128) void k_mq_posterior2(const float *__restrict__
     auto emit = [&](float al, float rb, int t) {             // gamma_t from alpha_hat_t and Rb_t
         const float g = act ? al * rb : 0.f;
         const float Sg = mq_sum<D>(g);
-        const float v = (mode == 0) ? g * __builtin_amdgcn_rcpf(Sg) : __logf(g) - __logf(Sg);
-        if (act) o[(size_t)t * q + j] = v;
+        if constexpr (DEC::on) {
+            if (cnt == 0) tfirst = t;
+            if (act) ring[cnt * rstride + j] = g * __builtin_amdgcn_rcpf(Sg);
+            ++cnt;
+        } else {
+            const float v = (mode == 0) ? g * __builtin_amdgcn_rcpf(Sg) : __logf(g) - __logf(Sg);
+            if (act) o[(size_t)t * q + j] = v;
+        }
     };
     if (wv == 0) {
         float x = act ? pi[(size_t)m * q + j] : 0.f;
@@ -455,6 +559,7 @@ __global__ __launch_bounds__(128) void k_mq_posterior2(const float *__restrict__
                 orows.up(tb + MQ_PF, tr, rn);
 #pragma unroll
                 for (int u = 0; u < MQ_PF; ++u) step(tb + u, ce[u], cr[u]);
+                if (DEC::on && phase && cnt == MQ_RING) drain();
             }
 #pragma unroll
             for (int u = 0; u < MQ_PF; ++u)
@@ -492,6 +597,7 @@ __global__ __launch_bounds__(128) void k_mq_posterior2(const float *__restrict__
                 orows.down(tb - MQ_PF, ta, an);
 #pragma unroll
                 for (int u = 0; u < MQ_PF; ++u) step(tb - u, ce[u], ca[u]);
+                if (DEC::on && phase && cnt == MQ_RING) drain();
             }
 #pragma unroll
             for (int u = 0; u < MQ_PF; ++u)
@@ -499,7 +605,31 @@ __global__ __launch_bounds__(128) void k_mq_posterior2(const float *__restrict__
             if (!phase) __syncthreads();                    // the forward wave has parked alpha_hat_t for t < mid
         }
     }
+    drain();
 }
+
+template <int QB, int D = 0>
+__global__ __launch_bounds__(128) void k_mq_posterior2(const float *__restrict__ A, const float *__restrict__ pi,
+                                                       const float *__restrict__ E, int b, int L, int q, float eps,
+                                                       float *__restrict__ out, double *__restrict__ ll, int mode,
+                                                       const int *__restrict__ need = nullptr,
+                                                       const MqSp *__restrict__ sp = nullptr) {
+    mq_posterior2_body<QB, D, NoDecode>(A, pi, E, b, L, q, eps, out, ll, mode, need, sp, NoDecode(), nullptr);
+}
+
+// k_mq_posterior2 with the DecodeMid output policy; park: the workspace's parking region.
+// Dynamic LDS: mq_decode_lds(q) bytes.
+template <int QB, int D = 0>
+__global__ __launch_bounds__(128) void k_mq_posterior2_decode(const float *__restrict__ A, const float *__restrict__ pi,
+                                                              const float *__restrict__ E, int b, int L, int q, float eps,
+                                                              float *__restrict__ park, double *__restrict__ ll,
+                                                              const int *__restrict__ need, const MqSp *__restrict__ sp,
+                                                              const DecodeMid dec) {
+    extern __shared__ __attribute__((aligned(16))) float mq_lds[];
+    mid_weights(dec, mq_lds);
+    mq_posterior2_body<QB, D, DecodeMid>(A, pi, E, b, L, q, eps, park, ll, 0, need, sp, dec, mq_lds);
+}
+static unsigned mq_decode_lds(int q) { return (unsigned)((MID_WT_FLOATS + 2 * MQ_RING * (q | 1)) * sizeof(float)); }
 
 // sp (or null: dense steps only): room for k MqSp tables, filled here
 static void mq_sp_prepare(const float *A, int k, int q, MqSp *sp, hipStream_t st) {
@@ -520,6 +650,23 @@ static void mq_posterior2(const float *A, const float *pi, const float *E, int k
         hipLaunchKernelGGL((k_mq_posterior2<48>), grid, dim3(128), 0, st, A, pi, E, b, L, q, eps, out, ll, mode, need, (const MqSp *)sp);
     else
         hipLaunchKernelGGL((k_mq_posterior2<64>), grid, dim3(128), 0, st, A, pi, E, b, L, q, eps, out, ll, mode, need, (const MqSp *)sp);
+}
+
+// the decode form of mq_posterior2 (any L >= 1: at L = 1 the forward wave has the one position and finds Rb = 1
+// parked, the arithmetic of mq_forward + mq_backward)
+static void mq_posterior2_decode(const float *A, const float *pi, const float *E, int k, int b, int L, int q, float eps,
+                                 float *park, double *ll, const DecodeMid &dec, hipStream_t st, const int *need,
+                                 MqSp *sp) {
+    const dim3 grid((unsigned)(k * b));
+    const unsigned lds = mq_decode_lds(q);
+    const MqSp *csp = sp;
+    if (sp) {
+        mq_sp_prepare(A, k, q, sp, st);
+        launch(k_mq_posterior2_decode<64, 4>, grid, dim3(128), lds, st, A, pi, E, b, L, q, eps, park, ll, need, csp, dec);
+        launch(k_mq_posterior2_decode<64, 8>, grid, dim3(128), lds, st, A, pi, E, b, L, q, eps, park, ll, need, csp, dec);
+    }
+    auto *kern = q <= 32 ? k_mq_posterior2_decode<32> : q <= 48 ? k_mq_posterior2_decode<48> : k_mq_posterior2_decode<64>;
+    launch(kern, grid, dim3(128), lds, st, A, pi, E, b, L, q, eps, park, ll, need, csp, dec);
 }
 
 static void mq_forward_signed(const float *A, const float *pi, const float *E, int k, int b, int L, int q, float eps,

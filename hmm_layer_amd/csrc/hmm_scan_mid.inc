@@ -144,15 +144,21 @@ static void scan_loglik(const float *A, const float *pi, const float *E, const M
 
 template <class S>
 static void scan_posterior(const float *A, const float *pi, const float *E, const MidPlan &pp, float eps, int mode,
-                           float *out, char *ws, hipStream_t st) {
+                           float *out, char *ws, hipStream_t st, const DecodeMid *dec) {
     const WsMid w(pp, ws);
     scan_reduce_scan<S>(A, pi, E, pp, eps, ws, st);
     launch(forward<S::NT, false, false>, mid_grid(pp), dim3(256), 0, st, A, E, w.prefix, nullptr, w.ckpt, nullptr, w.elig,
            pp.p, eps, pp.nwaves, nullptr, nullptr);
+    if (dec) {                                               // hmm_posterior_decode_mid (HMM_POST_PROB, no `out`)
+        launch(backward<S::NT, 0, false, DecodeMid>, mid_grid(pp), dim3(256), 0, st, A, E, w.ckpt, w.suffix, nullptr,
+               nullptr, nullptr, w.phi, w.elig, pp.p, eps, pp.nwaves, nullptr, *dec);
+        scan_select<S>(pp, w, w.phi, st);
+        return;
+    }
     auto *kern = mode == HMM_POST_PROB ? backward<S::NT, 0, false>
                  : mode == HMM_POST_LOG ? backward<S::NT, 1, false> : backward<S::NT, 2, false>;
     launch(kern, mid_grid(pp), dim3(256), 0, st, A, E, w.ckpt, w.suffix, w.lsuf, w.loglik, out, w.phi, w.elig, pp.p, eps,
-           pp.nwaves, nullptr);
+           pp.nwaves, nullptr, NoDecode());
     scan_select<S>(pp, w, w.phi, st);
 }
 
@@ -180,6 +186,6 @@ static void scan_backward(const float *A, const float *E, const MidPlan &pp, flo
                             st);
     scan_reduce_scan<S>(A, w.upi, E, pp, eps, ws, st);
     launch(backward<S::NT, 3, true>, mid_grid(pp), dim3(256), 0, st, A, E, nullptr, w.suffix, w.lsuf, nullptr, log_beta,
-           w.phi, w.elig, pp.p, eps, pp.nwaves, w.prefix);
+           w.phi, w.elig, pp.p, eps, pp.nwaves, w.prefix, NoDecode());
     scan_select<S>(pp, w, w.phi, st);
 }

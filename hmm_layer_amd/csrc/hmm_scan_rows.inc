@@ -367,6 +367,29 @@ __device__ __forceinline__ void flush(const OutT<NT> &o, int lane, int row0, int
     __builtin_amdgcn_wave_barrier();
 }
 
+// DecodeMid's flush of the same rows: the chain table holds ROW offsets from `rowbase` (the wave's first row in the
+// (k,b,L) outputs).  A lane takes one staged row of one chain (16 chains x nrows rows: up to 128 at NT = 2, 64 at
+// NT = 4) and collapses it (collapse_row, hmm_midq.inc); a chain's ragged end and chains the wave does not own
+// (len 0) are skipped through the table.  Every lane addresses its own byte, so a chunk may start at any byte offset.
+// NT = 2 holds the row's 32 values in registers; NT = 4, at one wave per SIMD and up to 256 VGPRs, streams it in
+// pieces of 16.
+template <int NT>
+__device__ __forceinline__ void decode_flush(const OutT<NT> &o, const DecodeMid &d, const float *wt, long long rowbase,
+                                             int lane, int row0, int nrows) {
+    const int *tab = reinterpret_cast<const int *>(o.seg + 16 * Rows<NT>::STAGE_STRIDE);
+    const float inv = 1.0f / (float)nrows;
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll 1
+    for (int pc = lane; pc < 16 * nrows; pc += 64) {
+        const int c = (int)(((float)pc + 0.5f) * inv);                    // pc / nrows, exact for these ranges
+        const int r = pc - c * nrows;
+        if (r >= tab[16 + c] - row0) continue;
+        collapse_row<Rows<NT>::W, NT == 2 ? 32 : 16>(o.seg + c * Rows<NT>::STAGE_STRIDE + r * o.q, o.q, d, wt,
+                                                     rowbase + tab[c] + row0 + r);
+    }
+    __builtin_amdgcn_wave_barrier();
+}
+
 // max(d, eps)'s clamp-born part, component-wise: where the clamp was active the whole eps is born there, elsewhere the
 // carried clamp-born part df (forward_body's CERT / backward_body's CERT3 in hmm_engine.hip)
 __device__ __forceinline__ f4 born4(f4 d, f4 df, float eps) {
@@ -867,14 +890,24 @@ __global__ __launch_bounds__(256) void forward(const float *__restrict__ A, cons
 //   chunk is carried along (Gv) and weighed at the chunk's first position with alpha_hat there, one forward step from
 //   the chunk scan's prefix vector (a uniform start); also the clamp-born share of R where the chunk hands over to the
 //   one before, and what it becomes under that chunk's last observation -> phi[chain]
-template <int NT, int MODE, bool CERT3>
+// DEC: the output policy (MODE 0), the kernel's last argument.  NoDecode (an empty argument) flushes the staged gamma
+// rows (flush<NT>); DecodeMid (hmm_posterior_decode_mid; no `out`) collapses them (decode_flush<NT>) with the block's
+// weight table in LDS — everything up to the staged row is shared.
+template <int NT, int MODE, bool CERT3, class DEC = NoDecode>
 __global__ __launch_bounds__(256) void backward(const float *__restrict__ A, const float *__restrict__ E,
                                                 const float *__restrict__ ckpt, const float *__restrict__ suffix,
                                                 const double *__restrict__ lsuf, const double *__restrict__ loglik,
                                                 float *__restrict__ out, float *__restrict__ phi,
                                                 const int *__restrict__ elig, Plan p, float eps, long long nwaves,
-                                                const float *__restrict__ prefix) {
+                                                const float *__restrict__ prefix, const DEC dec) {
     static_assert(!CERT3 || MODE == 3, "CERT3 is the log beta certificate");
+    static_assert(!DEC::on || MODE == 0, "labels are decoded from the probability output");
+    const float *wt = nullptr;
+    if constexpr (DEC::on) {                                 // (the whole block, before any wave leaves)
+        __shared__ __attribute__((aligned(16))) float wts[MID_WT_FLOATS];
+        mid_weights(dec, wts);
+        wt = wts;
+    }
     typedef Rows<NT> R;
     constexpr int W = R::W, BLK = R::BLK;
     const long long wave = (long long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -906,8 +939,11 @@ __global__ __launch_bounds__(256) void backward(const float *__restrict__ A, con
     const BT<NT> bd = make_bounds<NT>(g, q, eps);
     const int rowb = q * (int)sizeof(float);
     __shared__ __attribute__((aligned(16))) float ostage[4 * R::STAGE_SEG];
-    const OutT<NT> os = make_out<NT>(ostage + w * R::STAGE_SEG, reinterpret_cast<char *>(out + (tl.baseE - E)), q, lane,
-                                     tl.voff - g * 16, tl.len);
+    // (DecodeMid: the chain table in rows, not bytes, and the wave's first row in place of a base pointer)
+    const OutT<NT> os = DEC::on ? make_out<NT>(ostage + w * R::STAGE_SEG, nullptr, q, lane, (tl.voff - g * 16) / rowb, tl.len)
+                                : make_out<NT>(ostage + w * R::STAGE_SEG, reinterpret_cast<char *>(out + (tl.baseE - E)), q,
+                                               lane, tl.voff - g * 16, tl.len);
+    const long long rowbase = DEC::on ? (long long)(tl.baseE - E) / q : 0;
 
     XT<NT> Rv = ld_vec<NT>(suffix + (size_t)tl.chain * W, g);
     float llf = 0.f;
@@ -1005,7 +1041,8 @@ __global__ __launch_bounds__(256) void backward(const float *__restrict__ A, con
         if (MODE == 3) lbb += (double)lacc;
         if (j % GB == 0) {
             const int top = p.nsub - j;
-            flush<NT>(os, lane, j * BLK, (top < GB ? top : GB) * BLK);
+            if constexpr (DEC::on) decode_flush<NT>(os, dec, wt, rowbase, lane, j * BLK, (top < GB ? top : GB) * BLK);
+            else flush<NT>(os, lane, j * BLK, (top < GB ? top : GB) * BLK);
         }
     }
     phiacc = col_sum(phiacc);

@@ -125,7 +125,7 @@ static void ssm_posterior(const float *A, const float *pi, const float *E, const
     auto *kern = mode == HMM_POST_PROB ? backward<S::NT, 0, false>
                  : mode == HMM_POST_LOG ? backward<S::NT, 1, false> : backward<S::NT, 2, false>;
     launch(kern, mid_grid(pp), dim3(256), 0, st, A, E, w.ckpt, w.suffix, w.lsuf, w.loglik, out, w.phi, w.elig, p, eps,
-           pp.nwaves, nullptr);
+           pp.nwaves, nullptr, NoDecode());
     if (loglik) launch(k_copy_loglik, dim3((p.NB + 255) / 256), dim3(256), 0, st, total, loglik, p.NB);
     if (phi_out)
         launch(k_mid_phi, dim3((p.NB + 255) / 256), dim3(256), 0, st, w.phi, w.elig, ws_at<int>(ws, sp.o_elig2), w.exps,

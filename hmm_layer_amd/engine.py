@@ -143,6 +143,14 @@ DECODE_SIGNATURES = {
     "hmm_posterior_decode": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _P, _I, _P, _P, _P, _P, _SZ, _P]),
 }
 
+# ... and those of the fused decode for 17..64 states (hmm_posterior_decode_mid), apart from both tables above for the
+# same reason: each table's guard-band completeness check lives in the test file that has its rows.
+DECODE_MID_SIGNATURES = {
+    "hmm_posterior_decode_mid_max_states": (_I, []),
+    "hmm_posterior_decode_mid_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "hmm_posterior_decode_mid": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _P, _I, _P, _P, _P, _P, _SZ, _P]),
+}
+
 
 def lib():
     """The loaded shared library (loaded once).  Raises if it has not been built."""
@@ -154,7 +162,7 @@ def lib():
             "HIP engine library %s is missing: build it with `python -m hmm_layer_amd.build` "
             "(there is no CPU fallback)" % LIB_PATH)
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**_SIGNATURES, **DECODE_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**_SIGNATURES, **DECODE_SIGNATURES, **DECODE_MID_SIGNATURES}.items():
         if not hasattr(L, name):
             raise EngineError("the engine library %s does not export %s: rebuild it with "
                               "`python -m hmm_layer_amd.build`" % (LIB_PATH, name))
@@ -467,30 +475,38 @@ def decode_posterior(gamma, table, C):
 def posterior_decode(A, pi, E, state_class=None, num_classes=None, eps=EPS, want_conf=True):
     """Posterior decoding -> (label (k,b,L) uint8, conf (k,b,L) fp32 or None, loglik (k,b) fp64): per position the
     class with the largest posterior (the sum of the state posteriors of its states; the lowest class on ties) and
-    that posterior.  Up to 16 states the engine's kernels produce the labels themselves and the (k,b,L,q) tensor is
-    never written; above, this composes posterior(POST_PROB) with torch ops (same shapes, dtypes and tie rule) and the
-    number of classes is not limited to 16 (but to 256, the range of a label)."""
+    that posterior.  Up to 64 states the engine's kernels produce the labels themselves and the (k,b,L,q) tensor is
+    never written (hmm_posterior_decode up to 16 states, hmm_posterior_decode_mid for 17..64 with the identity map or
+    at most 16 classes; the latter's workspace holds a parking region as large as that tensor, see the header).
+    Everything else — more than 64 states, or more than 16 classes above 16 states — composes posterior(POST_PROB)
+    with torch ops (same shapes, dtypes and tie rule); the number of classes is then limited to 256, the range of a
+    label.  The fused call's workspace is cached per (device, stream) like every workspace of this module; for 17..64
+    states it is as large as the posterior tensor and stays allocated until release_workspaces()."""
     A, pi, E = _dev(A, "A"), _dev(pi, "pi"), _dev(E, "E")
     A, pi, dims = _shapes(A, E, pi)
     q = dims[3]
     table, C = class_table(state_class, num_classes, q)
-    if q > lib().hmm_posterior_decode_max_states():
+    small = q <= lib().hmm_posterior_decode_max_states()
+    if not small and (q > lib().hmm_posterior_decode_mid_max_states() or (table is not None and C > 16)):
         if C > 256:
             raise ValueError("labels are bytes: at most 256 classes, got %d" % C)
         gamma, ll = posterior(A, pi, E, POST_PROB, eps)
         label, conf = decode_posterior(gamma, table, C)
         return label, (conf if want_conf else None), ll
-    if C > 16:
+    if small and C > 16:
         raise ValueError("at most 16 classes, got %d" % C)
+    nbytes = (lib().hmm_workspace_bytes(OP_POSTERIOR, *dims) if small
+              else lib().hmm_posterior_decode_mid_workspace_bytes(*dims))
+    call = lib().hmm_posterior_decode if small else lib().hmm_posterior_decode_mid
     with torch.cuda.device(E.device):
-        ws = _workspace(E.device, lib().hmm_workspace_bytes(OP_POSTERIOR, *dims), DECODE_TAG)
+        ws = _workspace(E.device, nbytes, DECODE_TAG)
         label = torch.empty(dims[:3], dtype=torch.uint8, device=E.device)
         conf = torch.empty(dims[:3], dtype=torch.float32, device=E.device) if want_conf else None
         ll = torch.empty(dims[:2], dtype=torch.float64, device=E.device)
         tab = (ctypes.c_int * q)(*table) if table is not None else None
-        _check(lib().hmm_posterior_decode(A.data_ptr(), pi.data_ptr(), E.data_ptr(), *dims, eps, tab, C,
-                                          label.data_ptr(), conf.data_ptr() if want_conf else None, ll.data_ptr(),
-                                          ws.data_ptr(), ws.numel(), _stream(E.device)))
+        _check(call(A.data_ptr(), pi.data_ptr(), E.data_ptr(), *dims, eps, tab, C,
+                    label.data_ptr(), conf.data_ptr() if want_conf else None, ll.data_ptr(),
+                    ws.data_ptr(), ws.numel(), _stream(E.device)))
     return label, conf, ll
 
 

@@ -249,7 +249,7 @@ int hmm_window_table(int op, int k, int b, int L, int q, const void *workspace, 
  * Posterior decoding, fused: per position the CLASS with the largest posterior and that posterior, without the
  * (k,b,L,q) tensor ever reaching memory — 1 + 4 bytes per position instead of 4 q.  For
  * q <= hmm_posterior_decode_max_states() (16); above, callers compose hmm_posterior with a reduction of their own
- * (hmm_layer_amd.engine.posterior_decode does): fused kernels for 17..64 states and beyond are a follow-up.
+ * (hmm_layer_amd.engine.posterior_decode does); 17..64 states have hmm_posterior_decode_mid below.
  *   state_class  HOST pointer, q entries in 0 .. num_classes-1: the class of every state; NULL = the identity map
  *                (every state its own class; num_classes must then equal q).  Read during the call and passed to the
  *                kernels by value: the caller may change or free it at once, and a captured graph keeps the table it
@@ -278,6 +278,43 @@ int hmm_posterior_decode(const float *A, const float *pi, const float *E,
                          const int *state_class, int num_classes,
                          unsigned char *label, float *conf, double *loglik,
                          void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * The same for 17 <= q <= hmm_posterior_decode_mid_max_states() (64): the two-, three- and four-copy gene models
+ * (29 / 43 / 57 states) and any learned dense A of that range.  Arguments, outputs, clamp semantics and routing are
+ * those of hmm_posterior_decode, applied to what hmm_posterior(HMM_POST_PROB) computes for these models: the chunked
+ * scan (hmm_scan_rows.inc) collapses its staged gamma rows on chip, and the sequences that hmm_posterior routes to the
+ * one-wave-per-sequence kernels (hmm_midq.inc: models the device finds non-primitive, sequences the certificate
+ * flags, HMM_EXACT_ALWAYS, every sequence of 33..64 states outside the chunked scan's range) are routed here too,
+ * to a form of those kernels that stages its gamma rows in LDS and collapses them the same way.
+ *   state_class  HOST pointer or NULL, as above; reaches the kernels by value (sixteen 64-bit membership masks)
+ *   num_classes  1 .. 16 with a table; q with the identity map (state_class NULL)
+ *   label, conf, loglik   as above.  Identity map: conf is bit for bit the largest entry of hmm_posterior's row and
+ *                label its lowest index; loglik is bit for bit hmm_posterior's.
+ * Workspace: hmm_posterior_decode_mid_workspace_bytes(k, b, L, q) (0: unsupported shape), 256-byte aligned.  Its
+ * first hmm_workspace_bytes(HMM_OP_POSTERIOR, k, b, L, q) bytes have exactly hmm_posterior's layout, so
+ * hmm_exact_count(HMM_OP_POSTERIOR, ...) reads the routing of a finished call as it does for hmm_posterior.  A
+ * PARKING REGION of k*b*L*q floats follows: the serial walk's two waves park alpha_hat (t < L/2) and the backward
+ * vector (t >= L/2) there until they meet, where hmm_posterior parks them in `out`.  THE WORKSPACE IS THEREFORE AS
+ * LARGE AS THE (k,b,L,q) TENSOR THE CALL AVOIDS WRITING — still less memory than hmm_posterior plus a reduction
+ * (gamma, class sums and an argmax), and only walked sequences touch the region; bounding it by device-assigned slots
+ * is a follow-up.  The query returns exactly what the call uses.
+ * Memory contract: every label and conf element is written; nothing is read from the workspace before the call has
+ * written it; label chunks start at arbitrary byte offsets; every offset into E, label and conf is 64-bit.  Runs on
+ * `stream` alone with no host synchronisation (capturable); no atomics in the outputs; repeated calls are
+ * bit-identical.
+ * Argument checks, before any HIP call, in this order: shape (HMM_ERR_BAD_SHAPE), q < 17 or q > 64
+ * (HMM_ERR_Q_UNSUPPORTED), NULL among A, pi, E, label, workspace (HMM_ERR_NULL_POINTER), the class table as for
+ * hmm_posterior_decode (HMM_ERR_BAD_ARGUMENT), workspace too small or not 256-byte aligned (HMM_ERR_WORKSPACE).
+ * Fused decode above 64 states and sequence-sharded decode are follow-ups.
+ */
+int hmm_posterior_decode_mid_max_states(void);
+size_t hmm_posterior_decode_mid_workspace_bytes(int k, int b, int L, int q);
+int hmm_posterior_decode_mid(const float *A, const float *pi, const float *E,
+                             int k, int b, int L, int q, float eps,
+                             const int *state_class, int num_classes,
+                             unsigned char *label, float *conf, double *loglik,
+                             void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Viterbi state paths (max-plus scan).  The reference has none (only a docstring mention,

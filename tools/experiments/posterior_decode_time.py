@@ -1,4 +1,4 @@
-"""What fused posterior decoding (engine.posterior_decode, up to 16 states) costs next to what users run today.
+"""What fused posterior decoding (engine.posterior_decode, up to 64 states) costs next to what users run today.
 
 Per step (a model, a shape, a kind of input), in ONE process, after a warm-up of every variant, timed with device
 events, the three variants ALTERNATING round by round so that drift hits them alike:
@@ -14,8 +14,12 @@ reported (both sums are fp32, in different orders: only near-ties may differ).
 
 Steps: the 15-state gene model at b = 1024 x L = 100 000 on uniform-random emissions and on the fused emitter's
 output for softmax(2 randn) class probabilities (47 % zeros; the record says how many sequences were routed), at
-b = 32 x L = 9999, and the 7-state model at b = 1024 x L = 100 000.  One child process per step under its own time
-limit; the first failure stops the run.  One JSON line per step.
+b = 32 x L = 9999, and the 7-state model at b = 1024 x L = 100 000.  For 17..64 states (hmm_posterior_decode_mid;
+MID_STEPS, emissions 0.05 + 0.9 u^4): the 29-state two-copy gene model onto 6 classes at b = 1024 x L = 100 000 and
+b = 32 x L = 9999, the 43-state three-copy model at b = 1024 x L = 10 000 (every sequence on the one-wave-per-sequence
+walk) and b = 32 x L = 9999 (the 64-lane scan), and a dense 24-state model at b = 128 x L = 100 000.  (ii) is timed on
+the code path of the build before the fused kernels, engine.posterior + engine.decode_posterior.  One child process
+per step under its own time limit; the first failure stops the run.  One JSON line per step.
 
     python tools/experiments/posterior_decode_time.py [--steps g15-1024-100000-uniform,...] [--rounds N] [--out FILE]
                                                       [--lib OTHER_BUILD.so]      (A/B of a kernel change)
@@ -38,17 +42,26 @@ if "--lib" in sys.argv:                                      # another build of 
     engine.LIB_PATH = os.path.abspath(sys.argv[sys.argv.index("--lib") + 1])
 DEV = "cuda:0"
 STEPS = ("g15-1024-100000-uniform", "g15-1024-100000-emitter", "g15-32-9999-uniform", "g7-1024-100000-uniform")
+MID_STEPS = ("g29-1024-100000-peaked", "g29-32-9999-peaked", "g43-1024-10000-peaked", "g43-32-9999-peaked",
+             "d24-128-100000-peaked")                         # --steps mid
 # Ir, I0-2, E0-2, START, EI0-2, IE0-2, STOP -> intergenic / intron / exon phase 0, 1, 2
-CLASSES = {15: [0, 1, 1, 1, 2, 3, 4, 2, 1, 1, 1, 1, 1, 1, 4], 7: [0, 1, 1, 1, 2, 3, 4]}
+CLASSES = {15: [0, 1, 1, 1, 2, 3, 4, 2, 1, 1, 1, 1, 1, 1, 4], 7: [0, 1, 1, 1, 2, 3, 4],
+           # the multi-copy gene models: intergenic, then five classes per copy's 14 states, shared by the copies
+           29: [0] + [1 + (i % 14) // 3 for i in range(28)], 43: [0] + [1 + (i % 14) // 3 for i in range(42)],
+           24: [i % 6 for i in range(24)]}
 CODONS = dict(start_codons=[("ATG", 1.)], stop_codons=[("TAG", .34), ("TAA", .33), ("TGA", .33)],
               intron_begin_pattern=[("NGT", .99), ("NGC", .005), ("NAT", .005)],
               intron_end_pattern=[("AGN", .99), ("ACN", .01)])
 
 
-def model(q):
+def model(q, dense=False):
     from hmm_layer_amd.gene_pred_hmm_transitioner import GenePredMultiHMMTransitioner, SimpleGenePredHMMTransitioner
+    if dense:
+        g = torch.Generator(device=DEV).manual_seed(q)
+        A = torch.rand((1, q, q), device=DEV, generator=g) ** 3 + 1e-3
+        return (A / A.sum(-1, keepdim=True)).contiguous(), torch.full((1, q), 1.0 / q, device=DEV)
     kw = dict(initial_exon_len=200, initial_intron_len=4500, initial_ir_len=10000, starting_distribution_init="zeros")
-    tr = (GenePredMultiHMMTransitioner(**kw) if q == 15 else SimpleGenePredHMMTransitioner(**kw)).to(DEV)
+    tr = (SimpleGenePredHMMTransitioner(**kw) if q == 7 else GenePredMultiHMMTransitioner(k=(q - 1) // 14, **kw)).to(DEV)
     with torch.no_grad():
         A, pi = tr.make_A().contiguous(), tr.make_initial_distribution().reshape(1, -1).contiguous()
     assert A.shape[-1] == q
@@ -59,6 +72,8 @@ def emissions(kind, b, L, q):
     g = torch.Generator(device=DEV).manual_seed(7)
     if kind == "uniform":
         return torch.rand((1, b, L, q), device=DEV, generator=g) * 0.9 + 0.05
+    if kind == "peaked":
+        return torch.rand((1, b, L, q), device=DEV, generator=g).pow_(4).mul_(0.9).add_(0.05)
     assert q == 15
     from hmm_layer_amd.gene_pred_hmm_emitter import GenePredHMMEmitter
     em = GenePredHMMEmitter(**CODONS)
@@ -99,11 +114,11 @@ def kernel_split(fn, passes=3):
 def calls(step):
     name, b, L, kind = step.split("-")
     q = int(name[1:])
-    A, pi = model(q)
+    A, pi = model(q, name[0] == "d")
     E = emissions(kind, int(b), int(L), q)
     for _ in range(3):
         engine.posterior(A, pi, E)
-        engine.posterior_decode(A, pi, E, CLASSES[q], 5)
+        engine.posterior_decode(A, pi, E, CLASSES[q])
     torch.cuda.synchronize()
     print("done")
 
@@ -111,9 +126,9 @@ def calls(step):
 def one(step, rounds):
     name, b, L, kind = step.split("-")
     q, b, L = int(name[1:]), int(b), int(L)
-    A, pi = model(q)
+    A, pi = model(q, name[0] == "d")
     E = emissions(kind, b, L, q)
-    table, C = CLASSES[q], 5
+    table, C = CLASSES[q], max(CLASSES[q]) + 1
     gamma = torch.empty_like(E)
 
     def v1():
@@ -153,8 +168,12 @@ def one(step, rounds):
         t = times[n]
         rec[n + "_ms"] = {"min": round(min(t), 4), "median": round(statistics.median(t), 4),
                           "spread": round(max(t) - min(t), 4), "host_enqueue_median": round(statistics.median(host[n]), 4)}
-    rec["routing_decode"] = engine.exact_detail((1, b, L, q), tag=engine.DECODE_TAG)
-    rec["routing_posterior"] = engine.exact_detail((1, b, L, q))
+    if q <= 16:
+        rec["routing_decode"] = engine.exact_detail((1, b, L, q), tag=engine.DECODE_TAG)
+        rec["routing_posterior"] = engine.exact_detail((1, b, L, q))
+    else:       # sequences the walk served next to the chunked scan (0 where the walk serves the whole call by plan)
+        rec["routing_decode"] = {"routed": engine.exact_count(engine.OP_POSTERIOR, (1, b, L, q), tag=engine.DECODE_TAG)}
+        rec["routing_posterior"] = {"routed": engine.exact_count(engine.OP_POSTERIOR, (1, b, L, q))}
     # what the fused call returns against the composed one
     l2, c2, ll2 = v2()
     l3, c3, ll3 = v3()
@@ -183,8 +202,11 @@ def main():
         return one(arg("--one"), rounds)
     if arg("--calls"):
         return calls(arg("--calls"))
-    limit = int(arg("--limit") or 150)
-    for step in (arg("--steps") or ",".join(STEPS)).split(","):
+    steps = arg("--steps") or ",".join(STEPS)
+    # the 17..64-state steps hold E, two gamma tensors and a gamma-sized parking region (11.9 GB each at the largest)
+    # and draw up to 3e9 emissions: a longer limit per child than the 15-state steps have
+    limit = int(arg("--limit") or (300 if steps == "mid" else 150))
+    for step in (",".join(MID_STEPS) if steps == "mid" else steps).split(","):
         # a child process per step, each under its own time limit; the first failure stops the run
         res = subprocess.run([sys.executable, os.path.abspath(__file__), "--one", step, "--rounds", str(rounds)] +
                              (["--lib", engine.LIB_PATH] if arg("--lib") else []),
