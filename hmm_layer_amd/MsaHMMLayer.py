@@ -30,6 +30,7 @@ from . import autograd, distributed, engine
 from .Bidirectional import Bidirectional
 from .BaseRNN import BaseRNN
 from .TotalProbabilityCell import TotalProbabilityCell
+from .gene_pred_hmm_transitioner import GenePredMultiHMMTransitioner
 
 
 def _engine_inputs(inputs, cell, end_hints, training):
@@ -250,14 +251,17 @@ class MsaHmmLayer(nn.Module):
         integer tensor; None: every state its own class); a class posterior is the sum over its states, ties go to
         the lowest class.  On a HIP device one engine call (engine.posterior_decode: the (k,b,L,q) posterior is never
         written for models of up to 64 states with the identity map or at most 16 classes — the multi-copy gene
-        models of 29 / 43 / 57 states included —; other models compose the posterior with torch ops); elsewhere the
-        same reduction of a step-at-a-time posterior.  Inference only."""
+        models of 29 / 43 / 57 states included —, nor for 65..256 states where the per-sequence walk measured
+        faster (hmm_posterior_decode_wide; above 128 states only for a GenePredMultiHMMTransitioner, whose A takes the
+        walk's sparse step); other models compose the posterior with torch ops); elsewhere the same reduction of a
+        step-at-a-time posterior.  Inference only."""
         if _wants_grad(inputs, self.cell):
             raise ValueError("posterior_decode is inference only (labels carry no gradient): call it under "
                              "torch.no_grad(), or train through state_posterior_log_probs")
         A, pi, E = _engine_inputs(inputs, self.cell, end_hints, False)
         if E.is_cuda:
-            return engine.posterior_decode(A, pi, E, state_class, num_classes, eps=self.cell.epsilon)
+            sparse = isinstance(self.cell.transitioner, GenePredMultiHMMTransitioner)
+            return engine.posterior_decode(A, pi, E, state_class, num_classes, eps=self.cell.epsilon, sparse=sparse)
         table, C = engine.class_table(state_class, num_classes, E.shape[-1])
         gamma, loglik = _posterior_probs_host(A, pi, E, self.cell.epsilon)
         return (*engine.decode_posterior(gamma, table, C), loglik)

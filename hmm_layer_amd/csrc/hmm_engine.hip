@@ -3031,6 +3031,7 @@ __global__ __launch_bounds__(256) void k_loglik_partials(const double *__restric
 #include "hmm_scan_rows.inc"
 #include "hmm_scan_mid.inc"
 #include "hmm_seqshard_mid.inc"
+#include "hmm_wideq.inc"
 
 // ---- the router: which path serves (op, k, b, L, q), the plans that path needs, the workspace it takes.  Every entry
 // point below and hmm_workspace_bytes go through it, so they cannot disagree.

@@ -151,6 +151,18 @@ DECODE_MID_SIGNATURES = {
     "hmm_posterior_decode_mid": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _P, _I, _P, _P, _P, _P, _SZ, _P]),
 }
 
+# ... and those of the per-sequence walk for 65..256 states (hmm_posterior_walk, hmm_posterior_decode_wide), in a table
+# of their own for the same reason.
+POSTERIOR_WALK_SIGNATURES = {
+    "hmm_posterior_walk_min_states": (_I, []),
+    "hmm_posterior_walk_max_states": (_I, []),
+    "hmm_posterior_walk_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "hmm_posterior_walk_pays": (_I, [_I, _I, _I, _I]),
+    "hmm_posterior_walk": (_I, _POSTERIOR),
+    "hmm_posterior_decode_wide_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "hmm_posterior_decode_wide": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _P, _I, _P, _P, _P, _P, _SZ, _P]),
+}
+
 
 def lib():
     """The loaded shared library (loaded once).  Raises if it has not been built."""
@@ -162,7 +174,8 @@ def lib():
             "HIP engine library %s is missing: build it with `python -m hmm_layer_amd.build` "
             "(there is no CPU fallback)" % LIB_PATH)
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**_SIGNATURES, **DECODE_SIGNATURES, **DECODE_MID_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**_SIGNATURES, **DECODE_SIGNATURES, **DECODE_MID_SIGNATURES,
+                                      **POSTERIOR_WALK_SIGNATURES}.items():
         if not hasattr(L, name):
             raise EngineError("the engine library %s does not export %s: rebuild it with "
                               "`python -m hmm_layer_amd.build`" % (LIB_PATH, name))
@@ -442,6 +455,28 @@ def posterior(A, pi, E, mode=POST_PROB, eps=EPS, out=None, profile=None):
     return out, ll
 
 
+def posterior_walk(A, pi, E, mode=POST_LOG, eps=EPS):
+    """-> (posterior (k,b,L,q) fp32 per `mode`, loglik (k,b) fp64) by the per-sequence walk for 65..256 states
+    (hmm_posterior_walk): one workgroup per sequence with the cell's exact step, the sparse step for models whose
+    states have at most 8 predecessors and successors apart from two hubs.  posterior() keeps its per-position GEMMs
+    in this range; the two agree to rounding order.  Raises ValueError outside 65..256 states."""
+    lo, hi = lib().hmm_posterior_walk_min_states(), lib().hmm_posterior_walk_max_states()
+    if torch.is_tensor(E) and E.dim() == 4 and not lo <= E.shape[3] <= hi:     # (before the device is asked for)
+        raise ValueError("posterior_walk serves %d..%d states, got q = %d" % (lo, hi, E.shape[3]))
+    if int(mode) not in (POST_PROB, POST_LOG, POST_LOG_NO_LL):
+        raise ValueError("unknown mode %r" % (mode,))
+    A, pi, E = _dev(A, "A"), _dev(pi, "pi"), _dev(E, "E")
+    A, pi, dims = _shapes(A, E, pi)
+    with torch.cuda.device(E.device):
+        ws = _workspace(E.device, lib().hmm_posterior_walk_workspace_bytes(*dims), WALK_TAG)
+        out = torch.empty_like(E)
+        ll = torch.empty(dims[:2], dtype=torch.float64, device=E.device)
+        _check(lib().hmm_posterior_walk(A.data_ptr(), pi.data_ptr(), E.data_ptr(), *dims, eps, int(mode),
+                                        out.data_ptr(), ll.data_ptr(), ws.data_ptr(), ws.numel(), _stream(E.device)))
+    return out, ll
+
+
+WALK_TAG = "posterior_walk"          # posterior_walk()'s workspace
 DECODE_TAG = "posterior_decode"      # posterior_decode()'s workspace: its routing records survive a posterior() call
 
 
@@ -472,22 +507,31 @@ def decode_posterior(gamma, table, C):
     return gamma.argmax(dim=-1).to(torch.uint8), gamma.max(dim=-1).values
 
 
-def posterior_decode(A, pi, E, state_class=None, num_classes=None, eps=EPS, want_conf=True):
+def posterior_decode(A, pi, E, state_class=None, num_classes=None, eps=EPS, want_conf=True, sparse=False):
     """Posterior decoding -> (label (k,b,L) uint8, conf (k,b,L) fp32 or None, loglik (k,b) fp64): per position the
     class with the largest posterior (the sum of the state posteriors of its states; the lowest class on ties) and
     that posterior.  Up to 64 states the engine's kernels produce the labels themselves and the (k,b,L,q) tensor is
     never written (hmm_posterior_decode up to 16 states, hmm_posterior_decode_mid for 17..64 with the identity map or
     at most 16 classes; the latter's workspace holds a parking region as large as that tensor, see the header).
-    Everything else — more than 64 states, or more than 16 classes above 16 states — composes posterior(POST_PROB)
-    with torch ops (same shapes, dtypes and tie rule); the number of classes is then limited to 256, the range of a
-    label.  The fused call's workspace is cached per (device, stream) like every workspace of this module; for 17..64
-    states it is as large as the posterior tensor and stays allocated until release_workspaces()."""
+    For 65..256 states, with the identity map or at most 16 classes, the per-sequence walk does the same
+    (hmm_posterior_decode_wide, same parking region) where hmm_posterior_walk_pays says that it measured faster than
+    the composition, for models of up to 128 states and, with `sparse=True`, up to 256: `sparse` is the caller's
+    statement that every state of A has at most 8 non-zero predecessors and successors apart from two hubs (the gene
+    models), so that the walk takes its sparse step — its dense step above 128 states is slow.
+    Everything else — more than 256 states, more than 16 classes above 16 states, a shape where the walk does not
+    pay — composes posterior(POST_PROB) with torch ops (same shapes, dtypes and tie rule); the number of classes is
+    then limited to 256, the range of a label.  The fused call's workspace is cached per (device, stream) like every
+    workspace of this module; above 16 states it is as large as the posterior tensor and stays allocated until
+    release_workspaces()."""
     A, pi, E = _dev(A, "A"), _dev(pi, "pi"), _dev(E, "E")
     A, pi, dims = _shapes(A, E, pi)
     q = dims[3]
     table, C = class_table(state_class, num_classes, q)
     small = q <= lib().hmm_posterior_decode_max_states()
-    if not small and (q > lib().hmm_posterior_decode_mid_max_states() or (table is not None and C > 16)):
+    mid = not small and q <= lib().hmm_posterior_decode_mid_max_states()
+    wide = (lib().hmm_posterior_walk_min_states() <= q <= lib().hmm_posterior_walk_max_states()
+            and (q <= 128 or sparse) and lib().hmm_posterior_walk_pays(*dims) == 1)
+    if not small and (not (mid or wide) or (table is not None and C > 16)):
         if C > 256:
             raise ValueError("labels are bytes: at most 256 classes, got %d" % C)
         gamma, ll = posterior(A, pi, E, POST_PROB, eps)
@@ -496,8 +540,10 @@ def posterior_decode(A, pi, E, state_class=None, num_classes=None, eps=EPS, want
     if small and C > 16:
         raise ValueError("at most 16 classes, got %d" % C)
     nbytes = (lib().hmm_workspace_bytes(OP_POSTERIOR, *dims) if small
-              else lib().hmm_posterior_decode_mid_workspace_bytes(*dims))
-    call = lib().hmm_posterior_decode if small else lib().hmm_posterior_decode_mid
+              else lib().hmm_posterior_decode_mid_workspace_bytes(*dims) if mid
+              else lib().hmm_posterior_decode_wide_workspace_bytes(*dims))
+    call = (lib().hmm_posterior_decode if small else lib().hmm_posterior_decode_mid if mid
+            else lib().hmm_posterior_decode_wide)
     with torch.cuda.device(E.device):
         ws = _workspace(E.device, nbytes, DECODE_TAG)
         label = torch.empty(dims[:3], dtype=torch.uint8, device=E.device)

@@ -306,7 +306,7 @@ int hmm_posterior_decode(const float *A, const float *pi, const float *E,
  * Argument checks, before any HIP call, in this order: shape (HMM_ERR_BAD_SHAPE), q < 17 or q > 64
  * (HMM_ERR_Q_UNSUPPORTED), NULL among A, pi, E, label, workspace (HMM_ERR_NULL_POINTER), the class table as for
  * hmm_posterior_decode (HMM_ERR_BAD_ARGUMENT), workspace too small or not 256-byte aligned (HMM_ERR_WORKSPACE).
- * Fused decode above 64 states and sequence-sharded decode are follow-ups.
+ * 65..256 states: hmm_posterior_decode_wide below.  Sequence-sharded decode is a follow-up.
  */
 int hmm_posterior_decode_mid_max_states(void);
 size_t hmm_posterior_decode_mid_workspace_bytes(int k, int b, int L, int q);
@@ -315,6 +315,77 @@ int hmm_posterior_decode_mid(const float *A, const float *pi, const float *E,
                              const int *state_class, int num_classes,
                              unsigned char *label, float *conf, double *loglik,
                              void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Posteriors and fused posterior decoding for hmm_posterior_walk_min_states() (65) <= q <=
+ * hmm_posterior_walk_max_states() (256) states by a PER-SEQUENCE WALK (hmm_wideq.inc): the gene models of 5 to 18
+ * copies (71 .. 253 states) and any learned A of that range.  hmm_posterior evaluates this range with one GEMM launch
+ * per position and direction; here one workgroup walks one sequence, serial in time, with the cell's exact step: the
+ * clamp semantics are those of hmm_posterior (max(E, eps), max(pi, eps), the forward clamp of the predicted mixture,
+ * the backward max(A r, eps), normaliser logs accumulated in fp64, zero entries of A exact zeros).  There is no
+ * certificate and no routing; hmm_exact_count has nothing to report for these calls.  The results agree with
+ * hmm_posterior's to rounding order only: no bit-identity is promised across the two evaluations.
+ *
+ * hmm_posterior_walk: arguments, the three HMM_POST_* modes and outputs (out (k,b,L,q), loglik (k,b) fp64 or NULL)
+ * as hmm_posterior.  The two halves of the workgroup walk from both ends and PARK their vectors in `out` until they
+ * meet at ceil(L/2); every element of `out` is overwritten.  Workspace: hmm_posterior_walk_workspace_bytes (0:
+ * unsupported shape); it has no part that grows with L.
+ *
+ * Step selection, per model, on the device (no host round trip):
+ *   sparse        every state has at most 8 non-zero predecessors and at most 8 non-zero successors, except at most
+ *                 2 HUB states of any degree (the intergenic state of a c-copy gene model has c + 1 of each: 19 at 18
+ *                 copies).  A state's sum runs over its list in increasing source index, four products then four; a
+ *                 hub's sum over ALL states is formed by the whole workgroup half (products summed within each wave
+ *                 of 64 states, then the waves in increasing order).
+ *   dense, <=128  the row / column of A in registers: four partial sums over the states i = 0, 1, 2, 3 (mod 4) in
+ *                 increasing index, added as (s0 + s1) + (s2 + s3).
+ *   dense, >128   the same sums with A read from memory at every position: SLOW (q loads per state and position),
+ *                 and correct.  It is what a model of 129..256 states outside the sparse rule gets; nothing else is
+ *                 substituted for it.  hmm_posterior's GEMMs are the faster evaluation for such a model.
+ * HMM_OPT_FORCE_DENSE = 1 forces the dense step.  Normalisers and the row sums of gamma are sums within each wave of
+ * 64 states, then over the waves in increasing order.
+ *
+ * hmm_posterior_decode_wide: arguments and outputs as hmm_posterior_decode_mid (state_class HOST pointer or NULL,
+ * num_classes 1..16 with a table, q with the identity map; label (k,b,L) bytes, conf and loglik or NULL).  The class
+ * table reaches the kernels by value (sixteen 256-bit membership masks), so a captured graph keeps its table.  The
+ * class posterior is the fp32 sum of the gamma row over ALL states in increasing index with weights 0 / 1 (the bits of
+ * adding the members alone); classes are compared in increasing index with a strict >.  With the identity map nothing
+ * is summed: conf is bit for bit the largest entry of hmm_posterior_walk(HMM_POST_PROB)'s row and label its lowest
+ * index.  loglik is bit for bit hmm_posterior_walk's in every mode.
+ * Workspace: hmm_posterior_decode_wide_workspace_bytes = the walk's workspace rounded up to 256 bytes, then a PARKING
+ * REGION of k*b*L*q floats, addressed like `out`, where the walk parks what hmm_posterior_walk parks in `out` (the
+ * same stated contract as hmm_posterior_decode_mid; bounding it by checkpoints is a follow-up).
+ *
+ * hmm_posterior_walk_pays(k, b, L, q): 1 where the fused decode measured at least 1.25x faster than hmm_posterior
+ * followed by a reduction over the (k,b,L,q) tensor (DESIGN, "Decoded output, 65-256 states"), 0 elsewhere and where
+ * nothing was measured.  As measured on one MI355X (L = 10 000; 1, 32 and 1024 sequences; the sparse step at 71, 127
+ * and 253 states, the dense step at 96 and 128): 1 for k*b <= 1024 sequences, 0 above, whatever L.  The dense step above
+ * 128 states was not measured: send only models that take the sparse step there.
+ * hmm_layer_amd.engine.posterior_decode asks it; the entry points run wherever they are called.
+ *
+ * Memory contract: every element of out, label and conf is written; nothing is read from the workspace before the
+ * call has written it; label starts at an arbitrary byte offset; every offset into E, out, label, conf and the parking
+ * region is 64-bit.  Both calls run on `stream` alone with no helper stream and no host synchronisation (capturable);
+ * no atomics in the outputs; repeated calls are bit-identical.
+ * Argument checks, before any HIP call, in this order: shape (HMM_ERR_BAD_SHAPE), q < 65 or q > 256
+ * (HMM_ERR_Q_UNSUPPORTED), NULL among A, pi, E, out / label, workspace (HMM_ERR_NULL_POINTER), the mode, respectively
+ * the class table as for hmm_posterior_decode_mid (HMM_ERR_BAD_ARGUMENT), workspace too small or not 256-byte aligned
+ * (HMM_ERR_WORKSPACE).
+ */
+int hmm_posterior_walk_min_states(void);
+int hmm_posterior_walk_max_states(void);
+size_t hmm_posterior_walk_workspace_bytes(int k, int b, int L, int q);
+int hmm_posterior_walk_pays(int k, int b, int L, int q);
+int hmm_posterior_walk(const float *A, const float *pi, const float *E,
+                       int k, int b, int L, int q, float eps, int mode,
+                       float *out, double *loglik,
+                       void *workspace, size_t workspace_bytes, void *stream);
+size_t hmm_posterior_decode_wide_workspace_bytes(int k, int b, int L, int q);
+int hmm_posterior_decode_wide(const float *A, const float *pi, const float *E,
+                              int k, int b, int L, int q, float eps,
+                              const int *state_class, int num_classes,
+                              unsigned char *label, float *conf, double *loglik,
+                              void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Viterbi state paths (max-plus scan).  The reference has none (only a docstring mention,
