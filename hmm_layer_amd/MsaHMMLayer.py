@@ -177,7 +177,7 @@ def _loglik_impl(inputs, cell, end_hints=None, training=False):
         A, pi, E = _engine_inputs(inputs, cell, end_hints, training)
         return engine.forward(A, pi, E, want_log_alpha=False, eps=cell.epsilon)[1]
     A, pi, E = _graph_inputs(inputs, cell, end_hints, training)
-    return autograd.loglik(A, pi, E, eps=cell.epsilon)
+    return autograd.loglik(A, pi, E, eps=cell.epsilon, support_only=getattr(cell.transitioner, "support_grad", False))
 
 
 class MsaHmmLayer(nn.Module):

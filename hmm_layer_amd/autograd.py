@@ -31,8 +31,42 @@ class LogLikelihood(torch.autograd.Function):
                 dE if need[2] else None, None)
 
 
-def loglik(A, pi, E, eps=engine.EPS):
-    """Differentiable (k,b) fp64 log-likelihoods."""
+class SupportLogLikelihood(torch.autograd.Function):
+    """LogLikelihood for 65..256 states through the per-sequence walk with the sparse step (hmm_loglik_grad_walk):
+    forward = its log-likelihood form, which checks once that no model was refused; backward = the walk on the same A.
+    The gradient for A is exactly 0 wherever A == 0 and LogLikelihood's elsewhere."""
+
+    @staticmethod
+    def forward(ctx, A, pi, E, eps):
+        A, pi, E = A.contiguous(), pi.contiguous(), E.contiguous()
+        ctx.save_for_backward(A, pi, E)
+        ctx.eps = eps
+        return engine.loglik_grad_walk(A, pi, E, eps=eps, want_grads=False, check=True)[3]
+
+    @staticmethod
+    def backward(ctx, grad_loglik):
+        A, pi, E = ctx.saved_tensors
+        dA, dpi, dE, _ = engine.loglik_grad_walk(A, pi, E, grad_loglik.to(torch.float32).contiguous(), eps=ctx.eps,
+                                                 check=False)
+        need = ctx.needs_input_grad
+        return (dA if need[0] else None, dpi.reshape(pi.shape) if need[1] else None,
+                dE if need[2] else None, None)
+
+
+def loglik(A, pi, E, eps=engine.EPS, support_only=False):
+    """Differentiable (k,b) fp64 log-likelihoods.  support_only: False, today's path; True, for 65..256 states where
+    hmm_loglik_grad_walk_pays says 1, the walk with the sparse step, whose gradient for A is exactly 0 wherever
+    A == 0 (sound where A is scattered from per-edge parameters, as the gene transitioners do; not what a leaf A
+    holding exact zeros gets from the default); "always", the same without asking the predicate.  Ignored outside
+    65..256 states."""
+    if support_only not in (False, True, "always"):
+        raise ValueError("support_only must be False, True or \"always\", got %r" % (support_only,))
+    if support_only:
+        L = engine.lib()
+        q = E.shape[-1]
+        if L.hmm_loglik_grad_walk_min_states() <= q <= L.hmm_loglik_grad_walk_max_states() and (
+                support_only == "always" or L.hmm_loglik_grad_walk_pays(*E.shape) == 1):
+            return SupportLogLikelihood.apply(A, pi, E, eps)
     return LogLikelihood.apply(A, pi, E, eps)
 
 

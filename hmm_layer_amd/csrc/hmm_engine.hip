@@ -3505,4 +3505,5 @@ int hmm_loglik_partials(const double *loglik, const float *weights, int k, int b
 #include "hmm_grad_scan.inc"
 #include "hmm_postgrad_scan.inc"
 #include "hmm_grad_large.inc"
+#include "hmm_gradwq.inc"
 #include "hmm_postgrad_large.inc"

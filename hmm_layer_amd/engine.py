@@ -163,6 +163,17 @@ POSTERIOR_WALK_SIGNATURES = {
     "hmm_posterior_decode_wide": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _P, _I, _P, _P, _P, _P, _SZ, _P]),
 }
 
+# ... and those of the training walk for 65..256 states (hmm_loglik_grad_walk), in a table of their own for the same
+# reason.
+LOGLIK_GRAD_WALK_SIGNATURES = {
+    "hmm_loglik_grad_walk_min_states": (_I, []),
+    "hmm_loglik_grad_walk_max_states": (_I, []),
+    "hmm_loglik_grad_walk_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "hmm_loglik_grad_walk_pays": (_I, [_I, _I, _I, _I]),
+    "hmm_loglik_grad_walk_refused": (_LL, _LAST_CALL),
+    "hmm_loglik_grad_walk": (_I, _LOGLIK_GRAD),
+}
+
 
 def lib():
     """The loaded shared library (loaded once).  Raises if it has not been built."""
@@ -175,7 +186,7 @@ def lib():
             "(there is no CPU fallback)" % LIB_PATH)
     L = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**_SIGNATURES, **DECODE_SIGNATURES, **DECODE_MID_SIGNATURES,
-                                      **POSTERIOR_WALK_SIGNATURES}.items():
+                                      **POSTERIOR_WALK_SIGNATURES, **LOGLIK_GRAD_WALK_SIGNATURES}.items():
         if not hasattr(L, name):
             raise EngineError("the engine library %s does not export %s: rebuild it with "
                               "`python -m hmm_layer_amd.build`" % (LIB_PATH, name))
@@ -1084,6 +1095,52 @@ def loglik_grad_large(A, pi, E, grad_loglik=None, eps=EPS):
     """loglik_grad() through hmm_loglik_grad_large, for any 1 <= q <= 4096 (same arguments, results and
     semantics; the walk / GEMM evaluation is chosen by q or by OPT_GLARGE)."""
     return _loglik_grad("loglik_grad_large", "hmm_loglik_grad_large_max_states", A, pi, E, grad_loglik, eps)
+
+
+GRAD_WALK_TAG = "loglik_grad_walk"   # loglik_grad_walk()'s workspace: loglik_grad_walk_refused() reads its counter
+
+
+def loglik_grad_walk(A, pi, E, grad_loglik=None, eps=EPS, want_grads=True, check=True):
+    """-> (dA, dpi, dE, loglik (k,b) fp64) by the per-sequence walk with the sparse step for 65..256 states
+    (hmm_loglik_grad_walk), or (None, None, None, loglik) with want_grads=False: the log-likelihood alone, bit for bit
+    the gradient call's.  dE and dpi are loglik_grad_large()'s; dA holds the same derivative wherever A != 0 and an
+    exact 0 wherever A == 0 (a matrix scattered from per-edge parameters never reads those).  A model with more than
+    two states above degree 8 is refused on the device (NaN in all its outputs): with check=True the call reads the
+    refusal counter (one synchronisation) and raises EngineError.  Raises ValueError outside 65..256 states."""
+    lo, hi = lib().hmm_loglik_grad_walk_min_states(), lib().hmm_loglik_grad_walk_max_states()
+    if torch.is_tensor(E) and E.dim() == 4 and not lo <= E.shape[3] <= hi:     # (before the device is asked for)
+        raise ValueError("loglik_grad_walk serves %d..%d states, got q = %d" % (lo, hi, E.shape[3]))
+    A, pi, E = _dev(A, "A"), _dev(pi, "pi"), _dev(E, "E")
+    A, pi, dims = _shapes(A, E, pi)
+    k, b, L, q = dims
+    if grad_loglik is not None:
+        grad_loglik = _dev(grad_loglik, "grad_loglik")
+        if tuple(grad_loglik.shape) != (k, b):
+            raise ValueError("grad_loglik must have shape %s" % ((k, b),))
+    with torch.cuda.device(E.device):
+        ws = _workspace(E.device, lib().hmm_loglik_grad_walk_workspace_bytes(*dims), GRAD_WALK_TAG)
+        dA = dpi = dE = None
+        if want_grads:
+            dA = torch.empty((k, q, q), dtype=torch.float32, device=E.device)
+            dpi = torch.empty((k, q), dtype=torch.float32, device=E.device)
+            dE = torch.empty_like(E)
+        ll = torch.empty((k, b), dtype=torch.float64, device=E.device)
+        _check(lib().hmm_loglik_grad_walk(A.data_ptr(), pi.data_ptr(), E.data_ptr(), *dims, eps,
+                                          grad_loglik.data_ptr() if grad_loglik is not None else None,
+                                          *(t.data_ptr() if t is not None else None for t in (dA, dpi, dE)),
+                                          ll.data_ptr(), ws.data_ptr(), ws.numel(), _stream(E.device)))
+        if check:
+            n = loglik_grad_walk_refused(dims, E.device)
+            if n:
+                raise EngineError("loglik_grad_walk: %d of %d models have more than two states above degree 8 and "
+                                  "were refused (their outputs are NaN)" % (n, k))
+    return dA, dpi, dE, ll
+
+
+def loglik_grad_walk_refused(dims, device=None):
+    """How many of the k models of the LAST loglik_grad_walk call with shape `dims` on this device and stream were
+    refused (synchronises)."""
+    return posterior_grad_serial_count(dims, device, _fn="hmm_loglik_grad_walk_refused", _tag=GRAD_WALK_TAG)
 
 
 def _posterior_grad(name, A, pi, E, grad_out, mode, eps):

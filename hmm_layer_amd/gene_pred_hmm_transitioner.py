@@ -214,12 +214,18 @@ class GenePredHMMTransitioner(SimpleGenePredHMMTransitioner):
 
 
 class GenePredMultiHMMTransitioner(GenePredHMMTransitioner):
-    """k copies of the 14 gene states sharing one intergenic state: 1 + 14k states, 1 + 22k edges."""
+    """k copies of the 14 gene states sharing one intergenic state: 1 + 14k states, 1 + 22k edges.
 
-    def __init__(self, k=1, init_component_sd=0.2, **kwargs):
+    support_grad=True lets the layer's log-likelihood train through the per-sequence walk with the sparse step
+    (autograd.loglik(support_only=True): 65..256 states, where hmm_loglik_grad_walk_pays says so), whose gradient for
+    A is exactly 0 on absent edges; dense_transition_matrix multiplies those entries' gradients by its mask, so the
+    parameters' gradients do not depend on them."""
+
+    def __init__(self, k=1, init_component_sd=0.2, support_grad=False, **kwargs):
         self.k = k
         self.num_states = 1 + 14 * k
         self.init_component_sd = init_component_sd
+        self.support_grad = support_grad
         super().__init__(**kwargs)
         self.init = self.make_transition_init(k, init_component_sd)
 
@@ -240,7 +246,7 @@ class GenePredMultiHMMTransitioner(GenePredHMMTransitioner):
 
     def get_config(self):
         config = super().get_config()
-        config.update({"k": self.k})
+        config.update({"k": self.k, "support_grad": self.support_grad})
         return config
 
 

@@ -1042,6 +1042,45 @@ int hmm_loglik_grad_large(const float *A, const float *pi, const float *E,
                           void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * Log-likelihoods and their gradient for hmm_loglik_grad_walk_min_states() (65) <= q <=
+ * hmm_loglik_grad_walk_max_states() (256) states by a PER-SEQUENCE WALK WITH THE SPARSE STEP (hmm_gradwq.inc): the
+ * training counterpart of hmm_posterior_walk for the gene models of 5 to 18 copies.  One workgroup per sequence,
+ * lane = state, two launches (forward sweep, backward sweep), the step of hmm_posterior_walk's sparse form: every
+ * state has at most 8 non-zero predecessors and successors except at most two hub states, decided per model on the
+ * device.  Derivatives and clamp handling are exactly those of hmm_loglik_grad_large (position 0 included), with
+ * ONE DIFFERENCE IN dA: every entry with A[i][j] == 0 is written as an exact 0, where hmm_loglik_grad* return the
+ * derivative that autograd through a dense A would give.  Every entry with A[i][j] != 0 gets the same derivative
+ * as there.  A transition matrix scattered from per-edge parameters never reads the absent entries.
+ *   grad_loglik  (k,b) or NULL (= ones).
+ *   dA, dpi, dE  all three, or all three NULL: then the call is the LOG-LIKELIHOOD ALONE (forward sweep only, no
+ *                write to any gradient) and loglik is required.  loglik is bit for bit the same in both forms.
+ *   loglik       (k,b) fp64 or NULL (with gradients).
+ * A MODEL OUTSIDE THE SPARSE RULE (more than two states above degree 8) IS REFUSED ON THE DEVICE: every element of
+ * its dA, dpi, dE rows and loglik is NaN, the other models of the call are served, and
+ * hmm_loglik_grad_walk_refused(k, b, L, q, workspace, workspace_bytes) copies from the FINISHED call's workspace how
+ * many of the k models were refused (it synchronises; negative: an HMM_ERR_* code).  HMM_OPT_FORCE_DENSE does not
+ * act on this call.
+ * Workspace: hmm_loglik_grad_walk_workspace_bytes (0: unsupported shape or q); it does not grow with L.  Sums run
+ * in a fixed order (fp32 within a sequence, fp64 across sequences, normaliser logs in fp64): repeated calls return
+ * bit-identical results.  Everything runs in order on `stream`, without host synchronisation: capturable.
+ * Argument checks, before any HIP call and in this order: bad shape -1; q < 65 or q > 256 -2; a NULL A / pi / E /
+ * workspace, one or two of dA / dpi / dE, or neither gradients nor loglik -3; a small or misaligned (256 bytes)
+ * workspace -4.
+ * hmm_loglik_grad_walk_pays(k, b, L, q): 1 only where tools/experiments/loglik_grad_walk_time.py measured this call
+ * at least 1.25x faster than hmm_loglik_grad_large at its default route; 0 elsewhere, outside the range and wherever
+ * nothing was measured.
+ */
+int hmm_loglik_grad_walk_min_states(void);
+int hmm_loglik_grad_walk_max_states(void);
+size_t hmm_loglik_grad_walk_workspace_bytes(int k, int b, int L, int q);
+int hmm_loglik_grad_walk_pays(int k, int b, int L, int q);
+long long hmm_loglik_grad_walk_refused(int k, int b, int L, int q, const void *workspace, size_t workspace_bytes);
+int hmm_loglik_grad_walk(const float *A, const float *pi, const float *E,
+                         int k, int b, int L, int q, float eps, const float *grad_loglik,
+                         float *dA, float *dpi, float *dE, double *loglik,
+                         void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Gradient of a loss on the state posteriors (training through state_posterior_log_probs).  The
  * reference differentiates _state_posterior_log_probs_impl by autograd through its Python loops
  * (hmm_layer/MsaHMMLayer.py:422-521 called with training=True, tests/parallel_rnn_forward.py:70-80);
