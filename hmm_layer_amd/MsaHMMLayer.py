@@ -80,7 +80,9 @@ def _state_posterior_log_probs_impl(inputs, cell, reverse_cell=None, bidirection
         # autograd node, analytic backward (hmm_posterior_grad)
         A, pi, E = _graph_inputs(inputs, cell, end_hints, training, what="posterior")
         mode = engine.POST_LOG_NO_LL if no_loglik else engine.POST_LOG
-        return _with_prior(cell, autograd.posterior(A, pi, E, mode=mode, eps=cell.epsilon), return_prior)
+        support = getattr(cell.transitioner, "support_grad", False)
+        return _with_prior(cell, autograd.posterior(A, pi, E, mode=mode, eps=cell.epsilon, support_only=support),
+                           return_prior)
     A, pi, E = _engine_inputs(inputs, cell, end_hints, training)
     mode = engine.POST_LOG_NO_LL if no_loglik else engine.POST_LOG
     post, _ = engine.posterior(A, pi, E, mode=mode, eps=cell.epsilon)
@@ -240,7 +242,8 @@ class MsaHmmLayer(nn.Module):
         output, without the exp/log round trip."""
         if _wants_grad(inputs, self.cell):                  # differentiable, like state_posterior_log_probs
             A, pi, E = _graph_inputs(inputs, self.cell, end_hints, training, what="posterior")
-            probs = autograd.posterior(A, pi, E, mode=engine.POST_PROB, eps=self.cell.epsilon)
+            probs = autograd.posterior(A, pi, E, mode=engine.POST_PROB, eps=self.cell.epsilon,
+                                       support_only=getattr(self.cell.transitioner, "support_grad", False))
             return probs, autograd.loglik(A, pi, E, eps=self.cell.epsilon)
         A, pi, E = _engine_inputs(inputs, self.cell, end_hints, training)
         return engine.posterior(A, pi, E, mode=engine.POST_PROB, eps=self.cell.epsilon)

@@ -5,6 +5,12 @@ The reference trains by letting autograd unroll the Python time loop
 every step's tensors alive.  Here the graph holds ONE node: forward = hmm_forward (log-likelihood
 only, reads E once), backward = hmm_loglik_grad (hmm_loglik_grad_large above 64 states: one
 forward-backward pass producing dA, dpi and dE = w * gamma / E).  Nothing per position is saved between the two.
+
+posterior() is the same for a loss on the state posteriors (Posterior: hmm_posterior forward, hmm_posterior_grad /
+hmm_posterior_grad_large backward).  For 65..256 states both have an opt-in node on the per-sequence walks with the
+sparse step, whose gradient for A is defined on the support of A: loglik(support_only=...) -> SupportLogLikelihood
+(hmm_loglik_grad_walk), posterior(support_only=...) -> SupportPosterior (hmm_posterior_walk forward,
+hmm_posterior_grad_walk backward).
 """
 import torch
 
@@ -104,8 +110,48 @@ class Posterior(torch.autograd.Function):
         return (dA if need[0] else None, dpi.reshape(pi.shape) if need[1] else None, dE if need[2] else None, None, None)
 
 
-def posterior(A, pi, E, mode=engine.POST_LOG, eps=engine.EPS):
-    """Differentiable state posteriors; mode engine.POST_PROB, POST_LOG or POST_LOG_NO_LL."""
+class SupportPosterior(torch.autograd.Function):
+    """Posterior for 65..256 states through the per-sequence walks with the sparse step: forward =
+    hmm_posterior_walk (the walk, not hmm_posterior's per-position GEMMs: the two agree to rounding order only),
+    backward = hmm_posterior_grad_walk, which checks that no model was refused.  POST_LOG_NO_LL adds
+    hmm_loglik_grad_walk weighted by the per-sequence sum of the upstream gradient, as Posterior composes it.  The
+    gradient for A is exactly 0 wherever A == 0 and Posterior's elsewhere."""
+
+    @staticmethod
+    def forward(ctx, A, pi, E, mode, eps):
+        A, pi, E = A.contiguous(), pi.contiguous(), E.contiguous()
+        ctx.save_for_backward(A, pi, E)
+        ctx.mode, ctx.eps = int(mode), eps
+        return engine.posterior_walk(A, pi, E, mode=mode, eps=eps)[0]
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        A, pi, E = ctx.saved_tensors
+        grad_out = grad_out.to(torch.float32).contiguous()
+        if ctx.mode == engine.POST_LOG_NO_LL:
+            dA, dpi, dE = engine.posterior_grad_walk(A, pi, E, grad_out, mode=engine.POST_LOG, eps=ctx.eps, check=True)
+            w = grad_out.sum(dim=(2, 3)).contiguous()
+            dA2, dpi2, dE2, _ = engine.loglik_grad_walk(A, pi, E, w, eps=ctx.eps, check=False)
+            dA, dpi, dE = dA + dA2, dpi + dpi2, dE.add_(dE2)
+        else:
+            dA, dpi, dE = engine.posterior_grad_walk(A, pi, E, grad_out, mode=ctx.mode, eps=ctx.eps, check=True)
+        need = ctx.needs_input_grad
+        return (dA if need[0] else None, dpi.reshape(pi.shape) if need[1] else None, dE if need[2] else None, None, None)
+
+
+def posterior(A, pi, E, mode=engine.POST_LOG, eps=engine.EPS, support_only=False):
+    """Differentiable state posteriors; mode engine.POST_PROB, POST_LOG or POST_LOG_NO_LL.  support_only has the
+    meaning it has in loglik(): False, today's path; True, for 65..256 states where hmm_posterior_grad_walk_pays says
+    1, the walks with the sparse step (SupportPosterior), whose gradient for A is exactly 0 wherever A == 0; "always",
+    the same without asking the predicate.  Ignored outside 65..256 states."""
+    if support_only not in (False, True, "always"):
+        raise ValueError("support_only must be False, True or \"always\", got %r" % (support_only,))
+    if support_only:
+        L = engine.lib()
+        q = E.shape[-1]
+        if L.hmm_posterior_grad_walk_min_states() <= q <= L.hmm_posterior_grad_walk_max_states() and (
+                support_only == "always" or L.hmm_posterior_grad_walk_pays(*E.shape) == 1):
+            return SupportPosterior.apply(A, pi, E, mode, eps)
     return Posterior.apply(A, pi, E, mode, eps)
 
 

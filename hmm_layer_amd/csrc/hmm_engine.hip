@@ -3507,3 +3507,4 @@ int hmm_loglik_partials(const double *loglik, const float *weights, int k, int b
 #include "hmm_grad_large.inc"
 #include "hmm_gradwq.inc"
 #include "hmm_postgrad_large.inc"
+#include "hmm_postgradwq.inc"

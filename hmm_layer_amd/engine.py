@@ -174,6 +174,16 @@ LOGLIK_GRAD_WALK_SIGNATURES = {
     "hmm_loglik_grad_walk": (_I, _LOGLIK_GRAD),
 }
 
+# ... and those of the posterior-gradient walk for 65..256 states (hmm_posterior_grad_walk), likewise.
+POSTERIOR_GRAD_WALK_SIGNATURES = {
+    "hmm_posterior_grad_walk_min_states": (_I, []),
+    "hmm_posterior_grad_walk_max_states": (_I, []),
+    "hmm_posterior_grad_walk_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "hmm_posterior_grad_walk_pays": (_I, [_I, _I, _I, _I]),
+    "hmm_posterior_grad_walk_refused": (_LL, _LAST_CALL),
+    "hmm_posterior_grad_walk": (_I, _POSTERIOR_GRAD),
+}
+
 
 def lib():
     """The loaded shared library (loaded once).  Raises if it has not been built."""
@@ -186,7 +196,8 @@ def lib():
             "(there is no CPU fallback)" % LIB_PATH)
     L = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**_SIGNATURES, **DECODE_SIGNATURES, **DECODE_MID_SIGNATURES,
-                                      **POSTERIOR_WALK_SIGNATURES, **LOGLIK_GRAD_WALK_SIGNATURES}.items():
+                                      **POSTERIOR_WALK_SIGNATURES, **LOGLIK_GRAD_WALK_SIGNATURES,
+                                      **POSTERIOR_GRAD_WALK_SIGNATURES}.items():
         if not hasattr(L, name):
             raise EngineError("the engine library %s does not export %s: rebuild it with "
                               "`python -m hmm_layer_amd.build`" % (LIB_PATH, name))
@@ -1195,3 +1206,45 @@ def posterior_grad_large(A, pi, E, grad_out, mode=POST_LOG, eps=EPS):
     semantics; the walk / GEMM evaluation is chosen by q or by OPT_GLARGE).  POST_LOG_NO_LL is not a mode of
     this call: the autograd node composes it with loglik_grad_large."""
     return _posterior_grad("posterior_grad_large", A, pi, E, grad_out, mode, eps)
+
+
+POSTGRAD_WALK_TAG = "posterior_grad_walk"   # posterior_grad_walk()'s workspace: posterior_grad_walk_refused() reads its counter
+
+
+def posterior_grad_walk(A, pi, E, grad_out, mode=POST_LOG, eps=EPS, check=True):
+    """posterior_grad() -> (dA, dpi, dE) by the per-sequence walk with the sparse step for 65..256 states
+    (hmm_posterior_grad_walk).  dE and dpi are posterior_grad_large()'s; dA holds the same derivative wherever A != 0
+    and an exact 0 wherever A == 0 (a matrix scattered from per-edge parameters never reads those).  A model with more
+    than two states above degree 8 is refused on the device (NaN in all its outputs): with check=True the call reads
+    the refusal counter (one synchronisation) and raises EngineError.  Raises ValueError outside 65..256 states and
+    for a mode other than POST_PROB / POST_LOG (POST_LOG_NO_LL is composed by the autograd node)."""
+    lo, hi = lib().hmm_posterior_grad_walk_min_states(), lib().hmm_posterior_grad_walk_max_states()
+    if torch.is_tensor(E) and E.dim() == 4 and not lo <= E.shape[3] <= hi:     # (before the device is asked for)
+        raise ValueError("posterior_grad_walk serves %d..%d states, got q = %d" % (lo, hi, E.shape[3]))
+    if int(mode) not in (POST_PROB, POST_LOG):
+        raise ValueError("posterior_grad_walk supports mode POST_PROB or POST_LOG")
+    A, pi, E, grad_out = _dev(A, "A"), _dev(pi, "pi"), _dev(E, "E"), _dev(grad_out, "grad_out")
+    A, pi, dims = _shapes(A, E, pi)
+    k, b, L, q = dims
+    if grad_out.shape != E.shape:
+        raise ValueError("grad_out must be shaped like E")
+    with torch.cuda.device(E.device):
+        ws = _workspace(E.device, lib().hmm_posterior_grad_walk_workspace_bytes(*dims), POSTGRAD_WALK_TAG)
+        dA = torch.empty((k, q, q), dtype=torch.float32, device=E.device)
+        dpi = torch.empty((k, q), dtype=torch.float32, device=E.device)
+        dE = torch.empty_like(E)
+        _check(lib().hmm_posterior_grad_walk(A.data_ptr(), pi.data_ptr(), E.data_ptr(), *dims, eps, int(mode),
+                                             grad_out.data_ptr(), dA.data_ptr(), dpi.data_ptr(), dE.data_ptr(),
+                                             ws.data_ptr(), ws.numel(), _stream(E.device)))
+        if check:
+            n = posterior_grad_walk_refused(dims, E.device)
+            if n:
+                raise EngineError("posterior_grad_walk: %d of %d models have more than two states above degree 8 and "
+                                  "were refused (their outputs are NaN)" % (n, k))
+    return dA, dpi, dE
+
+
+def posterior_grad_walk_refused(dims, device=None):
+    """How many of the k models of the LAST posterior_grad_walk call with shape `dims` on this device and stream were
+    refused (synchronises)."""
+    return posterior_grad_serial_count(dims, device, _fn="hmm_posterior_grad_walk_refused", _tag=POSTGRAD_WALK_TAG)

@@ -219,7 +219,10 @@ class GenePredMultiHMMTransitioner(GenePredHMMTransitioner):
     support_grad=True lets the layer's log-likelihood train through the per-sequence walk with the sparse step
     (autograd.loglik(support_only=True): 65..256 states, where hmm_loglik_grad_walk_pays says so), whose gradient for
     A is exactly 0 on absent edges; dense_transition_matrix multiplies those entries' gradients by its mask, so the
-    parameters' gradients do not depend on them."""
+    parameters' gradients do not depend on them.  The same flag sends the layer's differentiable posteriors
+    (state_posterior_log_probs(training=True), state_posterior_probs) through autograd.posterior(support_only=True):
+    hmm_posterior_walk forward and hmm_posterior_grad_walk backward where hmm_posterior_grad_walk_pays says so; the
+    forward then is the walk's evaluation, which agrees with the default one to rounding order."""
 
     def __init__(self, k=1, init_component_sd=0.2, support_grad=False, **kwargs):
         self.k = k

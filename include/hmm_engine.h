@@ -1186,6 +1186,44 @@ int hmm_posterior_grad_large(const float *A, const float *pi, const float *E,
                              float *dA, float *dpi, float *dE,
                              void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * The same gradient for hmm_posterior_grad_walk_min_states() (65) <= q <= hmm_posterior_grad_walk_max_states() (256)
+ * states by a PER-SEQUENCE WALK WITH THE SPARSE STEP (hmm_postgradwq.inc): the counterpart of hmm_loglik_grad_walk
+ * for a loss on the posteriors of the gene models of 5 to 18 copies.  One workgroup per sequence, lane = state, the
+ * four sweeps of hmm_posterior_grad_large as four launches with the step of hmm_posterior_walk's sparse form: every
+ * state has at most 8 non-zero predecessors and successors except at most two hub states, decided per model on the
+ * device.  Arguments, modes (HMM_POST_PROB, HMM_POST_LOG), derivatives and the handling of all four clamps are
+ * exactly those of hmm_posterior_grad_large, with ONE DIFFERENCE IN dA, that of hmm_loglik_grad_walk: every entry
+ * with A[i][j] == 0 is written as an exact 0; every entry with A[i][j] != 0 gets the derivative
+ * hmm_posterior_grad_large gives.
+ * A MODEL OUTSIDE THE SPARSE RULE (more than two states above degree 8) IS REFUSED ON THE DEVICE: every element of
+ * its dA, dpi and dE rows is NaN, the other models of the call are served, and
+ * hmm_posterior_grad_walk_refused(k, b, L, q, workspace, workspace_bytes) copies from the FINISHED call's workspace
+ * how many of the k models were refused (it synchronises; negative: an HMM_ERR_* code).  HMM_OPT_FORCE_DENSE does
+ * not act on this call.
+ * Workspace: hmm_posterior_grad_walk_workspace_bytes (0: unsupported shape or q), exactly what the call uses: two
+ * k*b*L*q float arrays (the value recursions with their clamp bits; the two shares of dE meet in the caller's dE,
+ * so there is no third) and per-sequence parts that do not grow with L.  No atomics; sums run in a fixed order
+ * (fp32 within a sequence, fp64 across sequences): repeated calls return bit-identical results, whatever the
+ * workspace held.  Every offset into E, grad_out, dE and the workspace arrays is 64-bit.  Everything runs in order
+ * on `stream`, without host synchronisation: capturable.
+ * Argument checks, before any HIP call and in this order: bad shape -1; q < 65 or q > 256 -2; mode not
+ * HMM_POST_PROB / HMM_POST_LOG -6; a NULL A / pi / E / grad_out / dA / dpi / dE / workspace -3; a small or misaligned
+ * (256 bytes) workspace -4.
+ * hmm_posterior_grad_walk_pays(k, b, L, q): 1 only where tools/experiments/posterior_grad_walk_time.py measured this
+ * call at least 1.25x faster than hmm_posterior_grad_large at its default route; 0 elsewhere, outside the range and
+ * wherever nothing was measured.
+ */
+int hmm_posterior_grad_walk_min_states(void);
+int hmm_posterior_grad_walk_max_states(void);
+size_t hmm_posterior_grad_walk_workspace_bytes(int k, int b, int L, int q);
+int hmm_posterior_grad_walk_pays(int k, int b, int L, int q);
+long long hmm_posterior_grad_walk_refused(int k, int b, int L, int q, const void *workspace, size_t workspace_bytes);
+int hmm_posterior_grad_walk(const float *A, const float *pi, const float *E,
+                            int k, int b, int L, int q, float eps, int mode, const float *grad_out,
+                            float *dA, float *dpi, float *dE,
+                            void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
