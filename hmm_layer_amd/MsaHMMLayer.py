@@ -260,7 +260,8 @@ class MsaHmmLayer(nn.Module):
         step-at-a-time posterior.  Inference only."""
         if _wants_grad(inputs, self.cell):
             raise ValueError("posterior_decode is inference only (labels carry no gradient): call it under "
-                             "torch.no_grad(), or train through state_posterior_log_probs")
+                             "torch.no_grad(), or train through class_posterior_log_probs / "
+                             "state_posterior_log_probs")
         A, pi, E = _engine_inputs(inputs, self.cell, end_hints, False)
         if E.is_cuda:
             sparse = isinstance(self.cell.transitioner, GenePredMultiHMMTransitioner)
@@ -268,6 +269,41 @@ class MsaHmmLayer(nn.Module):
         table, C = engine.class_table(state_class, num_classes, E.shape[-1])
         gamma, loglik = _posterior_probs_host(A, pi, E, self.cell.epsilon)
         return (*engine.decode_posterior(gamma, table, C), loglik)
+
+    def class_posterior_log_probs(self, inputs, state_class, num_classes=None, end_hints=None, training=False,
+                                  log=True):
+        """Class posteriors (k,b,L,C): per position the sum of the state posteriors of every class of `state_class` (a
+        sequence or an integer tensor of q classes), as logs (log=True; -inf for a class of posterior 0) or
+        probabilities — what a model labelled by class is trained on; the trainable counterpart of posterior_decode.
+        With gradients wanted: one autograd node on the per-sequence walks for 65..256 states and at most 16 classes
+        where the transitioner's support_grad asks for them (autograd.class_posterior: neither the (k,b,L,q) posterior
+        nor a gradient of that size is written), else state posteriors collapsed by torch ops.  Without gradients on a
+        HIP device the fused forward where posterior_decode would take its fused call for this model
+        (hmm_posterior_walk_pays, and above 128 states only a GenePredMultiHMMTransitioner), else engine.posterior
+        collapsed; elsewhere a step-at-a-time posterior collapsed."""
+        mode = engine.POST_LOG if log else engine.POST_PROB
+        if state_class is None:
+            raise ValueError("class_posterior_log_probs needs a class table (state_class)")
+        if _wants_grad(inputs, self.cell):
+            A, pi, E = _graph_inputs(inputs, self.cell, end_hints, training, what="posterior")
+            return autograd.class_posterior(A, pi, E, state_class, num_classes, mode=mode, eps=self.cell.epsilon,
+                                            support_only=getattr(self.cell.transitioner, "support_grad", False))
+        A, pi, E = _engine_inputs(inputs, self.cell, end_hints, training)
+        q = E.shape[-1]
+        table, C = engine.class_table(state_class, num_classes, q)
+        if E.is_cuda:
+            lib = engine.lib()
+            if (C <= 16 and lib.hmm_posterior_walk_min_states() <= q <= lib.hmm_posterior_walk_max_states()
+                    and lib.hmm_posterior_walk_pays(*E.shape) == 1
+                    and (q <= 128 or isinstance(self.cell.transitioner, GenePredMultiHMMTransitioner))):
+                prob, logp, _ = engine.class_posterior_walk(A, pi, E, table, C, eps=self.cell.epsilon, prob=not log,
+                                                            log=log)
+                return logp if log else prob
+            gamma = engine.posterior(A, pi, E, mode=engine.POST_PROB, eps=self.cell.epsilon)[0]
+        else:
+            gamma = _posterior_probs_host(A, pi, E, self.cell.epsilon)[0]
+        P = engine.collapse_posterior(gamma, table, C)
+        return torch.log(P) if log else P
 
     # -- likelihood aggregation -----------------------------------------------------------
     def apply_sequence_weights(self, loglik, indices, aggregate=False):

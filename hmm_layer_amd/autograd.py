@@ -10,7 +10,10 @@ posterior() is the same for a loss on the state posteriors (Posterior: hmm_poste
 hmm_posterior_grad_large backward).  For 65..256 states both have an opt-in node on the per-sequence walks with the
 sparse step, whose gradient for A is defined on the support of A: loglik(support_only=...) -> SupportLogLikelihood
 (hmm_loglik_grad_walk), posterior(support_only=...) -> SupportPosterior (hmm_posterior_walk forward,
-hmm_posterior_grad_walk backward).
+hmm_posterior_grad_walk backward).  class_posterior() is posterior() summed over the states of each class of a class
+table, as a model labelled by class is trained: composed from posterior() with torch ops, or, opt-in for 65..256
+states, the node ClassPosterior (hmm_class_posterior_walk forward, hmm_class_posterior_grad_walk backward), between
+which nothing of size (k,b,L,q) but E is kept.
 """
 import torch
 
@@ -153,6 +156,62 @@ def posterior(A, pi, E, mode=engine.POST_LOG, eps=engine.EPS, support_only=False
                 support_only == "always" or L.hmm_posterior_grad_walk_pays(*E.shape) == 1):
             return SupportPosterior.apply(A, pi, E, mode, eps)
     return Posterior.apply(A, pi, E, mode, eps)
+
+
+class ClassPosterior(torch.autograd.Function):
+    """Class posteriors (k,b,L,C) of 65..256-state models, probabilities or logs, differentiable in A, pi and E
+    through the per-sequence walks: forward = hmm_class_posterior_walk, backward = hmm_class_posterior_grad_walk,
+    which checks that no model was refused.  Saved between the two: A, pi, E and the (k,b,L,C) probabilities; neither
+    the state posteriors nor a gradient of their size exist.  The gradient for A is exactly 0 wherever A == 0."""
+
+    @staticmethod
+    def forward(ctx, A, pi, E, table, C, mode, eps):
+        A, pi, E = A.contiguous(), pi.contiguous(), E.contiguous()
+        log = int(mode) == engine.POST_LOG
+        prob, logp, _ = engine.class_posterior_walk(A, pi, E, table, C, eps=eps, prob=True, log=log)
+        ctx.save_for_backward(A, pi, E, prob)
+        ctx.table, ctx.C, ctx.mode, ctx.eps = table, C, int(mode), eps
+        return logp if log else prob
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        A, pi, E, prob = ctx.saved_tensors
+        dA, dpi, dE = engine.class_posterior_grad_walk(A, pi, E, ctx.table, ctx.C, grad_out.to(torch.float32).contiguous(),
+                                                       class_prob=prob, mode=ctx.mode, eps=ctx.eps, check=True)
+        need = ctx.needs_input_grad
+        return (dA if need[0] else None, dpi.reshape(pi.shape) if need[1] else None, dE if need[2] else None,
+                None, None, None, None)
+
+
+def class_posterior(A, pi, E, state_class, num_classes=None, mode=engine.POST_LOG, eps=engine.EPS, support_only=False):
+    """Differentiable class posteriors (k,b,L,C): P_c[t] = the sum of the state posteriors of the states that
+    `state_class` maps to class c (mode engine.POST_PROB), or log P (POST_LOG; -inf where P is 0).  For 65..256 states
+    and at most 16 classes, support_only="always", or True where hmm_class_posterior_walk_pays says 1, takes the fused
+    node (ClassPosterior: nothing of size (k,b,L,q) but E and its gradient exists; the gradient for A is exactly 0
+    wherever A == 0, as in posterior()).  Everything else — any other q the engine serves, more classes, False —
+    composes posterior(POST_PROB, support_only=support_only) with engine.collapse_posterior (and log) in torch ops.
+    On both routes a class whose posterior is exactly 0 gives -inf in POST_LOG and passes no gradient."""
+    if support_only not in (False, True, "always"):
+        raise ValueError("support_only must be False, True or \"always\", got %r" % (support_only,))
+    if int(mode) not in (engine.POST_PROB, engine.POST_LOG):
+        raise ValueError("class_posterior supports mode POST_PROB or POST_LOG")
+    q = E.shape[-1]
+    if state_class is None:
+        raise ValueError("class_posterior needs a class table (state_class)")
+    table, C = engine.class_table(state_class, num_classes, q)
+    if support_only and C <= 16:
+        L = engine.lib()
+        if L.hmm_posterior_walk_min_states() <= q <= L.hmm_posterior_walk_max_states() and (
+                support_only == "always" or L.hmm_class_posterior_walk_pays(*E.shape) == 1):
+            return ClassPosterior.apply(A, pi, E, table, C, mode, eps)
+    P = engine.collapse_posterior(posterior(A, pi, E, mode=engine.POST_PROB, eps=eps, support_only=support_only),
+                                  table, C)
+    if int(mode) != engine.POST_LOG:
+        return P
+    # as the node: -inf where a class posterior is exactly 0, and nothing passes through it (torch.log alone would hand
+    # grad / 0 to the states of a non-empty class)
+    on = P > 0
+    return torch.where(on, torch.log(torch.where(on, P, torch.ones_like(P))), torch.full_like(P, float("-inf")))
 
 
 class GeneEmissions(torch.autograd.Function):

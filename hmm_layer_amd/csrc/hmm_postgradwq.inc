@@ -39,6 +39,11 @@
 // dropped.  A refused model (WqSp::sparse == 0) is left alone by the sweeps and the sums; k_gw_refuse writes NaN into
 // its dA, dpi and dE rows and the call's counter.  Every offset into E, grad_out, dE and the workspace arrays is
 // 64-bit.  No atomics.
+//
+// hmm_class_posterior_grad_walk is the same call for a loss on CLASS posteriors (sums of gamma over the states of a
+// class): sweeps 3 and 4 are templated on where G comes from (PgwStateG: the (k,b,L,q) tensor, today's code;
+// PgwClassG: a (k,b,L,C) tensor and the lane's class), log mode divides the upstream gradient by the class posteriors
+// first (k_pgw_class_quot) and then runs in prob mode; everything else is shared.
 
 #define PGW_PF 4                 // rows in flight per stream (k_pgw_alpha reads five streams; see DESIGN §12e)
 
@@ -103,13 +108,39 @@ __global__ __launch_bounds__(WQ_MAX, 4) void k_pgw_rb(const float *__restrict__ 
     }
 }
 
+// Where the two adjoints read the upstream gradient G of (sequence, position, this lane's state).  PgwStateG: a
+// (k,b,L,q) tensor, the element beside E's (hmm_posterior_grad_walk).  PgwClassG: a (k,b,L,ncls) tensor of per-class
+// gradients (hmm_class_posterior_grad_walk): the class table travels by value as DecodeWide's masks, every lane finds
+// its class once, and a wave's 64 lanes then touch at most ncls dwords of one or two cache lines per position.
+struct PgwStateG {
+    static constexpr bool cls = false;
+};
+struct alignas(8) PgwClassG {
+    static constexpr bool cls = true;
+    unsigned long long mask[QP][WQ_MAX / 64];   // bit s of mask[c]: state s belongs to class c
+    int ncls;                                   // 1 .. QP
+};
+
+// lane x's class (0 for a lane beyond q: it has no bit, reads a valid element and keeps G = 0)
+__device__ __forceinline__ int pgw_class_of(const PgwClassG &gs, int x) {
+    const int w = x >> 6, lane = x & 63;
+    int c = 0;
+#pragma unroll
+    for (int k = 1; k < QP; ++k)                              // (constant indices: the masks stay arguments)
+#pragma unroll
+        for (int u = 0; u < WQ_MAX / 64; ++u)
+            if (u == w && ((gs.mask[k][u] >> lane) & 1ull)) c = k;
+    return c;
+}
+
 // adjoint of the backward recursion, ascending in time: grid k*b, block NP.  Step p handles position p: it turns
 // Rbar_{p-1} into w_{p-1}, gathers bhbar = A^T w_{p-1}, adds w_{p-1} (x) bh_p to the owned edges, writes dEb_p into dE
 // and forms Rbar_p.  acc: (k*b, GW_ACC, NP).
-__global__ __launch_bounds__(WQ_MAX, 4) void k_pgw_beta(const float *__restrict__ E, const float *__restrict__ AH,
-                                                     const float *__restrict__ RB, const float *__restrict__ G, int b,
-                                                     int L, int q, float eps, int mode, float *__restrict__ dE,
-                                                     float *__restrict__ acc, const WqSp *__restrict__ sp) {
+template <class GS>
+__device__ __forceinline__ void pgw_beta_body(const float *__restrict__ E, const float *__restrict__ AH,
+                                              const float *__restrict__ RB, const float *__restrict__ G, int b, int L,
+                                              int q, float eps, int mode, float *__restrict__ dE,
+                                              float *__restrict__ acc, const WqSp *__restrict__ sp, const GS &gs) {
     __shared__ __attribute__((aligned(16))) float wv[WQ_MAX];
     __shared__ f4 pa[2][WQ_MAX / 64];                         // [buffer][wave]: sum U, U Rb, G U Rb, G
     __shared__ f4 pb[2][WQ_MAX / 64];                         //                 sum sb, hub 0, hub 1 (of hin w)
@@ -170,15 +201,23 @@ __global__ __launch_bounds__(WQ_MAX, 4) void k_pgw_beta(const float *__restrict_
         rbs = rb1s;
     };
     auto at = [&](int t) { return base + (size_t)(t < L ? t : L - 1) * q + xc; };
+    const float *gp = G;                                       // PgwClassG: the sequence's row 0 (block-uniform) ...
+    unsigned cls = 0;                                          // ... and this lane's class: the one per-lane offset
+    int C = 0;
+    if constexpr (GS::cls) { C = gs.ncls; gp = G + (size_t)row * L * C; cls = pgw_class_of(gs, x) & (QP - 1); }
+    auto gat = [&](int t, size_t o) -> float {                 // G of position min(t, L - 1); o = at(t)
+        if constexpr (GS::cls) return (gp + (size_t)(t < L ? t : L - 1) * C)[cls];
+        else return G[o];
+    };
     float en[PGW_PF], un[PGW_PF], rn[PGW_PF], gn[PGW_PF];
 #pragma unroll
-    for (int u = 0; u < PGW_PF; ++u) { const size_t o = at(u); en[u] = E[o]; un[u] = AH[o]; rn[u] = RB[o]; gn[u] = G[o]; }
+    for (int u = 0; u < PGW_PF; ++u) { const size_t o = at(u); en[u] = E[o]; un[u] = AH[o]; rn[u] = RB[o]; gn[u] = gat(u, o); }
     for (int tb = 0; tb < L; tb += PGW_PF) {
 #pragma unroll
         for (int u = 0; u < PGW_PF; ++u) {
             const float e = en[u], us = un[u], r = rn[u], g = gn[u];
             const size_t o = at(tb + u + PGW_PF);
-            en[u] = E[o]; un[u] = AH[o]; rn[u] = RB[o]; gn[u] = G[o];
+            en[u] = E[o]; un[u] = AH[o]; rn[u] = RB[o]; gn[u] = gat(tb + u + PGW_PF, o);
             if (tb + u < L) step(tb + u, e, us, r, g);        // block-uniform
         }
     }
@@ -188,14 +227,33 @@ __global__ __launch_bounds__(WQ_MAX, 4) void k_pgw_beta(const float *__restrict_
     ar[8 * NP] = ah0;  ar[9 * NP] = ah1;
 }
 
+__global__ __launch_bounds__(WQ_MAX, 4) void k_pgw_beta(const float *__restrict__ E, const float *__restrict__ AH,
+                                                     const float *__restrict__ RB, const float *__restrict__ G, int b,
+                                                     int L, int q, float eps, int mode, float *__restrict__ dE,
+                                                     float *__restrict__ acc, const WqSp *__restrict__ sp) {
+    pgw_beta_body(E, AH, RB, G, b, L, q, eps, mode, dE, acc, sp, PgwStateG());
+}
+
+// the same with per-class gradients: Gs (k,b,L,gs.ncls).  (Five workgroups per CU asked for: the state form reaches
+// them at 92 VGPRs on its own, this one needs telling to stay within 96.)
+__global__ __launch_bounds__(WQ_MAX, 5) void k_pgw_beta_class(const float *__restrict__ E, const float *__restrict__ AH,
+                                                           const float *__restrict__ RB, const float *__restrict__ Gs,
+                                                           int b, int L, int q, float eps, int mode,
+                                                           float *__restrict__ dE, float *__restrict__ acc,
+                                                           const WqSp *__restrict__ sp, const PgwClassG gs) {
+    pgw_beta_body(E, AH, RB, Gs, b, L, q, eps, mode, dE, acc, sp, gs);
+}
+
 // adjoint of the forward recursion, descending in time: grid k*b, block NP.  Step t normalises U_t, adds
 // alpha_hat_t (x) Rfbar_{t+1} (gathered by the step before) to the owned edges, finishes dE_t in place (dE holds the
 // share of k_pgw_beta) and gathers abar_{t-1} = A Rfbar_t; at t = 0 the sequence's dpi.  acc: (k*b, GW_ACC, NP).
-__global__ __launch_bounds__(WQ_MAX, 4) void k_pgw_alpha(const float *__restrict__ pi, const float *__restrict__ E,
-                                                      const float *__restrict__ AH, const float *__restrict__ RB,
-                                                      const float *__restrict__ G, int b, int L, int q, float eps,
-                                                      int mode, float *__restrict__ dE, float *__restrict__ acc,
-                                                      float *__restrict__ dpi_part, const WqSp *__restrict__ sp) {
+template <class GS>
+__device__ __forceinline__ void pgw_alpha_body(const float *__restrict__ pi, const float *__restrict__ E,
+                                               const float *__restrict__ AH, const float *__restrict__ RB,
+                                               const float *__restrict__ G, int b, int L, int q, float eps, int mode,
+                                               float *__restrict__ dE, float *__restrict__ acc,
+                                               float *__restrict__ dpi_part, const WqSp *__restrict__ sp,
+                                               const GS &gs) {
     __shared__ __attribute__((aligned(16))) float rv[WQ_MAX];
     __shared__ f4 pa[1][WQ_MAX / 64];                         // [wave]: sum U, U Rb, G U Rb, G
     __shared__ f4 pb[1][WQ_MAX / 64];                         //         sum G (U > 0), abar U
@@ -260,11 +318,19 @@ __global__ __launch_bounds__(WQ_MAX, 4) void k_pgw_alpha(const float *__restrict
     // the rings run towards position 0; positions before the start re-read row 0.  dE_t is read here before the step of
     // position t writes it (each lane reads and writes its own element only).
     auto at = [&](int t) { return base + (size_t)(t > 0 ? t : 0) * q + xc; };
+    const float *gp = G;                                       // PgwClassG: the sequence's row 0 (block-uniform) ...
+    unsigned cls = 0;                                          // ... and this lane's class: the one per-lane offset
+    int C = 0;
+    if constexpr (GS::cls) { C = gs.ncls; gp = G + (size_t)row * L * C; cls = pgw_class_of(gs, x) & (QP - 1); }
+    auto gat = [&](int t, size_t o) -> float {                 // G of position max(t, 0); o = at(t)
+        if constexpr (GS::cls) return (gp + (size_t)(t > 0 ? t : 0) * C)[cls];
+        else return G[o];
+    };
     float en[PGW_PF], un[PGW_PF], rn[PGW_PF], gn[PGW_PF], dn[PGW_PF];
 #pragma unroll
     for (int u = 0; u < PGW_PF; ++u) {
         const size_t o = at(L - 1 - u);
-        en[u] = E[o]; un[u] = AH[o]; rn[u] = RB[o]; gn[u] = G[o]; dn[u] = dE[o];
+        en[u] = E[o]; un[u] = AH[o]; rn[u] = RB[o]; gn[u] = gat(L - 1 - u, o); dn[u] = dE[o];
     }
     __syncthreads();                                          // hal zeroed
     for (int tb = L - 1; tb >= 0; tb -= PGW_PF) {
@@ -272,7 +338,7 @@ __global__ __launch_bounds__(WQ_MAX, 4) void k_pgw_alpha(const float *__restrict
         for (int u = 0; u < PGW_PF; ++u) {
             const float e = en[u], us = un[u], r = rn[u], g = gn[u], d = dn[u];
             const size_t o = at(tb - u - PGW_PF);
-            en[u] = E[o]; un[u] = AH[o]; rn[u] = RB[o]; gn[u] = G[o]; dn[u] = dE[o];
+            en[u] = E[o]; un[u] = AH[o]; rn[u] = RB[o]; gn[u] = gat(tb - u - PGW_PF, o); dn[u] = dE[o];
             if (tb - u >= 0) step(tb - u, e, us, r, g, d);    // block-uniform
         }
     }
@@ -280,6 +346,34 @@ __global__ __launch_bounds__(WQ_MAX, 4) void k_pgw_alpha(const float *__restrict
     ar[0 * NP] = a0.x; ar[1 * NP] = a0.y; ar[2 * NP] = a0.z; ar[3 * NP] = a0.w;
     ar[4 * NP] = a1.x; ar[5 * NP] = a1.y; ar[6 * NP] = a1.z; ar[7 * NP] = a1.w;
     ar[8 * NP] = ah0;  ar[9 * NP] = ah1;
+}
+
+__global__ __launch_bounds__(WQ_MAX, 4) void k_pgw_alpha(const float *__restrict__ pi, const float *__restrict__ E,
+                                                      const float *__restrict__ AH, const float *__restrict__ RB,
+                                                      const float *__restrict__ G, int b, int L, int q, float eps,
+                                                      int mode, float *__restrict__ dE, float *__restrict__ acc,
+                                                      float *__restrict__ dpi_part, const WqSp *__restrict__ sp) {
+    pgw_alpha_body(pi, E, AH, RB, G, b, L, q, eps, mode, dE, acc, dpi_part, sp, PgwStateG());
+}
+
+// the same with per-class gradients: Gs (k,b,L,gs.ncls)
+__global__ __launch_bounds__(WQ_MAX, 4) void k_pgw_alpha_class(const float *__restrict__ pi, const float *__restrict__ E,
+                                                            const float *__restrict__ AH, const float *__restrict__ RB,
+                                                            const float *__restrict__ Gs, int b, int L, int q,
+                                                            float eps, int mode, float *__restrict__ dE,
+                                                            float *__restrict__ acc, float *__restrict__ dpi_part,
+                                                            const WqSp *__restrict__ sp, const PgwClassG gs) {
+    pgw_alpha_body(pi, E, AH, RB, Gs, b, L, q, eps, mode, dE, acc, dpi_part, sp, gs);
+}
+
+// log mode's upstream gradient in prob-mode terms: Gp = grad_out / class_prob (the IEEE fp32 quotient), 0 where the
+// class posterior is 0 (an empty or exactly-zero class passes nothing).  n = k b L ncls elements, grid-stride.
+__global__ __launch_bounds__(256) void k_pgw_class_quot(const float *__restrict__ g, const float *__restrict__ P,
+                                                        float *__restrict__ Gp, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const float p = P[i];
+        Gp[i] = p > 0.f ? g[i] / p : 0.f;
+    }
 }
 
 // dA (k,q,q) from the sequences' accumulators of both adjoints: one wave per (model, row i).  Every entry of the row is
@@ -401,6 +495,62 @@ int hmm_posterior_grad_walk(const float *A, const float *pi, const float *E, int
     launch(k_pgw_rb, grid, blk, 0, st, E, b, L, q, eps, RB, csp);
     launch(k_pgw_beta, grid, blk, 0, st, E, cAH, cRB, grad_out, b, L, q, eps, mode, dE, accb, csp);
     launch(k_pgw_alpha, grid, blk, 0, st, pi, E, cAH, cRB, grad_out, b, L, q, eps, mode, dE, acca, dpp, csp);
+    launch(k_pgw_sum, dim3(q, k), dim3(64), 0, st, (const float *)accb, (const float *)acca, dA, b, q, p.NP, csp);
+    launch(k_pg_sum_rows, dim3(q, k), dim3(64), 0, st, (const float *)dpp, dpi, b, q);
+    launch(k_gw_refuse, dim3(GW_REFUSE_BLOCKS, k), dim3(256), 0, st, csp, k, b, L, q, dA, dpi, dE, ll,
+           ws_at<int>(workspace, p.o_count));
+    return check_launch();
+}
+
+// hmm_posterior_grad_walk's layout first (hmm_posterior_grad_walk_refused reads the counter of a finished call of
+// either kind), then log mode's quotient tensor (k,b,L,num_classes)
+size_t hmm_class_posterior_grad_walk_workspace_bytes(int k, int b, int L, int q, int num_classes) {
+    PgwPlan p;
+    if (make_pgwplan(k, b, L, q, &p) || num_classes < 1 || num_classes > QP) return 0;
+    return align_up(p.total) + align_up((size_t)k * b * L * num_classes * sizeof(float));
+}
+
+int hmm_class_posterior_grad_walk(const float *A, const float *pi, const float *E, int k, int b, int L, int q, float eps,
+                                  int mode, const int *state_class, int num_classes, const float *class_prob,
+                                  const float *grad_out, float *dA, float *dpi, float *dE, void *workspace,
+                                  size_t workspace_bytes, void *stream) {
+    PgwPlan p;
+    int rc = make_pgwplan(k, b, L, q, &p);
+    if (rc) return rc;
+    if (mode != HMM_POST_PROB && mode != HMM_POST_LOG) return HMM_ERR_BAD_ARGUMENT;
+    if (!A || !pi || !E || !state_class || !grad_out || !dA || !dpi || !dE || !workspace ||
+        (mode == HMM_POST_LOG && !class_prob))
+        return HMM_ERR_NULL_POINTER;
+    if (num_classes < 1 || num_classes > QP) return HMM_ERR_BAD_ARGUMENT;
+    PgwClassG gs{};
+    gs.ncls = num_classes;
+    for (int s = 0; s < q; ++s) {                              // the table is read here, once, and travels by value
+        if (state_class[s] < 0 || state_class[s] >= num_classes) return HMM_ERR_BAD_ARGUMENT;
+        gs.mask[state_class[s]][s >> 6] |= 1ull << (s & 63);
+    }
+    const size_t o_gp = align_up(p.total), ng = (size_t)k * b * L * num_classes;
+    if ((rc = check_ws(o_gp + align_up(ng * sizeof(float)), workspace, workspace_bytes))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    WqSp *sp = ws_at<WqSp>(workspace, p.o_sp);
+    const WqSp *csp = sp;
+    double *ll = ws_at<double>(workspace, p.o_ll);
+    float *AH = ws_at<float>(workspace, p.o_ah), *RB = ws_at<float>(workspace, p.o_rb);
+    float *accb = ws_at<float>(workspace, p.o_accb), *acca = ws_at<float>(workspace, p.o_acca);
+    float *dpp = ws_at<float>(workspace, p.o_dpi);
+    const float *cAH = AH, *cRB = RB, *Gs = grad_out;
+    if (mode == HMM_POST_LOG) {                                // d/d gamma_j of sum Gc log P = Gc / P at j's class
+        float *Gp = ws_at<float>(workspace, o_gp);
+        const size_t nb = (ng + 255) / 256;
+        launch(k_pgw_class_quot, dim3((unsigned)(nb < 65536 ? nb : 65536)), dim3(256), 0, st, grad_out, class_prob, Gp, ng);
+        Gs = Gp;
+    }
+    const dim3 grid((unsigned)((size_t)k * b)), blk((unsigned)p.NP);
+    launch(k_wq_prep, dim3(k), dim3(WQ_MAX), 0, st, A, sp, q, 0);
+    launch(k_gw_fwd<true>, grid, blk, 0, st, pi, E, b, L, q, eps, AH, ll, csp);
+    launch(k_pgw_rb, grid, blk, 0, st, E, b, L, q, eps, RB, csp);
+    launch(k_pgw_beta_class, grid, blk, 0, st, E, cAH, cRB, Gs, b, L, q, eps, (int)HMM_POST_PROB, dE, accb, csp, gs);
+    launch(k_pgw_alpha_class, grid, blk, 0, st, pi, E, cAH, cRB, Gs, b, L, q, eps, (int)HMM_POST_PROB, dE, acca, dpp, csp,
+           gs);
     launch(k_pgw_sum, dim3(q, k), dim3(64), 0, st, (const float *)accb, (const float *)acca, dA, b, q, p.NP, csp);
     launch(k_pg_sum_rows, dim3(q, k), dim3(64), 0, st, (const float *)dpp, dpi, b, q);
     launch(k_gw_refuse, dim3(GW_REFUSE_BLOCKS, k), dim3(256), 0, st, csp, k, b, L, q, dA, dpi, dE, ll,

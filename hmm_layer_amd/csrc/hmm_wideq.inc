@@ -35,6 +35,9 @@
 // (hmm_midq.inc): the class posterior is the fp32 sum over ALL states in increasing index with weights 0 / 1
 // (fma(v, 1, s) = s + v rounded once, fma(v, 0, s) = s), classes are compared in increasing index with a strict >,
 // and with the identity map nothing is summed.  The class table travels by value as 16 masks of 256 bits.
+// ClassWide (hmm_class_posterior_walk) is DecodeWide without the argmax: same staging, masks and class-sum loop (so the
+// sums have the bits DecodeWide compares), and drain() writes the ncls sums of every staged row to out_prob and / or
+// out_log, where k_wq_class_log turns them into their logs after the walk (a sum of 0 gives -inf).
 
 #define WQ_MIN 65
 #define WQ_MAX 256
@@ -56,10 +59,20 @@ struct WqSp {
 
 struct alignas(8) DecodeWide {
     static constexpr bool on = true;
+    static constexpr bool sums = false;         // the argmax leaves, not the sums
     unsigned long long mask[QP][WQ_MAX / 64];   // bit s of mask[c]: state s belongs to class c
     unsigned char *label;                       // (k,b,L)
     float *conf;                                // (k,b,L) or null
     int ncls;                                   // number of classes; 0: the identity map (no sums)
+};
+
+struct alignas(8) ClassWide {
+    static constexpr bool on = true;
+    static constexpr bool sums = true;
+    unsigned long long mask[QP][WQ_MAX / 64];   // as DecodeWide's
+    float *prob;                                // (k,b,L,ncls) or null
+    float *logp;                                // (k,b,L,ncls) or null
+    int ncls;                                   // 1 .. QP
 };
 
 // one block of 256 threads per model: the lists, the hubs and the verdict
@@ -222,20 +235,32 @@ __device__ __forceinline__ void wq_walk_body(const float *__restrict__ A, const 
                 }
                 __syncthreads();
             }
-            for (int rr = threadIdx.x; rr < nrows; rr += blockDim.x) {
-                const int slot = rr < cntF ? rr : WQ_T + rr - cntF;
-                const int t = rr < cntF ? firstF + rr : firstB - (rr - cntF);
-                const float *rp = ncls > 0 ? csum + slot * QP : ring + slot * rs;
-                const int n = ncls > 0 ? ncls : q;
-                float best = rp[0];
-                int lab = 0;
-                for (int s = 1; s < n; ++s) {
-                    const float v = rp[s];
-                    if (v > best) { best = v; lab = s; }                  // strict: the lowest index wins a tie
+            if constexpr (DEC::sums) {                      // ClassWide: the sums themselves (ncls >= 1)
+                for (int p = threadIdx.x; p < nrows * ncls; p += blockDim.x) {
+                    const int rr = p / ncls, c = p - rr * ncls;
+                    const int slot = rr < cntF ? rr : WQ_T + rr - cntF;
+                    const int t = rr < cntF ? firstF + rr : firstB - (rr - cntF);
+                    const float v = csum[slot * QP + c];
+                    const size_t at = ((size_t)row * L + t) * ncls + c;
+                    if (dec.prob) dec.prob[at] = v;
+                    if (dec.logp) dec.logp[at] = v;               // k_wq_class_log takes the log in place, after the walk
                 }
-                const long long at = row * L + t;
-                dec.label[at] = (unsigned char)lab;
-                if (dec.conf) dec.conf[at] = best;
+            } else {
+                for (int rr = threadIdx.x; rr < nrows; rr += blockDim.x) {
+                    const int slot = rr < cntF ? rr : WQ_T + rr - cntF;
+                    const int t = rr < cntF ? firstF + rr : firstB - (rr - cntF);
+                    const float *rp = ncls > 0 ? csum + slot * QP : ring + slot * rs;
+                    const int n = ncls > 0 ? ncls : q;
+                    float best = rp[0];
+                    int lab = 0;
+                    for (int s = 1; s < n; ++s) {
+                        const float v = rp[s];
+                        if (v > best) { best = v; lab = s; }              // strict: the lowest index wins a tie
+                    }
+                    const long long at = row * L + t;
+                    dec.label[at] = (unsigned char)lab;
+                    if (dec.conf) dec.conf[at] = best;
+                }
             }
             __syncthreads();
             cntF = cntB = 0;
@@ -364,6 +389,24 @@ void k_wq_walk_decode(const float *__restrict__ A, const float *__restrict__ At,
     wq_walk_body<STEP, DecodeWide>(A, At, pi, E, b, L, q, eps, park, ll, 0, sp, dec, wq_lds);
 }
 
+// the ClassWide form; park and dynamic LDS as for k_wq_walk_decode
+template <int STEP>
+__global__ __launch_bounds__(STEP == 1 ? 2 * WQ_REG : 2 * WQ_MAX)
+void k_wq_walk_class(const float *__restrict__ A, const float *__restrict__ At, const float *__restrict__ pi,
+                     const float *__restrict__ E, int b, int L, int q, float eps, float *__restrict__ park,
+                     double *__restrict__ ll, const WqSp *__restrict__ sp, const ClassWide dec) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long wq_lds[];
+    wq_walk_body<STEP, ClassWide>(A, At, pi, E, b, L, q, eps, park, ll, 0, sp, dec, wq_lds);
+}
+
+// out_log of the ClassWide form, in place: the sums the walk left there -> their logs, -inf for 0.  The fp64 log rounded
+// once: logf measured 2.04 ulp on these sums, over the 2 ulp the header promises, and the fp64 log inside drain() cost
+// the sparse walk 30 VGPRs and one of its two workgroups per CU.  n = k b L ncls elements, grid-stride.
+__global__ __launch_bounds__(256) void k_wq_class_log(float *__restrict__ x, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        x[i] = (float)log((double)x[i]);
+}
+
 // ---- host side
 struct WqPlan { size_t o_ll, o_sp, o_At, total; };
 static int make_wqplan(int k, int b, int L, int q, WqPlan *p) {
@@ -377,9 +420,10 @@ static int make_wqplan(int k, int b, int L, int q, WqPlan *p) {
     return HMM_OK;
 }
 
-// dec null: gamma rows per `mode` into `out`; else labels, with `out` the parking region
+// dec and cls null: gamma rows per `mode` into `out`; dec: labels, cls: class sums, with `out` the parking region
 static void wq_walk(const float *A, const float *pi, const float *E, int k, int b, int L, int q, float eps, int mode,
-                    float *out, const WqPlan &p, char *ws, const DecodeWide *dec, hipStream_t st) {
+                    float *out, const WqPlan &p, char *ws, const DecodeWide *dec, hipStream_t st,
+                    const ClassWide *cls = nullptr) {
     WqSp *sp = ws_at<WqSp>(ws, p.o_sp);
     const WqSp *csp = sp;
     double *ll = ws_at<double>(ws, p.o_ll);
@@ -388,7 +432,12 @@ static void wq_walk(const float *A, const float *pi, const float *E, int k, int 
     if (q > WQ_REG) launch(k_lq_transpose, dim3((q + 31) / 32, (q + 31) / 32, k), dim3(256), 0, st, A, At, q);
     const dim3 grid((unsigned)((size_t)k * b)), blk((unsigned)(2 * ((q + 63) / 64 * 64)));
     const float *cAt = At;
-    if (dec) {
+    if (cls) {
+        const unsigned lds = wq_decode_lds(q);
+        launch(k_wq_walk_class<0>, grid, blk, lds, st, A, cAt, pi, E, b, L, q, eps, out, ll, csp, *cls);
+        launch(q <= WQ_REG ? k_wq_walk_class<1> : k_wq_walk_class<2>, grid, blk, lds, st, A, cAt, pi, E, b, L, q, eps,
+               out, ll, csp, *cls);
+    } else if (dec) {
         const unsigned lds = wq_decode_lds(q);
         launch(k_wq_walk_decode<0>, grid, blk, lds, st, A, cAt, pi, E, b, L, q, eps, out, ll, csp, *dec);
         launch(q <= WQ_REG ? k_wq_walk_decode<1> : k_wq_walk_decode<2>, grid, blk, lds, st, A, cAt, pi, E, b, L, q, eps,
@@ -463,6 +512,53 @@ int hmm_posterior_decode_wide(const float *A, const float *pi, const float *E, i
     if ((rc = check_ws(o_park + (size_t)k * b * L * q * sizeof(float), workspace, workspace_bytes))) return rc;
     hipStream_t st = (hipStream_t)stream;
     wq_walk(A, pi, E, k, b, L, q, eps, HMM_POST_PROB, ws_at<float>(workspace, o_park), p, (char *)workspace, &dec, st);
+    if (loglik) launch(k_copy_loglik, dim3((k * b + 255) / 256), dim3(256), 0, st, ws_at<double>(workspace, p.o_ll), loglik, k * b);
+    return check_launch();
+}
+
+size_t hmm_class_posterior_walk_workspace_bytes(int k, int b, int L, int q) {
+    return hmm_posterior_decode_wide_workspace_bytes(k, b, L, q);
+}
+
+// 1 where autograd's fused class-posterior node (this forward + hmm_class_posterior_grad_walk) measured at least 1.25x
+// faster than the composition it replaces (DESIGN §12f; tools/experiments/class_posterior_walk_time.py,
+// profiles/class_posterior_walk.json); 0 where nothing was measured.  Measured on one MI355X at L = 10 000, one model,
+// 6 classes, log mode, a label-style upstream gradient, the gene models of 71, 127 and 253 states at 1 / 32 / 1024
+// sequences: 0.93 .. 1.00x at 1 and 32 sequences (the walks are latency-bound there, and the class forward costs 1.5 to
+// 4 ms more than hmm_posterior_walk), 1.58x / 2.04x / 1.83x at 1024.  So the rule is the three cells that pay and
+// nothing else: neither the crossover between 32 and 1024 sequences, nor more than 1024, nor other state counts were
+// measured, nor more than one model per call (k > 1: 0).  The one extrapolation is L, by the convention of
+// hmm_posterior_walk_pays and hmm_posterior_grad_walk_pays: it does not enter, both evaluations cost per position.
+#define CPW_PAYS_SEQS 1024
+int hmm_class_posterior_walk_pays(int k, int b, int L, int q) {
+    WqPlan p;
+    if (make_wqplan(k, b, L, q, &p)) return 0;
+    return (q == 71 || q == 127 || q == 253) && k == 1 && b == CPW_PAYS_SEQS ? 1 : 0;
+}
+
+int hmm_class_posterior_walk(const float *A, const float *pi, const float *E, int k, int b, int L, int q, float eps,
+                             const int *state_class, int num_classes, float *out_prob, float *out_log, double *loglik,
+                             void *workspace, size_t workspace_bytes, void *stream) {
+    WqPlan p;
+    int rc = make_wqplan(k, b, L, q, &p);
+    if (rc) return rc;
+    if (!A || !pi || !E || !state_class || !workspace || (!out_prob && !out_log)) return HMM_ERR_NULL_POINTER;
+    if (num_classes < 1 || num_classes > QP) return HMM_ERR_BAD_ARGUMENT;
+    ClassWide cls{};
+    cls.prob = out_prob; cls.logp = out_log; cls.ncls = num_classes;
+    for (int s = 0; s < q; ++s) {                              // the table is read here, once, and travels by value
+        if (state_class[s] < 0 || state_class[s] >= num_classes) return HMM_ERR_BAD_ARGUMENT;
+        cls.mask[state_class[s]][s >> 6] |= 1ull << (s & 63);
+    }
+    const size_t o_park = align_up(p.total);
+    if ((rc = check_ws(o_park + (size_t)k * b * L * q * sizeof(float), workspace, workspace_bytes))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    wq_walk(A, pi, E, k, b, L, q, eps, HMM_POST_PROB, ws_at<float>(workspace, o_park), p, (char *)workspace, nullptr, st,
+            &cls);
+    if (out_log) {
+        const size_t n = (size_t)k * b * L * num_classes, nb = (n + 255) / 256;
+        launch(k_wq_class_log, dim3((unsigned)(nb < 65536 ? nb : 65536)), dim3(256), 0, st, out_log, n);
+    }
     if (loglik) launch(k_copy_loglik, dim3((k * b + 255) / 256), dim3(256), 0, st, ws_at<double>(workspace, p.o_ll), loglik, k * b);
     return check_launch();
 }

@@ -184,6 +184,16 @@ POSTERIOR_GRAD_WALK_SIGNATURES = {
     "hmm_posterior_grad_walk": (_I, _POSTERIOR_GRAD),
 }
 
+# ... and those of the class posteriors with gradients for 65..256 states (hmm_class_posterior_walk,
+# hmm_class_posterior_grad_walk), likewise.
+CLASS_POSTERIOR_WALK_SIGNATURES = {
+    "hmm_class_posterior_walk_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "hmm_class_posterior_walk_pays": (_I, [_I, _I, _I, _I]),
+    "hmm_class_posterior_walk": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _P, _I, _P, _P, _P, _P, _SZ, _P]),
+    "hmm_class_posterior_grad_walk_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
+    "hmm_class_posterior_grad_walk": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _I, _P, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+}
+
 
 def lib():
     """The loaded shared library (loaded once).  Raises if it has not been built."""
@@ -197,7 +207,7 @@ def lib():
     L = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**_SIGNATURES, **DECODE_SIGNATURES, **DECODE_MID_SIGNATURES,
                                       **POSTERIOR_WALK_SIGNATURES, **LOGLIK_GRAD_WALK_SIGNATURES,
-                                      **POSTERIOR_GRAD_WALK_SIGNATURES}.items():
+                                      **POSTERIOR_GRAD_WALK_SIGNATURES, **CLASS_POSTERIOR_WALK_SIGNATURES}.items():
         if not hasattr(L, name):
             raise EngineError("the engine library %s does not export %s: rebuild it with "
                               "`python -m hmm_layer_amd.build`" % (LIB_PATH, name))
@@ -519,12 +529,18 @@ def class_table(state_class, num_classes, q):
     return table, C
 
 
+def collapse_posterior(gamma, table, C):
+    """Class sums (..., C) of a posterior tensor (..., q) with torch ops: index_add_ over the state axis by the class
+    map `table` (a list of q ints).  Differentiable."""
+    idx = torch.tensor(table, dtype=torch.long, device=gamma.device)
+    return torch.zeros(gamma.shape[:-1] + (C,), dtype=gamma.dtype, device=gamma.device).index_add_(-1, idx, gamma)
+
+
 def decode_posterior(gamma, table, C):
     """What posterior_decode computes, from a posterior tensor (..., q) with torch ops: class sums (index_add_ over the
     state axis), then the largest class per position, the lowest index on ties -> (label uint8, conf)."""
     if table is not None:
-        idx = torch.tensor(table, dtype=torch.long, device=gamma.device)
-        gamma = torch.zeros(gamma.shape[:-1] + (C,), dtype=gamma.dtype, device=gamma.device).index_add_(-1, idx, gamma)
+        gamma = collapse_posterior(gamma, table, C)
     # (torch.argmax returns the first maximal index; torch.max's index is not specified on ties)
     return gamma.argmax(dim=-1).to(torch.uint8), gamma.max(dim=-1).values
 
@@ -1248,3 +1264,92 @@ def posterior_grad_walk_refused(dims, device=None):
     """How many of the k models of the LAST posterior_grad_walk call with shape `dims` on this device and stream were
     refused (synchronises)."""
     return posterior_grad_serial_count(dims, device, _fn="hmm_posterior_grad_walk_refused", _tag=POSTGRAD_WALK_TAG)
+
+
+CLASS_WALK_TAG = "class_posterior_walk"              # class_posterior_walk()'s workspace
+CLASS_GRAD_WALK_TAG = "class_posterior_grad_walk"    # class_posterior_grad_walk()'s: its refusal counter is read from it
+
+
+def _class_walk_args(name, E, state_class, num_classes):
+    """Checks shared by class_posterior_walk and class_posterior_grad_walk, before the device is asked for
+    -> (table as a ctypes array, C)."""
+    lo, hi = lib().hmm_posterior_walk_min_states(), lib().hmm_posterior_walk_max_states()
+    if not torch.is_tensor(E) or E.dim() != 4:
+        raise ValueError("E must be a tensor of shape (k, b, L, q)")
+    q = E.shape[3]
+    if not lo <= q <= hi:
+        raise ValueError("%s serves %d..%d states, got q = %d" % (name, lo, hi, q))
+    if state_class is None:
+        raise ValueError("%s needs a class table (state_class)" % name)
+    table, C = class_table(state_class, num_classes, q)
+    if C > 16:
+        raise ValueError("at most 16 classes, got %d" % C)
+    return (ctypes.c_int * q)(*table), C
+
+
+def class_posterior_walk(A, pi, E, state_class, num_classes=None, eps=EPS, prob=True, log=False):
+    """Class posteriors for 65..256 states by the per-sequence walk (hmm_class_posterior_walk)
+    -> (prob (k,b,L,C) fp32 or None, log (k,b,L,C) fp32 or None, loglik (k,b) fp64): P_c[t] = the sum of the state
+    posteriors of class c's states, with the bits posterior_decode's fused call compares; log = its log (-inf for a
+    sum of 0).  The (k,b,L,q) tensor is not written (the workspace keeps a parking region of that size, as
+    posterior_decode's).  state_class: a sequence or an integer tensor of q classes, at most 16 of them.  Raises
+    ValueError outside 65..256 states, without a table, above 16 classes, or with neither output asked for."""
+    tab, C = _class_walk_args("class_posterior_walk", E, state_class, num_classes)
+    if not (prob or log):
+        raise ValueError("class_posterior_walk: ask for prob, log or both")
+    A, pi, E = _dev(A, "A"), _dev(pi, "pi"), _dev(E, "E")
+    A, pi, dims = _shapes(A, E, pi)
+    with torch.cuda.device(E.device):
+        ws = _workspace(E.device, lib().hmm_class_posterior_walk_workspace_bytes(*dims), CLASS_WALK_TAG)
+        P = torch.empty(dims[:3] + (C,), dtype=torch.float32, device=E.device) if prob else None
+        Lg = torch.empty(dims[:3] + (C,), dtype=torch.float32, device=E.device) if log else None
+        ll = torch.empty(dims[:2], dtype=torch.float64, device=E.device)
+        _check(lib().hmm_class_posterior_walk(A.data_ptr(), pi.data_ptr(), E.data_ptr(), *dims, eps, tab, C,
+                                              P.data_ptr() if prob else None, Lg.data_ptr() if log else None,
+                                              ll.data_ptr(), ws.data_ptr(), ws.numel(), _stream(E.device)))
+    return P, Lg, ll
+
+
+def class_posterior_grad_walk(A, pi, E, state_class, num_classes, grad_out, class_prob=None, mode=POST_LOG, eps=EPS,
+                              check=True):
+    """Gradients of <grad_out, out> with out = the class posteriors (POST_PROB) or their logs (POST_LOG) of
+    class_posterior_walk -> (dA (k,q,q), dpi (k,q), dE (k,b,L,q)) by hmm_class_posterior_grad_walk: grad_out is
+    (k,b,L,C), and nothing of size (k,b,L,q) but dE and the walk's workspace is touched.  POST_PROB is
+    posterior_grad_walk(POST_PROB) with grad_out[..., state_class], bit for bit; POST_LOG needs class_prob, the
+    forward's prob, and passes nothing through a class whose posterior is 0.  dA has exact zeros wherever A == 0; a
+    model outside the sparse rule is refused as in posterior_grad_walk (check=True: one synchronisation, EngineError)."""
+    tab, C = _class_walk_args("class_posterior_grad_walk", E, state_class, num_classes)
+    if int(mode) not in (POST_PROB, POST_LOG):
+        raise ValueError("class_posterior_grad_walk supports mode POST_PROB or POST_LOG")
+    if int(mode) == POST_LOG and class_prob is None:
+        raise ValueError("class_posterior_grad_walk: POST_LOG needs class_prob (class_posterior_walk's prob)")
+    A, pi, E, grad_out = _dev(A, "A"), _dev(pi, "pi"), _dev(E, "E"), _dev(grad_out, "grad_out")
+    A, pi, dims = _shapes(A, E, pi)
+    k, b, L, q = dims
+    if tuple(grad_out.shape) != (k, b, L, C):
+        raise ValueError("grad_out must have shape (k, b, L, C) = %s, got %s" % ((k, b, L, C), tuple(grad_out.shape)))
+    if int(mode) == POST_LOG:
+        class_prob = _dev(class_prob, "class_prob")
+        if class_prob.shape != grad_out.shape:
+            raise ValueError("class_prob must be shaped like grad_out")
+    with torch.cuda.device(E.device):
+        ws = _workspace(E.device, lib().hmm_class_posterior_grad_walk_workspace_bytes(*dims, C), CLASS_GRAD_WALK_TAG)
+        dA = torch.empty((k, q, q), dtype=torch.float32, device=E.device)
+        dpi = torch.empty((k, q), dtype=torch.float32, device=E.device)
+        dE = torch.empty_like(E)
+        _check(lib().hmm_class_posterior_grad_walk(
+            A.data_ptr(), pi.data_ptr(), E.data_ptr(), *dims, eps, int(mode), tab, C,
+            class_prob.data_ptr() if int(mode) == POST_LOG else None, grad_out.data_ptr(), dA.data_ptr(),
+            dpi.data_ptr(), dE.data_ptr(), ws.data_ptr(), ws.numel(), _stream(E.device)))
+        if check:
+            n = class_posterior_grad_walk_refused(dims, E.device)
+            if n:
+                raise EngineError("class_posterior_grad_walk: %d of %d models have more than two states above degree "
+                                  "8 and were refused (their outputs are NaN)" % (n, k))
+    return dA, dpi, dE
+
+
+def class_posterior_grad_walk_refused(dims, device=None):
+    """How many of the k models of the LAST class_posterior_grad_walk call with shape `dims` on this device and stream
+    were refused (synchronises): the workspace begins with hmm_posterior_grad_walk's layout."""
+    return posterior_grad_serial_count(dims, device, _fn="hmm_posterior_grad_walk_refused", _tag=CLASS_GRAD_WALK_TAG)

@@ -1224,6 +1224,70 @@ int hmm_posterior_grad_walk(const float *A, const float *pi, const float *E,
                             float *dA, float *dpi, float *dE,
                             void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * CLASS POSTERIORS WITH ANALYTIC GRADIENTS for 65 <= q <= 256 states: the trainable counterpart of
+ * hmm_posterior_decode_wide.  A model whose states are labelled by class (state_class: HOST pointer to q ints in
+ * 0..num_classes-1, REQUIRED; num_classes 1..16) is trained on P_c[t] = sum over the states j of class c of gamma_t[j];
+ * no gamma output tensor (k,b,L,q) is written and no upstream gradient of that size is read.  (The forward's workspace
+ * still holds a parking region of k*b*L*q floats, below, and the backward's its two arrays of that size.)
+ *
+ * hmm_class_posterior_walk: the walk of hmm_posterior_walk (same step selection per model, clamp semantics and
+ * HMM_OPT_FORCE_DENSE) with a third output policy beside hmm_posterior_decode_wide's: the same staging, masks and
+ * class-sum loop (the fp32 sum of the gamma row over ALL states in increasing index with weights 0 / 1), so the sums
+ * have the bits hmm_posterior_decode_wide compares — with the same table, out_prob at label is conf and the lowest
+ * argmax of out_prob is label.  out_prob (k,b,L,num_classes) gets the sums, out_log (same shape) their logs, within
+ * 2 fp32 ulp of log(out_prob) (the fp64 log rounded once; a sum of 0, e.g. an empty class, gives -inf); either may be
+ * NULL, not both.  loglik (k,b) fp64 or NULL is bit for bit
+ * hmm_posterior_walk's.  The table reaches the kernels by value: a captured graph keeps its table.
+ * Workspace: hmm_class_posterior_walk_workspace_bytes = hmm_posterior_decode_wide_workspace_bytes, the PARKING REGION
+ * of k*b*L*q floats included, under the same stated contract.  Every element of the outputs given is written; no
+ * atomics; repeated calls are bit-identical; every offset is 64-bit; the call runs on `stream` alone (capturable).
+ * Argument checks, before any HIP call, in this order: shape (HMM_ERR_BAD_SHAPE), q < 65 or q > 256
+ * (HMM_ERR_Q_UNSUPPORTED), NULL among A, pi, E, state_class, workspace, or both outputs NULL (HMM_ERR_NULL_POINTER),
+ * num_classes outside 1..16 or a table entry outside 0..num_classes-1 (HMM_ERR_BAD_ARGUMENT), workspace too small or
+ * not 256-byte aligned (HMM_ERR_WORKSPACE).
+ *
+ * hmm_class_posterior_grad_walk: gradients of a loss on the class posteriors -> dA (k,q,q), dpi (k,q), dE (k,b,L,q),
+ * with grad_out (k,b,L,num_classes) the upstream gradient Gc:
+ *   HMM_POST_PROB   loss = sum Gc P: hmm_posterior_grad_walk(HMM_POST_PROB) with G[t][j] = Gc[t][class(j)], bit for
+ *                   bit.  Gc is read in place: every lane finds its class once and loads Gc[t][class] where the state
+ *                   form loads G[t][j].  class_prob is ignored.
+ *   HMM_POST_LOG    loss = sum Gc log P.  d loss / d gamma_j = Gc[class(j)] / P[class(j)], so this IS the prob-mode
+ *                   adjoint with G'[t][c] = Gc[t][c] / P_c[t], the IEEE fp32 quotient, and G' = 0 where P_c == 0 (an
+ *                   empty or exactly-zero class passes nothing).  class_prob (k,b,L,num_classes), REQUIRED, is the
+ *                   forward's out_prob; a pre-pass writes G' into the workspace and the adjoints run in prob mode.
+ * Everything else is hmm_posterior_grad_walk's: the four sweeps, the edge owners, the fp64 sums over sequences, dA an
+ * exact 0 wherever A == 0, refusal of a model outside the sparse rule by NaN in its outputs, no atomics, 64-bit
+ * offsets, bit-identical repetition, one stream, capturable.
+ * Workspace: hmm_class_posterior_grad_walk_workspace_bytes(k, b, L, q, num_classes) (0: unsupported shape, q or
+ * num_classes) = hmm_posterior_grad_walk's layout first, rounded up to 256 bytes, then G' (k*b*L*num_classes floats).
+ * hmm_posterior_grad_walk_refused(k, b, L, q, workspace, workspace_bytes) THEREFORE READS THE COUNTER OF A FINISHED
+ * hmm_class_posterior_grad_walk CALL as it does hmm_posterior_grad_walk's.
+ * Argument checks, before any HIP call and in this order: bad shape -1; q < 65 or q > 256 -2; mode not HMM_POST_PROB /
+ * HMM_POST_LOG -6; a NULL A / pi / E / state_class / grad_out / dA / dpi / dE / workspace, or class_prob in
+ * HMM_POST_LOG, -3; num_classes outside 1..16 or a table entry outside 0..num_classes-1 -6; a small or misaligned
+ * (256 bytes) workspace -4.
+ *
+ * hmm_class_posterior_walk_pays(k, b, L, q): 1 only where tools/experiments/class_posterior_walk_time.py measured the
+ * fused node (both calls) at least 1.25x faster than autograd through hmm_posterior_grad_walk and torch ops over the
+ * (k,b,L,q) tensor; 0 elsewhere, outside the range and wherever nothing was measured.  As measured on
+ * one MI355X (L = 10 000, 6 classes, log mode): 1 for one model (k = 1) of 71, 127 or 253 states with b = 1024
+ * sequences, whatever L (L does not enter, as in hmm_posterior_grad_walk_pays); 0 for every other (k, b, q).
+ */
+size_t hmm_class_posterior_walk_workspace_bytes(int k, int b, int L, int q);
+int hmm_class_posterior_walk_pays(int k, int b, int L, int q);
+int hmm_class_posterior_walk(const float *A, const float *pi, const float *E,
+                             int k, int b, int L, int q, float eps,
+                             const int *state_class, int num_classes,
+                             float *out_prob, float *out_log, double *loglik,
+                             void *workspace, size_t workspace_bytes, void *stream);
+size_t hmm_class_posterior_grad_walk_workspace_bytes(int k, int b, int L, int q, int num_classes);
+int hmm_class_posterior_grad_walk(const float *A, const float *pi, const float *E,
+                                  int k, int b, int L, int q, float eps, int mode,
+                                  const int *state_class, int num_classes, const float *class_prob,
+                                  const float *grad_out, float *dA, float *dpi, float *dE,
+                                  void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
