@@ -71,6 +71,14 @@ typedef int i4 __attribute__((ext_vector_type(4)));
 #ifndef HMM_COALESCE_B
 #define HMM_COALESCE_B 0
 #endif
+#ifndef HMM_STAGE_BF
+#define HMM_STAGE_BF 1     // stage_row without exec-mask regions: a component past the row goes to the chain's pad slot
+#endif
+#ifndef HMM_COLSUM2
+#define HMM_COLSUM2 1      // backward step: gamma's and beta's normalisers in one paired column sum (col_sum2)
+#endif
+// (A/B of the two, profiles/apply_diet_ab.txt: k_backward<0,.,.,16> 2.79-2.94 ms with neither, 2.69-2.83 with the staging,
+//  2.81-2.93 with the paired sum alone, 2.63-2.77 with both; bit-identical outputs; with both 0 the code before them)
 #ifndef SCAN_PF
 #define SCAN_PF 1      // hops of operator loads in flight in the group-level scan kernels.  These kernels are
                        // bandwidth-bound, not latency-bound (k_scan_inner reads the 345 MB of chunk operators in 65 us):
@@ -313,6 +321,18 @@ __device__ __forceinline__ float col_sum(float v) {
     a += b; b = a;
     swap32(a, b);
     return a + b;
+}
+// two independent column sums at once: three swaps and two adds where two col_sum take four and four.
+// (u_i, w_i: the values in 16-lane row i)  swap16(u, w) leaves [u0 w0 u2 w2] and [u1 w1 u3 w3], their sum is
+// [u0+u1 w0+w1 u2+u3 w2+w3]; swap32 of that with itself and the add give [U W U W] with U = (u0+u1) + (u2+u3),
+// the association of col_sum, so the bits are col_sum's; the last swap16 spreads U and W over all rows.
+__device__ __forceinline__ void col_sum2(float u, float w, float &su, float &sw) {
+    swap16(u, w);
+    float c = u + w, d = c;
+    swap32(c, d);
+    float e = c + d, f = e;
+    swap16(e, f);
+    su = e; sw = f;
 }
 __device__ __forceinline__ float col_max(float v) {
     float a = v, b = v;
@@ -1701,10 +1721,23 @@ __device__ __forceinline__ OutStage make_outstage(float *seg, char *base, int q,
 __device__ __forceinline__ void stage_row(const OutStage &o, int n, int g, int s, f4 v) {
     float *p = o.seg + n * OUT_STRIDE + s * o.q + 4 * g;
     const int nv = o.q - 4 * g;
+#if HMM_STAGE_BF
+    // Four unconditional writes, for every q and both walking directions: a component that is not in the row
+    // (state 4g + i >= q; all four where the lane's window lies outside the row) goes to float i of the chain's
+    // 4-float pad at the end of its OUT_STRIDE instead — nothing reads the pad (flush_rows and decode_rows stop
+    // below HMM_OUT_ROWS * q <= HMM_OUT_ROWS * QP floats, permute_rows' blocks end there too).  The predicates are
+    // the lane's own for the whole kernel, so a write costs one select on its address and no exec-mask region.
+    float *d = o.seg + n * OUT_STRIDE + HMM_OUT_ROWS * QP;
+    (nv >= 1 ? p : d)[0] = v.x;
+    (nv >= 2 ? p : d)[1] = v.y;
+    (nv >= 3 ? p : d)[2] = v.z;
+    (nv >= 4 ? p : d)[3] = v.w;
+#else
     if (nv >= 1) p[0] = v.x;
     if (nv >= 2) p[1] = v.y;
     if (nv >= 3) p[2] = v.z;
     if (nv >= 4) p[3] = v.w;
+#endif
 }
 
 // write the staged rows row0 .. row0+nrows-1 (chunk-relative; nrows a multiple of 4, at most
@@ -2192,7 +2225,13 @@ __device__ __forceinline__ void backward_body(const float *__restrict__ A, const
     // chunk): no per-lane "is this step mine" selects
     auto block = [&](auto fullc, int j, const f4 *er) __attribute__((always_inline)) {
         constexpr bool FULL = decltype(fullc)::value;
-        const int srow = (j % (HMM_OUT_ROWS / BS)) * BS;               // where this block's rows sit in the staged group
+        int srow = (j % (HMM_OUT_ROWS / BS)) * BS;                     // where this block's rows sit in the staged group
+#if HMM_STAGE_BF
+        // With BS == HMM_OUT_ROWS this is the constant 0 and the 4 * BS selected row addresses of stage_row are the
+        // same in every block: hoisted out of the block loop they cost k_backward<0, ., ., 16> 50 registers and its
+        // second wave per SIMD.  Opaque here, they are formed next to their writes.
+        asm volatile("" : "+s"(srow));
+#endif
         f4 e[BS];
 #pragma unroll
         for (int s = 0; s < BS; ++s) e[s] = clampE(er[s], bd);
@@ -2223,12 +2262,18 @@ __device__ __forceinline__ void backward_body(const float *__restrict__ A, const
 #pragma unroll
         for (int s = BS - 1; s >= 0; --s) {
             const bool act = FULL || j * BS + s < tl.len;
+            // gamma's normaliser Sg and the backward normaliser S both hang on Rv alone: summed as a pair
+            constexpr bool PAIR = HMM_COLSUM2 && MODE != 3;
+            const f4 sf = PSI ? mul_abs4(Rv, e[s]) : e[s] * Rv;
+            float S;
             if (MODE == 3) {
                 float base = (float)(lbb + (double)lacc);
                 stage_row(os, n, g, srow + s, log4(Rv) + base);
             } else {
                 f4 gm = fa[s] * Rv;                     // PSI: negative where exactly one of the two clamps was active
-                float Sg = col_sum(PSI ? hsum_abs(gm) : hsum(gm));
+                float Sg;
+                if (PAIR) col_sum2(PSI ? hsum_abs(gm) : hsum(gm), hsum(sf), Sg, S);
+                else Sg = col_sum(PSI ? hsum_abs(gm) : hsum(gm));
                 const float ig = __builtin_amdgcn_rcpf(Sg);
                 if (PSI) ps = fmaf(hsum_neg(gm), act ? ig : 0.f, ps);
                 if (MODE == 0) {
@@ -2239,8 +2284,7 @@ __device__ __forceinline__ void backward_body(const float *__restrict__ A, const
                 stage_row(os, n, g, srow + s, gm);
             }
             if (CERT3 && s == 0) { Rc = Rv; Gc = Gv; ec0 = e[0]; }   // (the last block executed is the chunk's first)
-            f4 sf = PSI ? mul_abs4(Rv, e[s]) : e[s] * Rv;
-            float S = col_sum(hsum(sf));
+            if (!PAIR) S = col_sum(hsum(sf));
             const float iS = __builtin_amdgcn_rcpf(S);
             f4 bh = sf * iS;
             const f4 U = mfma4(ab, bh);
