@@ -275,12 +275,15 @@ class MsaHmmLayer(nn.Module):
         """Class posteriors (k,b,L,C): per position the sum of the state posteriors of every class of `state_class` (a
         sequence or an integer tensor of q classes), as logs (log=True; -inf for a class of posterior 0) or
         probabilities — what a model labelled by class is trained on; the trainable counterpart of posterior_decode.
-        With gradients wanted: one autograd node on the per-sequence walks for 65..256 states and at most 16 classes
-        where the transitioner's support_grad asks for them (autograd.class_posterior: neither the (k,b,L,q) posterior
-        nor a gradient of that size is written), else state posteriors collapsed by torch ops.  Without gradients on a
-        HIP device the fused forward where posterior_decode would take its fused call for this model
-        (hmm_posterior_walk_pays, and above 128 states only a GenePredMultiHMMTransitioner), else engine.posterior
-        collapsed; elsewhere a step-at-a-time posterior collapsed."""
+        With gradients wanted: autograd.class_posterior, which takes one fused autograd node (neither the (k,b,L,q)
+        posterior nor a gradient of that size is written) for up to 16 states and at most 16 classes where
+        hmm_class_posterior_grad_pays says 1, and on the per-sequence walks for 65..256 states and at most 16 classes
+        where the transitioner's support_grad asks for them; else state posteriors collapsed by torch ops.  Without
+        gradients on a HIP device: for up to 16 states and at most 16 classes the fused forward
+        (engine.class_posterior) where hmm_class_posterior_pays says 1; for 65..256 states the fused forward where
+        posterior_decode would take its fused call for this model (hmm_posterior_walk_pays, and above 128 states only a
+        GenePredMultiHMMTransitioner); else engine.posterior collapsed.  Elsewhere a step-at-a-time posterior
+        collapsed."""
         mode = engine.POST_LOG if log else engine.POST_PROB
         if state_class is None:
             raise ValueError("class_posterior_log_probs needs a class table (state_class)")
@@ -293,6 +296,9 @@ class MsaHmmLayer(nn.Module):
         table, C = engine.class_table(state_class, num_classes, q)
         if E.is_cuda:
             lib = engine.lib()
+            if C <= 16 and q <= engine.CLASS_MAX_STATES and lib.hmm_class_posterior_pays(*E.shape) == 1:
+                prob, logp, _ = engine.class_posterior(A, pi, E, table, C, eps=self.cell.epsilon, prob=not log, log=log)
+                return logp if log else prob
             if (C <= 16 and lib.hmm_posterior_walk_min_states() <= q <= lib.hmm_posterior_walk_max_states()
                     and lib.hmm_posterior_walk_pays(*E.shape) == 1
                     and (q <= 128 or isinstance(self.cell.transitioner, GenePredMultiHMMTransitioner))):

@@ -183,14 +183,44 @@ class ClassPosterior(torch.autograd.Function):
                 None, None, None, None)
 
 
-def class_posterior(A, pi, E, state_class, num_classes=None, mode=engine.POST_LOG, eps=engine.EPS, support_only=False):
+class ClassPosteriorSmall(torch.autograd.Function):
+    """Class posteriors (k,b,L,C) of models of up to 16 states, probabilities or logs, differentiable in A, pi and E:
+    forward = hmm_class_posterior (the chunked pipeline of posterior() with the class sums as its output), backward =
+    hmm_class_posterior_grad (posterior_grad's sweeps reading the upstream gradient per class).  Saved between the two:
+    A, pi, E and the (k,b,L,C) probabilities; neither the state posteriors nor a gradient of their size exist."""
+
+    @staticmethod
+    def forward(ctx, A, pi, E, table, C, mode, eps):
+        A, pi, E = A.contiguous(), pi.contiguous(), E.contiguous()
+        log = int(mode) == engine.POST_LOG
+        prob, logp, _ = engine.class_posterior(A, pi, E, table, C, eps=eps, prob=True, log=log)
+        ctx.save_for_backward(A, pi, E, prob)
+        ctx.table, ctx.C, ctx.mode, ctx.eps = table, C, int(mode), eps
+        return logp if log else prob
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        A, pi, E, prob = ctx.saved_tensors
+        dA, dpi, dE = engine.class_posterior_grad(A, pi, E, ctx.table, ctx.C, grad_out.to(torch.float32).contiguous(),
+                                                  class_prob=prob, mode=ctx.mode, eps=ctx.eps)
+        need = ctx.needs_input_grad
+        return (dA if need[0] else None, dpi.reshape(pi.shape) if need[1] else None, dE if need[2] else None,
+                None, None, None, None)
+
+
+def class_posterior(A, pi, E, state_class, num_classes=None, mode=engine.POST_LOG, eps=engine.EPS, support_only=False,
+                    fused=None):
     """Differentiable class posteriors (k,b,L,C): P_c[t] = the sum of the state posteriors of the states that
     `state_class` maps to class c (mode engine.POST_PROB), or log P (POST_LOG; -inf where P is 0).  For 65..256 states
     and at most 16 classes, support_only="always", or True where hmm_class_posterior_walk_pays says 1, takes the fused
     node (ClassPosterior: nothing of size (k,b,L,q) but E and its gradient exists; the gradient for A is exactly 0
-    wherever A == 0, as in posterior()).  Everything else — any other q the engine serves, more classes, False —
-    composes posterior(POST_PROB, support_only=support_only) with engine.collapse_posterior (and log) in torch ops.
-    On both routes a class whose posterior is exactly 0 gives -inf in POST_LOG and passes no gradient."""
+    wherever A == 0, as in posterior()).  For up to 16 states, at most 16 classes and E on a HIP device, `fused`
+    chooses the fused node of that range (ClassPosteriorSmall: hmm_class_posterior + hmm_class_posterior_grad, nothing
+    of size (k,b,L,q) but E and its gradient): None takes it where hmm_class_posterior_grad_pays says 1, True takes it
+    without asking (ValueError outside the range or off the device), False never.  Everything else — 17..64 states,
+    any other q the engine serves, more classes, a CPU tensor — composes posterior(POST_PROB,
+    support_only=support_only) with engine.collapse_posterior (and log) in torch ops.
+    On every route a class whose posterior is exactly 0 gives -inf in POST_LOG and passes no gradient."""
     if support_only not in (False, True, "always"):
         raise ValueError("support_only must be False, True or \"always\", got %r" % (support_only,))
     if int(mode) not in (engine.POST_PROB, engine.POST_LOG):
@@ -199,6 +229,14 @@ def class_posterior(A, pi, E, state_class, num_classes=None, mode=engine.POST_LO
     if state_class is None:
         raise ValueError("class_posterior needs a class table (state_class)")
     table, C = engine.class_table(state_class, num_classes, q)
+    if fused not in (None, True, False):
+        raise ValueError("fused must be None, True or False, got %r" % (fused,))
+    small = q <= engine.CLASS_MAX_STATES and C <= 16 and E.is_cuda
+    if fused is True and not small:
+        raise ValueError("class_posterior(fused=True) serves up to %d states and 16 classes on a HIP device, got q = %d, "
+                         "C = %d on %s" % (engine.CLASS_MAX_STATES, q, C, E.device))
+    if small and (fused is True or (fused is None and engine.lib().hmm_class_posterior_grad_pays(*E.shape) == 1)):
+        return ClassPosteriorSmall.apply(A, pi, E, table, C, mode, eps)
     if support_only and C <= 16:
         L = engine.lib()
         if L.hmm_posterior_walk_min_states() <= q <= L.hmm_posterior_walk_max_states() and (

@@ -1791,6 +1791,18 @@ struct alignas(64) Decode {
     unsigned char *label;        // (k,b,L)
     float *conf;                 // (k,b,L) or null
     int ncls;                    // number of classes; 0: the identity map (no sums)
+    void advance(size_t rows) { label += rows; if (conf) conf += rows; }      // host: a batch group's first row
+};
+// ClassOut (hmm_class_posterior): Decode without the argmax — the same staging, weight table and class-sum loop, so
+// the sums have the bits Decode compares — and every class's sum is stored: (k,b,L,ncls) floats to `prob` and / or
+// `logp`, where an elementwise kernel turns them into their logs after the pass (hmm_class_posterior.inc).
+struct alignas(64) ClassOut {
+    static constexpr bool on = true;
+    float w[QP][QP];             // w[c][s] = 1 where state s belongs to class c, else 0
+    float *prob;                 // (k,b,L,ncls) or null
+    float *logp;                 // (k,b,L,ncls) or null: receives the sums as well
+    int ncls;                    // 1..QP
+    void advance(size_t rows) { if (prob) prob += rows * ncls; if (logp) logp += rows * ncls; }
 };
 
 // Decode's flush: the chain table holds ROW offsets from `rowbase` (the wave's first row in the (k,b,L) outputs)
@@ -1826,6 +1838,36 @@ __device__ __forceinline__ void decode_rows(const OutStage &o, const Decode &d, 
         const long long at = rowbase + tab[c] + row0 + r;
         __builtin_nontemporal_store((unsigned char)lab, d.label + at);
         if (d.conf) __builtin_nontemporal_store(best, d.conf + at);
+    }
+    __builtin_amdgcn_wave_barrier();
+}
+
+// ClassOut's flush: lane i takes row i % nrows of chain i / nrows as above and stores its ncls sums, ncls floats from
+// 64-bit element offset (row index) * ncls.  The lanes of a store instruction write one float each, ncls floats
+// apart; a row's line is completed by the same lane's next stores, so these are ordinary (cached) stores.
+__device__ __forceinline__ void decode_rows(const OutStage &o, const ClassOut &d, long long rowbase, int lane, int row0,
+                                            int nrows) {
+    const float inv = 1.0f / (float)nrows;
+    const int *tab = reinterpret_cast<const int *>(o.seg + 16 * OUT_STRIDE);
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll 1                                                       // (one row's values in registers at a time)
+    for (int pc = lane; pc < 16 * nrows; pc += 64) {
+        const int c = (int)(((float)pc + 0.5f) * inv);                 // pc / nrows, exact for these ranges
+        const int r = pc - c * nrows;
+        if (r >= tab[16 + c] - row0) continue;                         // (a chain's ragged end; chains the wave does not own)
+        const float *row = o.seg + c * OUT_STRIDE + r * o.q;
+        float v[QP];
+#pragma unroll
+        for (int s = 0; s < QP; ++s) v[s] = s < o.q ? row[s] : 0.f;
+        const long long at = (rowbase + tab[c] + row0 + r) * d.ncls;
+#pragma unroll 1
+        for (int cl = 0; cl < d.ncls; ++cl) {
+            float sum = 0.f;                                           // states in increasing index
+#pragma unroll
+            for (int s = 0; s < QP; ++s) sum = __builtin_fmaf(v[s], d.w[cl][s], sum);
+            if (d.prob) d.prob[at + cl] = sum;
+            if (d.logp) d.logp[at + cl] = sum;
+        }
     }
     __builtin_amdgcn_wave_barrier();
 }
@@ -2178,8 +2220,8 @@ __global__ __launch_bounds__(256) void k_forward(const float *__restrict__ A, co
 // weighed at the chunk's FIRST position with alpha_hat there, one forward step from the chunk scan's prefix vector
 // (prev): psi[chain] = <alpha_hat, Gv> / <alpha_hat, R> there, or the clamp-born share of the backward vector
 // itself where the chunk hands over to the one before, if that is larger (log beta is a statement about that vector).
-// DEC: the output policy (MODE 0): NoDecode stores the gamma rows, Decode their class labels (decode_rows); everything
-// up to the staged rows is shared.
+// DEC: the output policy (MODE 0): NoDecode stores the gamma rows, Decode their class labels, ClassOut their class sums
+// (decode_rows); everything up to the staged rows is shared.
 template <int MODE, int KIND, bool CERT3 = false, int BS = SUB, class DEC = NoDecode>
 __device__ __forceinline__ void backward_body(const float *__restrict__ A, const float *__restrict__ E, f4 Rv, double lbb0,
                                               float llf, const float *__restrict__ ck, size_t ckb,
@@ -2390,14 +2432,14 @@ __global__ __launch_bounds__(256) void k_backward(const float *__restrict__ A, c
     if (!EXACT && rstart && tl.valid) *reinterpret_cast<f4 *>(rstart + (size_t)tl.chain * QP + 4 * g) = re;
 }
 
-// k_backward<0, false, false, BS> with the Decode output policy (hmm_posterior_decode)
+// k_backward<0, false, false, BS> with the Decode output policy (hmm_posterior_decode) or ClassOut (hmm_class_posterior)
 // (two blocks per compute unit, as k_backward<0> reaches on its own: at 16 steps per block the kernel sits at the edge
 // of the 256 registers that allows, and the decode flush must not tip it over)
-template <int BS>
+template <int BS, class DEC = Decode>
 __global__ __launch_bounds__(256, 2) void k_backward_decode(const float *__restrict__ A, const float *__restrict__ E,
                                                          const float *__restrict__ ckpt, const float *__restrict__ suffix,
                                                          float *__restrict__ psi, float *__restrict__ rstart, Routing rt,
-                                                         Plan p, float eps, long long nwaves, const Decode dec) {
+                                                         Plan p, float eps, long long nwaves, const DEC dec) {
     const long long wave = (long long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (wave >= nwaves) return;
     const int lane = threadIdx.x & 63, g = lane >> 4, n = lane & 15;
@@ -2409,8 +2451,8 @@ __global__ __launch_bounds__(256, 2) void k_backward_decode(const float *__restr
     const f4 R0 = *reinterpret_cast<const f4 *>(suffix + (size_t)tl.chain * QP + 4 * g);
     const float *ck = ckpt + ckpt_origin(tl, p, g, n);
     f4 re;
-    backward_body<0, KIND_SCAN, false, BS, Decode>(A, E, R0, 0.0, 0.f, ck, ckpt_block(p), nullptr, psi, tl, m, seg, p, eps,
-                                                   &re, nullptr, nullptr, dec);
+    backward_body<0, KIND_SCAN, false, BS, DEC>(A, E, R0, 0.0, 0.f, ck, ckpt_block(p), nullptr, psi, tl, m, seg, p, eps,
+                                                &re, nullptr, nullptr, dec);
     if (rstart && tl.valid) *reinterpret_cast<f4 *>(rstart + (size_t)tl.chain * QP + 4 * g) = re;
 }
 
@@ -2764,7 +2806,8 @@ __global__ __launch_bounds__(256) void k_window_posterior(const float *__restric
                 wshift);
 }
 
-// k_window_posterior<0> with the Decode output policy (hmm_posterior_decode)
+// k_window_posterior<0> with the Decode output policy (hmm_posterior_decode) or ClassOut (hmm_class_posterior)
+template <class DEC = Decode>
 __global__ __launch_bounds__(256) void k_window_decode(const float *__restrict__ A, const float *__restrict__ E,
                                                        const float *__restrict__ prefix, const double *__restrict__ llpre,
                                                        const float *__restrict__ suffix, const float *__restrict__ xend,
@@ -2772,10 +2815,10 @@ __global__ __launch_bounds__(256) void k_window_decode(const float *__restrict__
                                                        double *__restrict__ loglik, int *__restrict__ wtab,
                                                        const int *__restrict__ wlist, int *__restrict__ wcnt,
                                                        int *__restrict__ flags, double *__restrict__ dfix, Plan p, float eps,
-                                                       int ext0, const Decode dec) {
+                                                       int ext0, const DEC dec) {
     __shared__ __attribute__((aligned(16))) float ostage[4 * OUT_SEG];
     float *seg = ostage + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * OUT_SEG;
-    PostWindows<0, Decode> pol;
+    PostWindows<0, DEC> pol;
     pol.out = nullptr;
     pol.dec = &dec;
     window_walk(pol, A, E, prefix, llpre, suffix, xend, rstart, ckpt, loglik, wtab, wlist, wcnt, flags, dfix, p, eps, ext0, seg,
@@ -3017,11 +3060,12 @@ __global__ __launch_bounds__(256) void k_exact_posterior(const float *__restrict
     backward_body<MODE, KIND_EXACT>(A, E, ones4(p.q, g), 0.0, (float)ll, ck, ckpt_block(p), out, nullptr, tl, m, seg, p, eps);
 }
 
-// k_exact_posterior<0> with the Decode output policy (hmm_posterior_decode)
+// k_exact_posterior<0> with the Decode output policy (hmm_posterior_decode) or ClassOut (hmm_class_posterior)
+template <class DEC = Decode>
 __global__ __launch_bounds__(256) void k_exact_decode(const float *__restrict__ A, const float *__restrict__ pi,
                                                       const float *__restrict__ E, float *__restrict__ ckpt,
                                                       double *__restrict__ loglik, Routing rt, Plan p, float eps,
-                                                      long long nwaves, const Decode dec) {
+                                                      long long nwaves, const DEC dec) {
     const long long wave = (long long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (wave >= nwaves) return;
     const int lane = threadIdx.x & 63, g = lane >> 4, n = lane & 15;
@@ -3035,8 +3079,8 @@ __global__ __launch_bounds__(256) void k_exact_decode(const float *__restrict__ 
                                                             ckpt_block(p), nullptr, tl, m, seg, p, eps);
     if (tl.valid && g == 0) loglik[tl.chain] = ll;
     __threadfence();
-    backward_body<0, KIND_EXACT, false, SUB, Decode>(A, E, ones4(p.q, g), 0.0, 0.f, ck, ckpt_block(p), nullptr, nullptr, tl, m,
-                                                     seg, p, eps, nullptr, nullptr, nullptr, dec);
+    backward_body<0, KIND_EXACT, false, SUB, DEC>(A, E, ones4(p.q, g), 0.0, 0.f, ck, ckpt_block(p), nullptr, nullptr, tl, m,
+                                                  seg, p, eps, nullptr, nullptr, nullptr, dec);
 }
 
 // ------------------------------------------------------------------ small kernels
@@ -3552,3 +3596,4 @@ int hmm_loglik_partials(const double *loglik, const float *weights, int k, int b
 #include "hmm_gradwq.inc"
 #include "hmm_postgrad_large.inc"
 #include "hmm_postgradwq.inc"
+#include "hmm_class_posterior.inc"

@@ -82,6 +82,26 @@ __device__ __forceinline__ void pg_local(float G, float al, float rb, bool act, 
     }
 }
 
+// Where a state reads its upstream gradient: the G loader of every adjoint sweep (here and in
+// hmm_postgrad_chunked.inc).  PgStateG: G is (k,b,L,q) and state x of position t reads G[t][x] — hmm_posterior_grad.
+// PgClassG: G is (k,b,L,C) and a state reads its CLASS's entry, G[t][class(x)], in place — hmm_class_posterior_grad
+// (hmm_class_posterior.inc); the table travels by value, four bits per state.
+//   seq(row, L, q)  row 0 of sequence `row`;  stride(q)  floats per position;  col(x)  state x's entry within a position
+struct PgStateG {
+    const float *G;
+    __device__ __forceinline__ const float *seq(size_t row, int L, int q) const { return G + row * L * q; }
+    __device__ __forceinline__ int stride(int q) const { return q; }
+    __device__ __forceinline__ int col(int x) const { return x; }
+};
+struct PgClassG {
+    const float *G;
+    unsigned long long cls;                       // class of state s in bits 4 s .. 4 s + 3 (q <= 16)
+    int C;
+    __device__ __forceinline__ const float *seq(size_t row, int L, int) const { return G + row * L * C; }
+    __device__ __forceinline__ int stride(int) const { return C; }
+    __device__ __forceinline__ int col(int x) const { return (int)(cls >> (4 * (x & 15))) & 15; }
+};
+
 struct PgSide {
     float inv_sg, g_over_gamma, g_tiny, g_all;    // sum 1 / Sg_t;  sum |G| / gamma over gamma >= PG_TINY_GAMMA;  sum |G| below it;  sum |G|
     float zman;                                   // product of the steps' normalisers = zman * 2^zexp
@@ -94,10 +114,10 @@ struct PgSide {
 // with Rbar_in = d loss / d Rb_{t0} (0 for t0 = 0: position 0 has only its own output term) and leaves
 // d loss / d Rb_{t1} in *Rbar_out.  ACC: store dEb and the sweep's part of dA (row x of it in lane x: gp[i]).
 // side (or null): the product of the normalisers Sb_{t+1} of the steps, as zman * 2^zexp.
-template <int QB, bool ACC>
+template <int QB, bool ACC, class GL = PgStateG>
 __device__ __forceinline__ void pg_beta_body(const float *__restrict__ A, const float *__restrict__ E,
                                              const float *__restrict__ AH, const float *__restrict__ RB,
-                                             const float *__restrict__ G, int row, int m, int L, int q, float eps, int mode,
+                                             const GL G, int row, int m, int L, int q, float eps, int mode,
                                              int t0, int t1, float Rbar_in, float *Rbar_out, PgSide *side,
                                              float *__restrict__ dEb, float *__restrict__ gp) {
     const int x = threadIdx.x & 63;
@@ -108,17 +128,19 @@ __device__ __forceinline__ void pg_beta_body(const float *__restrict__ A, const 
     for (int i = 0; i < QB; ++i) { acol[i] = (act && i < q) ? Am[(size_t)i * q + x] : 0.f; grow[i] = 0.f; }
     const size_t base = (size_t)row * L * q;
     auto ld = [&](const float *p, int t) { return (act && t < L) ? p[base + (size_t)t * q + x] : 0.f; };
+    const float *Gs = G.seq((size_t)row, L, q);
+    const int gq = G.stride(q), gx = G.col(x);
     float rbs = ld(RB, t0);
     float Rbar = Rbar_in;
     if (t0 == 0) {                                           // R-bar of position 0: only the output term
         float unused;
-        pg_local(ld(G, 0), __builtin_fabsf(ld(AH, 0)), __builtin_fabsf(rbs), act, mode, &Rbar, &unused);
+        pg_local(act ? Gs[gx] : 0.f, __builtin_fabsf(ld(AH, 0)), __builtin_fabsf(rbs), act, mode, &Rbar, &unused);
         if (ACC && act) dEb[base + x] = 0.f;                 // bh_0 feeds nothing
     }
     // the rows of position t + 1 for the steps t = t0 .. tend - 1, MQ_PF steps ahead and with no branch around the
     // loads (MqRows, hmm_midq.inc: with one row in flight the wave slept a memory latency per step)
     const int tend = min(t1, L - 1);
-    const MqRows rE(E + base, q, x), rR(RB + base, q, x), rA(AH + base, q, x), rG(G + base, q, x);
+    const MqRows rE(E + base, q, x), rR(RB + base, q, x), rA(AH + base, q, x), rG(Gs, gq, gx);
     float ne[MQ_PF], nr[MQ_PF], na[MQ_PF], ng[MQ_PF];
     rE.up(t0 + 1, tend + 1, ne); rR.up(t0 + 1, tend + 1, nr); rA.up(t0 + 1, tend + 1, na); rG.up(t0 + 1, tend + 1, ng);
     float zm = 1.f;
@@ -183,11 +205,11 @@ __device__ __forceinline__ void pg_beta_body(const float *__restrict__ A, const 
 // d loss / d alpha_{t0-1} in *abar_out.  side (or null; the same values in every lane): what the chunked path
 // needs to know about these positions — the routing sums (hmm_postgrad_chunked.inc) and the product of the
 // normalisers S_t as zman * 2^zexp.
-template <int QB, bool ACC>
+template <int QB, bool ACC, class GL = PgStateG>
 __device__ __forceinline__ void pg_alpha_body(const float *__restrict__ A, const float *__restrict__ pi,
                                               const float *__restrict__ E, const float *__restrict__ AH,
                                               const float *__restrict__ Sst, const float *__restrict__ RB,
-                                              const float *__restrict__ G, int row, int m, int L, int q, float eps, int mode,
+                                              const GL G, int row, int m, int L, int q, float eps, int mode,
                                               int t0, int t1, float abar_in, float *abar_out, PgSide *side,
                                               float *__restrict__ dEa, float *__restrict__ gp,
                                               float *__restrict__ dpi_part) {
@@ -206,7 +228,8 @@ __device__ __forceinline__ void pg_alpha_body(const float *__restrict__ A, const
     // rows t1 - 1 .. t0 (alpha_hat one further: the step at t also reads alpha_hat_{t-1}), MQ_PF steps ahead, no branch
     // around the loads; the normalisers S_t come the same way (one value per row, every lane reads it)
     const int alo = max(t0 - 1, 0);
-    const MqRows rE(E + base, q, x), rR(RB + base, q, x), rA(AH + base, q, x), rG(G + base, q, x), rS(Sst + (size_t)row * L, 1, 0);
+    const MqRows rE(E + base, q, x), rR(RB + base, q, x), rA(AH + base, q, x), rG(G.seq((size_t)row, L, q), G.stride(q), G.col(x)),
+        rS(Sst + (size_t)row * L, 1, 0);
     float ne[MQ_PF], nr[MQ_PF], na[MQ_PF], ng[MQ_PF], ns[MQ_PF];
     rE.down(t1 - 1, t0, ne); rR.down(t1 - 1, t0, nr); rA.down(t1 - 1, alo, na); rG.down(t1 - 1, t0, ng); rS.down(t1 - 1, t0, ns);
     float phis = 0.f, c_p = 0.f, c_q = 0.f, c_t = 0.f, zm = 1.f;
@@ -292,11 +315,11 @@ __global__ __launch_bounds__(128) void k_pg_fb(const float *__restrict__ A, cons
         pg_rb_body<QB>(A, E, b, L, q, eps, RB, need);
 }
 
-template <int QB>
+template <int QB, class GL = PgStateG>
 __global__ __launch_bounds__(128) void k_pg_adj(const float *__restrict__ A, const float *__restrict__ pi,
                                                 const float *__restrict__ E, const float *__restrict__ AH,
                                                 const float *__restrict__ S, const float *__restrict__ RB,
-                                                const float *__restrict__ G, int b, int L, int q, float eps, int mode,
+                                                const GL G, int b, int L, int q, float eps, int mode,
                                                 float *__restrict__ dEb, float *__restrict__ dEa,
                                                 float *__restrict__ gpart_b, float *__restrict__ gpart_a,
                                                 float *__restrict__ dpi_part, const int *__restrict__ need) {
@@ -361,16 +384,16 @@ static void make_pgplan(int k, int b, int L, int q, PgPlan *p) {
     p->total = off;
 }
 
-template <int QB>
+template <int QB, class GL>
 static void pg_launch(const float *A, const float *pi, const float *E, int k, int b, int L, int q, float eps, int mode,
-                      const float *G, float *dA, float *dE, char *ws, const PgPlan &pp, hipStream_t st,
+                      const GL G, float *dA, float *dE, char *ws, const PgPlan &pp, hipStream_t st,
                       const int *need = nullptr) {
     const dim3 grid((unsigned)(k * b));
     float *AH = (float *)(ws + pp.o_ah), *RB = (float *)(ws + pp.o_rb), *S = (float *)(ws + pp.o_s);
     float *dEa = (float *)(ws + pp.o_dea);
     float *gb = (float *)(ws + pp.o_gpart), *ga = (float *)(ws + pp.o_gpart2), *dpp = (float *)(ws + pp.o_dpi);
     hipLaunchKernelGGL((k_pg_fb<QB>), grid, dim3(128), 0, st, A, pi, E, b, L, q, eps, AH, (double *)(ws + pp.o_ll), S, RB, need);
-    hipLaunchKernelGGL((k_pg_adj<QB>), grid, dim3(128), 0, st, A, pi, E, (const float *)AH, (const float *)S,
+    hipLaunchKernelGGL((k_pg_adj<QB, GL>), grid, dim3(128), 0, st, A, pi, E, (const float *)AH, (const float *)S,
                        (const float *)RB, G, b, L, q, eps, mode, dE, dEa, gb, ga, dpp, need);
     const size_t n = (size_t)k * b * L * q;
     hipLaunchKernelGGL(k_pg_merge, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, E, (const float *)dEa, dE, n, eps);
@@ -421,15 +444,15 @@ int hmm_posterior_grad(const float *A, const float *pi, const float *E, int k, i
         int rc = make_pcplan(k, b, L, q, &pc);
         if (rc) return rc;
         if (workspace_bytes < pc.total || ((uintptr_t)workspace & 255)) return HMM_ERR_WORKSPACE;
-        return pc_launch(A, pi, E, k, b, L, q, eps, mode, grad_out, dA, dpi, dE, ws, pc, st);
+        return pc_launch(A, pi, E, k, b, L, q, eps, mode, PgStateG{grad_out}, dA, dpi, dE, ws, pc, st);
     }
     PgPlan pp;
     make_pgplan(k, b, L, q, &pp);
     if (workspace_bytes < pp.total || ((uintptr_t)workspace & 255)) return HMM_ERR_WORKSPACE;
-    if (q <= 16) pg_launch<16>(A, pi, E, k, b, L, q, eps, mode, grad_out, dA, dE, ws, pp, st);
-    else if (q <= 32) pg_launch<32>(A, pi, E, k, b, L, q, eps, mode, grad_out, dA, dE, ws, pp, st);
-    else if (q <= 48) pg_launch<48>(A, pi, E, k, b, L, q, eps, mode, grad_out, dA, dE, ws, pp, st);
-    else pg_launch<64>(A, pi, E, k, b, L, q, eps, mode, grad_out, dA, dE, ws, pp, st);
+    if (q <= 16) pg_launch<16>(A, pi, E, k, b, L, q, eps, mode, PgStateG{grad_out}, dA, dE, ws, pp, st);
+    else if (q <= 32) pg_launch<32>(A, pi, E, k, b, L, q, eps, mode, PgStateG{grad_out}, dA, dE, ws, pp, st);
+    else if (q <= 48) pg_launch<48>(A, pi, E, k, b, L, q, eps, mode, PgStateG{grad_out}, dA, dE, ws, pp, st);
+    else pg_launch<64>(A, pi, E, k, b, L, q, eps, mode, PgStateG{grad_out}, dA, dE, ws, pp, st);
     hipLaunchKernelGGL(k_pg_sum_rows, dim3(q, k), dim3(64), 0, st, (const float *)(ws + pp.o_dpi), dpi, b, q);
     return check_launch();
 }

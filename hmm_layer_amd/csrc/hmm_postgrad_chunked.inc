@@ -345,10 +345,10 @@ __device__ __forceinline__ void pc_range(const Plan &p, int c, int dir, int *t0,
 //   dir 1  abar_in = d loss / d alpha_hat_{t1-1} (from the future) -> d loss / d alpha_hat_{t0-1}, positions t1-1 .. t0
 // ACC: store dE and the chunk's part of dA (row x of it in lane x) and of dpi.  Returns the leaving vector;
 // sd: the routing sums and the product of the normalisers (valid in every lane of the row).
-template <int W, bool ACC>
+template <int W, bool ACC, class GL = PgStateG>
 __device__ __forceinline__ float pc_beta_sweep(const PcRow &r, const float *__restrict__ A, const float *__restrict__ E,
                                                const float *__restrict__ AH, const float *__restrict__ RB,
-                                               const float *__restrict__ G, const Plan &p, float eps, int mode, int t0,
+                                               const GL G, const Plan &p, float eps, int mode, int t0,
                                                int t1, float Rbar_in, PgSide *sd, float *__restrict__ dEb,
                                                float *__restrict__ gp) {
     const int q = p.q, L = p.L, x = r.x;
@@ -359,19 +359,22 @@ __device__ __forceinline__ float pc_beta_sweep(const PcRow &r, const float *__re
     for (int i = 0; i < W; ++i) { acol[i] = (act && i < q) ? Am[(size_t)i * q + x] : 0.f; grow[i] = 0.f; }
     const size_t base = r.base;
     auto ld = [&](const float *ptr, int t) { return (act && t < L) ? ptr[base + (size_t)t * q + x] : 0.f; };
+    const float *Gx = G.seq((size_t)r.seq, L, q) + G.col(x);          // the loader (hmm_postgrad.inc): this state's column
+    const int gq = G.stride(q);
+    auto ldG = [&](int t) { return (act && t < L) ? Gx[(size_t)t * gq] : 0.f; };
     const float uni = x < q ? 1.f / (float)q : 0.f;
     float rbs = ld(RB, t0);
     float Rbar = Rbar_in;
     if (__builtin_amdgcn_ballot_w64(r.valid && t0 == 0) != 0ull) {    // R-bar of position 0: only the output term
         const bool first = r.valid && t0 == 0;
         float ga, gr, isg, gam;
-        pc_local<W>(first ? ld(G, 0) : 0.f, first ? __builtin_fabsf(ld(AH, 0)) : uni, first ? __builtin_fabsf(rbs) : 1.f,
+        pc_local<W>(first ? ldG(0) : 0.f, first ? __builtin_fabsf(ld(AH, 0)) : uni, first ? __builtin_fabsf(rbs) : 1.f,
                  x < q, mode, &ga, &gr, &isg, &gam);
         if (first) Rbar = ga;
         if (ACC && first && act) dEb[base + x] = 0.f;         // bh_0 feeds nothing
     }
     const int nmax = pc_wave_max_i(r.valid ? min(t1, L - 1) - t0 : 0);
-    float e1n = ld(E, t0 + 1), rb1n = ld(RB, t0 + 1), al1n = ld(AH, t0 + 1), g1n = ld(G, t0 + 1);
+    float e1n = ld(E, t0 + 1), rb1n = ld(RB, t0 + 1), al1n = ld(AH, t0 + 1), g1n = ldG(t0 + 1);
     float zm = 1.f;
     int ze = 0;
     for (int n = 0; n < nmax; ++n) {
@@ -379,7 +382,7 @@ __device__ __forceinline__ float pc_beta_sweep(const PcRow &r, const float *__re
         const bool on = r.valid && t < t1 && t + 1 < L;
         const float e1 = on ? fmaxf(e1n, eps) : 1.f, rb1s = on ? rb1n : 1.f, al1 = on ? __builtin_fabsf(al1n) : uni;
         const float G1 = on ? g1n : 0.f;
-        e1n = ld(E, t + 2); rb1n = ld(RB, t + 2); al1n = ld(AH, t + 2); g1n = ld(G, t + 2);
+        e1n = ld(E, t + 2); rb1n = ld(RB, t + 2); al1n = ld(AH, t + 2); g1n = ldG(t + 2);
         const float rb1 = __builtin_fabsf(rb1s);
         const float w = (on && act && __builtin_bit_cast(int, rbs) >= 0) ? Rbar : 0.f;     // clamp of Rb_t passes nothing
         const float sb = x < q ? e1 * rb1 : 0.f;
@@ -410,11 +413,11 @@ __device__ __forceinline__ float pc_beta_sweep(const PcRow &r, const float *__re
     return act ? Rbar : 0.f;
 }
 
-template <int W, bool ACC>
+template <int W, bool ACC, class GL = PgStateG>
 __device__ __forceinline__ float pc_alpha_sweep(const PcRow &r, const float *__restrict__ A, const float *__restrict__ pi,
                                                 const float *__restrict__ E, const float *__restrict__ AH,
                                                 const float *__restrict__ Sst, const float *__restrict__ RB,
-                                                const float *__restrict__ G, const Plan &p, float eps, int mode, int t0,
+                                                const GL G, const Plan &p, float eps, int mode, int t0,
                                                 int t1, float abar_in, PgSide *sd, float *__restrict__ dEa,
                                                 float *__restrict__ gp, float *__restrict__ dpi_part) {
     const int q = p.q, L = p.L, x = r.x;
@@ -425,11 +428,14 @@ __device__ __forceinline__ float pc_alpha_sweep(const PcRow &r, const float *__r
     for (int j = 0; j < W; ++j) { arow[j] = (act && j < q) ? Am[(size_t)x * q + j] : 0.f; grow[j] = 0.f; }
     const size_t base = r.base;
     auto ld = [&](const float *ptr, int t) { return (act && t >= 0) ? ptr[base + (size_t)t * q + x] : 0.f; };
+    const float *Gx = G.seq((size_t)r.seq, L, q) + G.col(x);          // the loader (hmm_postgrad.inc): this state's column
+    const int gq = G.stride(q);
+    auto ldG = [&](int t) { return (act && t >= 0) ? Gx[(size_t)t * gq] : 0.f; };
     auto ldS = [&](int t) { return (r.valid && t >= 0) ? Sst[(size_t)r.seq * L + t] : 1.f; };
     const float uni = x < q ? 1.f / (float)q : 0.f;
     float abar = abar_in;                                    // d loss / d alpha_t from the future
     const int nmax = pc_wave_max_i(r.valid ? t1 - t0 : 0);
-    float en = ld(E, t1 - 1), ahn = ld(AH, t1 - 1), rbn = ld(RB, t1 - 1), gn = ld(G, t1 - 1), Sn = ldS(t1 - 1);
+    float en = ld(E, t1 - 1), ahn = ld(AH, t1 - 1), rbn = ld(RB, t1 - 1), gn = ldG(t1 - 1), Sn = ldS(t1 - 1);
     float phis = 0.f, c_p = 0.f, c_q = 0.f, c_t = 0.f, zm = 1.f;
     int ze = 0;
     for (int n = 0; n < nmax; ++n) {
@@ -437,7 +443,7 @@ __device__ __forceinline__ float pc_alpha_sweep(const PcRow &r, const float *__r
         const bool on = r.valid && t >= t0;
         const float e = on ? fmaxf(en, eps) : 1.f, ahs = on ? ahn : uni, rb = on ? __builtin_fabsf(rbn) : 1.f;
         const float Gt = on ? gn : 0.f, Sv = on ? Sn : 1.f;
-        en = ld(E, t - 1); ahn = ld(AH, t - 1); rbn = ld(RB, t - 1); gn = ld(G, t - 1); Sn = ldS(t - 1);
+        en = ld(E, t - 1); ahn = ld(AH, t - 1); rbn = ld(RB, t - 1); gn = ldG(t - 1); Sn = ldS(t - 1);
         const float al = __builtin_fabsf(ahs);
         float ga, gr, isg, gam;
         pc_local<W>(Gt, al, rb, x < q, mode, &ga, &gr, &isg, &gam);
@@ -480,11 +486,11 @@ __device__ __forceinline__ float pc_alpha_sweep(const PcRow &r, const float *__r
 // ---- the inhomogeneous part of every chunk's map: the adjoint sweeps from a zero vector, nothing stored
 // but the vector leaving the chunk, the routing sums and the products of the normalisers.
 // blockIdx.y: 0 = adjoint of the backward recursion (ascending), 1 = of the forward recursion (descending)
-template <int W>
+template <int W, class GL = PgStateG>
 __global__ __launch_bounds__(64) void k_pc_src(const float *__restrict__ A, const float *__restrict__ pi,
                                                const float *__restrict__ E, const float *__restrict__ AH,
                                                const float *__restrict__ Sst, const float *__restrict__ RB,
-                                               const float *__restrict__ G, const int *__restrict__ topo, Plan p,
+                                               const GL G, const int *__restrict__ topo, Plan p,
                                                float eps, int mode, float *__restrict__ cvec, PgSide *__restrict__ sides) {
     const PcRow r = pc_row<W>(p, topo);
     const int dir = blockIdx.y;
@@ -635,12 +641,35 @@ __global__ __launch_bounds__(64) void k_pc_scan(const float *__restrict__ ops, c
     }
 }
 
-// ---- the sweeps again, from the true entering vectors, storing dE and the chunks' parts of dA and dpi
+// ---- log mode of hmm_class_posterior_grad (hmm_class_posterior.inc): the adjoints run in prob mode on G' = Gc / P, so
+// k_pc_scan's log rule is off, and the class analogue is applied here, between k_pc_scan and k_pc_final: a sequence
+// is flagged when  F sum_{P_c >= 1e-8} |Gc| / P_c + sum_{P_c < 1e-8} |Gc|  >  PC_LOG_EXPOSED sum |Gc|.
+// F is formed as k_pc_scan forms it (the same loads and sums in the same order); the three sums are the pre-pass's
+// (k_cp_quot: `parts` fp64 triples per sequence, summed here in index order).  One wave per sequence.
 template <int W>
+__global__ __launch_bounds__(64) void k_pc_class_rule(const PgSide *__restrict__ sides, const int *__restrict__ topo, Plan p,
+                                                      float eps, int exact_mode, int force,
+                                                      const double *__restrict__ csum, int parts, int *__restrict__ need) {
+    const int seq = blockIdx.x, x = threadIdx.x & 63;
+    if (PcW<W>::model_serial(topo, seq / p.b) || force || exact_mode != HMM_EXACT_AUTO) return;
+    const size_t ch0 = (size_t)seq * p.C;
+    float s = 0.f;
+    for (int c = x; c < p.C; c += 64) s += sides[(size_t)p.nchains + ch0 + c].inv_sg;
+    const float F = mq_wave_sum(s) * eps;
+    double gp = 0.0, gq = 0.0, gt = 0.0;
+    for (int i = 0; i < parts; ++i) {
+        const double *t = csum + ((size_t)seq * parts + i) * 3;
+        gp += t[0]; gq += t[1]; gt += t[2];
+    }
+    if (x == 0 && !(F * (float)gp + (float)gq <= PC_LOG_EXPOSED * (float)gt)) need[seq] = 1;
+}
+
+// ---- the sweeps again, from the true entering vectors, storing dE and the chunks' parts of dA and dpi
+template <int W, class GL = PgStateG>
 __global__ __launch_bounds__(64) void k_pc_final(const float *__restrict__ A, const float *__restrict__ pi,
                                                  const float *__restrict__ E, const float *__restrict__ AH,
                                                  const float *__restrict__ Sst, const float *__restrict__ RB,
-                                                 const float *__restrict__ G, const int *__restrict__ topo,
+                                                 const GL G, const int *__restrict__ topo,
                                                  const int *__restrict__ need, Plan p, float eps, int mode,
                                                  const float *__restrict__ lam, float *__restrict__ dEb,
                                                  float *__restrict__ dEa, float *__restrict__ gpart,
@@ -691,10 +720,11 @@ __global__ __launch_bounds__(256) void k_pc_fold_seq(const float *__restrict__ g
 
 // risk (or null): the dense reduces' per-chain marks flag a sequence as well (hmm_postgrad_scan.inc; hmm_posterior_grad's
 // own paths run without)
-template <int W>
+// csum (or null): the class log rule's sums, `cparts` triples per sequence (k_pc_class_rule)
+template <int W, class GL>
 static int pc_launch_w(const float *A, const float *pi, const float *E, int k, int b, int L, int q, float eps, int mode,
-                       const float *G, float *dA, float *dpi, float *dE, char *ws, const PcPlan &pc, hipStream_t st,
-                       const int *risk = nullptr) {
+                       const GL G, float *dA, float *dpi, float *dE, char *ws, const PcPlan &pc, hipStream_t st,
+                       const int *risk = nullptr, const double *csum = nullptr, int cparts = 0) {
     const Plan &p = pc.p;
     const PgPlan &pp = pc.pg;
     char *wp = ws + pc.o_pg;
@@ -708,13 +738,16 @@ static int pc_launch_w(const float *A, const float *pi, const float *E, int k, i
     const dim3 chains2((unsigned)((p.nchains + 64 / W - 1) / (64 / W)), 2);       // 64 / W chunks per wave
     hipLaunchKernelGGL(k_pc_values<W>, chains2, dim3(64), 0, st, A, E, (const float *)(ws + pc.o_prefix),
                        (const float *)(ws + pc.o_suffix), route, p, eps, AH, S, RB);
-    hipLaunchKernelGGL(k_pc_src<W>, chains2, dim3(64), 0, st, A, pi, E, (const float *)AH, (const float *)S,
+    hipLaunchKernelGGL((k_pc_src<W, GL>), chains2, dim3(64), 0, st, A, pi, E, (const float *)AH, (const float *)S,
                        (const float *)RB, G, route, p, eps, mode, cvec, sides);
     hipLaunchKernelGGL(k_pc_scan<W>, dim3(p.NB, 2), dim3(64), 0, st, (const float *)(ws + pc.o_ops),
                        (const int *)(ws + pc.o_exps), (const float *)AH, (const float *)RB, (const float *)cvec,
                        (const PgSide *)sides, route, p, eps, mode, opt(HMM_OPT_EXACT), opt(HMM_OPT_PGCHUNK) == 2 ? 1 : 0,
                        lam, need, risk);
-    hipLaunchKernelGGL(k_pc_final<W>, chains2, dim3(64), 0, st, A, pi, E, (const float *)AH, (const float *)S,
+    if (csum)
+        hipLaunchKernelGGL(k_pc_class_rule<W>, dim3(p.NB), dim3(64), 0, st, (const PgSide *)sides, route, p, eps,
+                           opt(HMM_OPT_EXACT), opt(HMM_OPT_PGCHUNK) == 2 ? 1 : 0, csum, cparts, need);
+    hipLaunchKernelGGL((k_pc_final<W, GL>), chains2, dim3(64), 0, st, A, pi, E, (const float *)AH, (const float *)S,
                        (const float *)RB, G, route, (const int *)need, p, eps, mode, (const float *)lam, dE, dEa, gpart, dpp);
     if (p.NB <= PC_FOLD_WAVES_MAX_SEQS)
         hipLaunchKernelGGL(k_pc_fold, dim3(q * q, p.NB, 2), dim3(64), 0, st, (const float *)gpart, (const int *)need, p, gb, ga);
@@ -722,14 +755,18 @@ static int pc_launch_w(const float *A, const float *pi, const float *E, int k, i
         hipLaunchKernelGGL(k_pc_fold_seq, dim3(p.NB, 2), dim3(256), 0, st, (const float *)gpart, (const int *)need, p, 2, gb, ga);
     // the serial sweeps for what is flagged (their waves exit at once otherwise), then the common tail.  The redo is
     // hmm_posterior_grad's own instantiation for q, bit for bit: rows of 64 serve 33..48 states with k_pg_*<48>
-    if (W == Q64 && q <= 48) pg_launch<48>(A, pi, E, k, b, L, q, eps, mode, G, dA, dE, wp, pp, st, need);
-    else pg_launch<W>(A, pi, E, k, b, L, q, eps, mode, G, dA, dE, wp, pp, st, need);
+    if constexpr (W == Q64) {
+        if (q <= 48) pg_launch<48>(A, pi, E, k, b, L, q, eps, mode, G, dA, dE, wp, pp, st, need);
+        else pg_launch<W>(A, pi, E, k, b, L, q, eps, mode, G, dA, dE, wp, pp, st, need);
+    } else {
+        pg_launch<W>(A, pi, E, k, b, L, q, eps, mode, G, dA, dE, wp, pp, st, need);
+    }
     hipLaunchKernelGGL(k_pg_sum_rows, dim3(q, k), dim3(64), 0, st, (const float *)dpp, dpi, b, q);
     return check_launch();
 }
 
 static int pc_launch(const float *A, const float *pi, const float *E, int k, int b, int L, int q, float eps, int mode,
-                     const float *G, float *dA, float *dpi, float *dE, char *ws, const PcPlan &pc, hipStream_t st) {
+                     const PgStateG G, float *dA, float *dpi, float *dE, char *ws, const PcPlan &pc, hipStream_t st) {
     if (pc.W == QP) {
         int rc = run_reduce_scan(A, pi, E, pc.p, eps, ws, st);
         if (rc) return rc;

@@ -34,7 +34,7 @@ template <class S>
 static int pgs_launch(const float *A, const float *pi, const float *E, int k, int b, int L, int q, float eps, int mode,
                       const float *G, float *dA, float *dpi, float *dE, char *ws, const PcPlan &pc, hipStream_t st) {
     scan_reduce_scan<S>(A, pi, E, pc.mid, eps, ws, st);
-    return pc_launch_w<S::W>(A, pi, E, k, b, L, q, eps, mode, G, dA, dpi, dE, ws, pc, st, (const int *)(ws + pc.mid.o_risk));
+    return pc_launch_w<S::W>(A, pi, E, k, b, L, q, eps, mode, PgStateG{G}, dA, dpi, dE, ws, pc, st, (const int *)(ws + pc.mid.o_risk));
 }
 
 extern "C" {

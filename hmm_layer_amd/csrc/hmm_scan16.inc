@@ -266,10 +266,11 @@ static int s16_backward(const float *A, const float *E, const Plan &p, float eps
 // The apply stage of the posterior, after run_reduce_scan on the same plan: forward (checkpoints), backward (out), then
 // the serial kernels for what is routed (allow_exact; not for a time slab of a sequence-sharded call).
 // dec (hmm_posterior_decode; mode HMM_POST_PROB, no `out`): the same launches with the backward, window and
-// whole-sequence kernels in their Decode form.
+// whole-sequence kernels in their Decode form; DEC = ClassOut (hmm_class_posterior): the same with that policy.
+template <class DEC = Decode>
 static int s16_apply(const float *A, const float *pi, const float *E, const Plan &p, float eps, int mode, char *ws,
                      float *out, double *loglik, hipStream_t st, Profile *pr, bool allow_exact = true,
-                     const Decode *dec = nullptr) {
+                     const DEC *dec = nullptr) {
     Plan px;
     int rc = make_xplan(p, &px);
     if (rc) return rc;
@@ -294,7 +295,7 @@ static int s16_apply(const float *A, const float *pi, const float *E, const Plan
                      : mode == HMM_POST_PROB ? k_backward<0, false>
                      : mode == HMM_POST_LOG ? k_backward<1, false> : k_backward<2, false>;
         if (dec)
-            launch(wide ? k_backward_decode<HMM_POST_BLOCK> : k_backward_decode<SUB>, apply_grid(p), dim3(256), 0, st, A, E,
+            launch(wide ? k_backward_decode<HMM_POST_BLOCK, DEC> : k_backward_decode<SUB, DEC>, apply_grid(p), dim3(256), 0, st, A, E,
                    w.ckpt, w.suffix, w.phi, w.rstart, rt, pb, eps, nw, *dec);
         else
             launch(kern, apply_grid(p), dim3(256), 0, st, A, E, w.ckpt, w.suffix, w.lsuf, w.loglik, out, w.phi, w.rstart,
@@ -303,9 +304,9 @@ static int s16_apply(const float *A, const float *pi, const float *E, const Plan
     if (allow_exact && dec) {
         Timed t(pr, HMM_KERNEL_EXACT, st);
         s16_select(p, w, rt, st);
-        launch(k_window_decode, win_grid(p), dim3(256), 0, st, A, E, w.prefix, w.llpre, w.suffix, w.xend, w.rstart, w.ckpt,
+        launch(k_window_decode<DEC>, win_grid(p), dim3(256), 0, st, A, E, w.prefix, w.llpre, w.suffix, w.xend, w.rstart, w.ckpt,
                w.loglik, w.wtab, w.wlist, w.wcnt, w.flags, w.dfix, p, eps, win_margin(p), *dec);
-        launch(k_exact_decode, apply_grid(px), dim3(256), 0, st, A, pi, E, w.ckpt, w.loglik, routing_flagged(rt, w), px, eps,
+        launch(k_exact_decode<DEC>, apply_grid(px), dim3(256), 0, st, A, pi, E, w.ckpt, w.loglik, routing_flagged(rt, w), px, eps,
                apply_waves(px), *dec);
     } else if (allow_exact) {
         // the serial kernels: per model as k_topo_check decided, per sequence from the clamp-born mass the
@@ -328,9 +329,10 @@ static int s16_apply(const float *A, const float *pi, const float *E, const Plan
 }
 
 // The posterior of every batch group: reduce + scan, then the apply stage.
+template <class DEC = Decode>
 static int s16_posterior(const float *A, const float *pi, const float *E, const Groups &G, float eps, int mode,
                          float *out, double *loglik, char *ws, hipStream_t st, Profile *pr,
-                         const Decode *dec = nullptr) {
+                         const DEC *dec = nullptr) {
     int rc = HMM_OK;
 #ifdef HMM_GROUPS_SERIAL
     hipStream_t *hs = nullptr;
@@ -347,11 +349,8 @@ static int s16_posterior(const float *A, const float *pi, const float *E, const 
             (void)hipEventRecord(*reduced, s0);
             if (rc == HMM_OK) (void)hipStreamWaitEvent(s1, *reduced, 0);
         }
-        Decode dg = dec ? *dec : Decode();                   // this group's rows of the decoded outputs
-        if (dec) {
-            dg.label += (size_t)G.b0[g] * p.L;
-            if (dg.conf) dg.conf += (size_t)G.b0[g] * p.L;
-        }
+        DEC dg = dec ? *dec : DEC();                         // this group's rows of the decoded outputs
+        if (dec) dg.advance((size_t)G.b0[g] * p.L);
         if (rc == HMM_OK)
             rc = s16_apply(A, pi, E + row, p, eps, mode, ws + G.off[g], dec ? nullptr : out + row,
                            loglik ? loglik + G.b0[g] : nullptr, s1, pr, true, dec ? &dg : nullptr);

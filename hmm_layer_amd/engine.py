@@ -194,6 +194,18 @@ CLASS_POSTERIOR_WALK_SIGNATURES = {
     "hmm_class_posterior_grad_walk": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _I, _P, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
 }
 
+# ... and those of the class posteriors with gradients for up to 16 states (hmm_class_posterior,
+# hmm_class_posterior_grad), likewise.
+CLASS_POSTERIOR_SIGNATURES = {
+    "hmm_class_posterior_max_states": (_I, []),
+    "hmm_class_posterior_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "hmm_class_posterior_pays": (_I, [_I, _I, _I, _I]),
+    "hmm_class_posterior": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _P, _I, _P, _P, _P, _P, _SZ, _P]),
+    "hmm_class_posterior_grad_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
+    "hmm_class_posterior_grad_pays": (_I, [_I, _I, _I, _I]),
+    "hmm_class_posterior_grad": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _I, _P, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+}
+
 
 def lib():
     """The loaded shared library (loaded once).  Raises if it has not been built."""
@@ -207,7 +219,8 @@ def lib():
     L = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**_SIGNATURES, **DECODE_SIGNATURES, **DECODE_MID_SIGNATURES,
                                       **POSTERIOR_WALK_SIGNATURES, **LOGLIK_GRAD_WALK_SIGNATURES,
-                                      **POSTERIOR_GRAD_WALK_SIGNATURES, **CLASS_POSTERIOR_WALK_SIGNATURES}.items():
+                                      **POSTERIOR_GRAD_WALK_SIGNATURES, **CLASS_POSTERIOR_WALK_SIGNATURES,
+                                      **CLASS_POSTERIOR_SIGNATURES}.items():
         if not hasattr(L, name):
             raise EngineError("the engine library %s does not export %s: rebuild it with "
                               "`python -m hmm_layer_amd.build`" % (LIB_PATH, name))
@@ -1353,3 +1366,85 @@ def class_posterior_grad_walk_refused(dims, device=None):
     """How many of the k models of the LAST class_posterior_grad_walk call with shape `dims` on this device and stream
     were refused (synchronises): the workspace begins with hmm_posterior_grad_walk's layout."""
     return posterior_grad_serial_count(dims, device, _fn="hmm_posterior_grad_walk_refused", _tag=CLASS_GRAD_WALK_TAG)
+
+
+CLASS_TAG = "class_posterior"              # class_posterior()'s workspace: exact_count(OP_POSTERIOR, ..., tag=CLASS_TAG) reads it
+CLASS_GRAD_TAG = "class_posterior_grad"    # class_posterior_grad()'s: class_posterior_grad_serial_count() reads it
+CLASS_MAX_STATES = 16                      # hmm_class_posterior_max_states(), known without the library
+
+
+def _class_args(name, E, state_class, num_classes):
+    """Checks shared by class_posterior and class_posterior_grad, before the device is asked for
+    -> (table as a ctypes array, C)."""
+    if not torch.is_tensor(E) or E.dim() != 4:
+        raise ValueError("E must be a tensor of shape (k, b, L, q)")
+    q = E.shape[3]
+    if not 1 <= q <= CLASS_MAX_STATES:
+        raise ValueError("%s serves 1..%d states, got q = %d" % (name, CLASS_MAX_STATES, q))
+    if state_class is None:
+        raise ValueError("%s needs a class table (state_class)" % name)
+    table, C = class_table(state_class, num_classes, q)
+    if C > 16:
+        raise ValueError("at most 16 classes, got %d" % C)
+    return (ctypes.c_int * q)(*table), C
+
+
+def class_posterior(A, pi, E, state_class, num_classes=None, eps=EPS, prob=True, log=False):
+    """Class posteriors for up to 16 states by the chunked pipeline of posterior() (hmm_class_posterior)
+    -> (prob (k,b,L,C) fp32 or None, log (k,b,L,C) fp32 or None, loglik (k,b) fp64): P_c[t] = the sum of the state
+    posteriors of class c's states, with the bits posterior_decode's fused call compares; log = its log (-inf for a
+    sum of 0).  Nothing of size (k,b,L,q) is written.  state_class: a sequence or an integer tensor of q classes, at
+    most 16 of them.  Raises ValueError outside 1..16 states, without a table, above 16 classes, or with neither
+    output asked for."""
+    tab, C = _class_args("class_posterior", E, state_class, num_classes)
+    if not (prob or log):
+        raise ValueError("class_posterior: ask for prob, log or both")
+    A, pi, E = _dev(A, "A"), _dev(pi, "pi"), _dev(E, "E")
+    A, pi, dims = _shapes(A, E, pi)
+    with torch.cuda.device(E.device):
+        ws = _workspace(E.device, lib().hmm_class_posterior_workspace_bytes(*dims), CLASS_TAG)
+        P = torch.empty(dims[:3] + (C,), dtype=torch.float32, device=E.device) if prob else None
+        Lg = torch.empty(dims[:3] + (C,), dtype=torch.float32, device=E.device) if log else None
+        ll = torch.empty(dims[:2], dtype=torch.float64, device=E.device)
+        _check(lib().hmm_class_posterior(A.data_ptr(), pi.data_ptr(), E.data_ptr(), *dims, eps, tab, C,
+                                         P.data_ptr() if prob else None, Lg.data_ptr() if log else None,
+                                         ll.data_ptr(), ws.data_ptr(), ws.numel(), _stream(E.device)))
+    return P, Lg, ll
+
+
+def class_posterior_grad(A, pi, E, state_class, num_classes, grad_out, class_prob=None, mode=POST_LOG, eps=EPS):
+    """Gradients of <grad_out, out> with out = the class posteriors (POST_PROB) or their logs (POST_LOG) of
+    class_posterior -> (dA (k,q,q), dpi (k,q), dE (k,b,L,q)) by hmm_class_posterior_grad: grad_out is (k,b,L,C), read
+    in place.  POST_PROB is posterior_grad(POST_PROB) with grad_out[..., state_class], bit for bit; POST_LOG needs
+    class_prob, the forward's prob, and passes nothing through a class whose posterior is 0.  Raises ValueError
+    outside 1..16 states, without a table, above 16 classes, and in log mode without class_prob."""
+    tab, C = _class_args("class_posterior_grad", E, state_class, num_classes)
+    if int(mode) not in (POST_PROB, POST_LOG):
+        raise ValueError("class_posterior_grad supports mode POST_PROB or POST_LOG")
+    if int(mode) == POST_LOG and class_prob is None:
+        raise ValueError("class_posterior_grad: POST_LOG needs class_prob (class_posterior's prob)")
+    A, pi, E, grad_out = _dev(A, "A"), _dev(pi, "pi"), _dev(E, "E"), _dev(grad_out, "grad_out")
+    A, pi, dims = _shapes(A, E, pi)
+    k, b, L, q = dims
+    if tuple(grad_out.shape) != (k, b, L, C):
+        raise ValueError("grad_out must have shape (k, b, L, C) = %s, got %s" % ((k, b, L, C), tuple(grad_out.shape)))
+    if int(mode) == POST_LOG:
+        class_prob = _dev(class_prob, "class_prob")
+        if class_prob.shape != grad_out.shape:
+            raise ValueError("class_prob must be shaped like grad_out")
+    with torch.cuda.device(E.device):
+        ws = _workspace(E.device, lib().hmm_class_posterior_grad_workspace_bytes(*dims, C), CLASS_GRAD_TAG)
+        dA = torch.empty((k, q, q), dtype=torch.float32, device=E.device)
+        dpi = torch.empty((k, q), dtype=torch.float32, device=E.device)
+        dE = torch.empty_like(E)
+        _check(lib().hmm_class_posterior_grad(
+            A.data_ptr(), pi.data_ptr(), E.data_ptr(), *dims, eps, int(mode), tab, C,
+            class_prob.data_ptr() if int(mode) == POST_LOG else None, grad_out.data_ptr(), dA.data_ptr(),
+            dpi.data_ptr(), dE.data_ptr(), ws.data_ptr(), ws.numel(), _stream(E.device)))
+    return dA, dpi, dE
+
+
+def class_posterior_grad_serial_count(dims, device=None):
+    """How many of the k*b sequences of the LAST class_posterior_grad call with shape `dims` on this device and stream
+    were served by the whole-sequence sweeps (synchronises): the workspace begins with hmm_posterior_grad's layout."""
+    return posterior_grad_serial_count(dims, device, _tag=CLASS_GRAD_TAG)

@@ -1288,6 +1288,78 @@ int hmm_class_posterior_grad_walk(const float *A, const float *pi, const float *
                                   const float *grad_out, float *dA, float *dpi, float *dE,
                                   void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * CLASS POSTERIORS WITH ANALYTIC GRADIENTS for q <= 16 states: the trainable counterpart of hmm_posterior_decode, with
+ * the arguments of the 65..256-state pair above, so that a caller switches by q alone.  THIS PAIR SERVES q <= 16 ONLY:
+ * 65..256 states go to hmm_class_posterior_walk / hmm_class_posterior_grad_walk; 17..64 states have no fused class
+ * call yet (it needs hmm_posterior_decode_mid's parking region and is a follow-up) and are composed from hmm_posterior /
+ * hmm_posterior_grad_scan by the caller.  state_class: HOST pointer to q ints in 0..num_classes-1, REQUIRED (the
+ * identity map is hmm_posterior); num_classes 1..16, may exceed q; a class may be empty.
+ *
+ * hmm_class_posterior: the pipeline and routing of hmm_posterior(HMM_POST_PROB) and hmm_posterior_decode (chunked
+ * kernels, windows, exact serial kernels) with a third output policy: the same staging, the same 0/1 weight table by
+ * value and the same class-sum loop (fp32 fma(v, w, sum) over the states in increasing index, from 0.0f), so out_prob
+ * (k,b,L,num_classes) has the bits hmm_posterior_decode compares: out_prob at label is conf, and the lowest argmax of
+ * out_prob is label.  out_log (same shape) is within 2 fp32 ulp of log(out_prob) — the fp64 log rounded once, formed by
+ * an elementwise kernel inside the same call — and -inf for a sum of 0.  Either output may be NULL, not both; every
+ * element of an output given is written.  loglik (k,b) fp64 or NULL is bit for bit hmm_posterior's.
+ * Workspace: hmm_class_posterior_workspace_bytes = hmm_workspace_bytes(HMM_OP_POSTERIOR, ...) (0: unsupported shape or
+ * q); there is no parking region, and hmm_exact_count(HMM_OP_POSTERIOR, ...) reads the routing of a finished call.
+ * One stream, capturable (the table travels by value: a captured graph keeps its table), no atomics, 64-bit offsets
+ * into E and the outputs, bit-identical repetition.
+ * Argument checks, before any HIP call, in this order: shape (HMM_ERR_BAD_SHAPE), q > 16 (HMM_ERR_Q_UNSUPPORTED), NULL
+ * among A, pi, E, state_class, workspace, or both outputs NULL (HMM_ERR_NULL_POINTER), num_classes outside 1..16 or a
+ * table entry outside 0..num_classes-1 (HMM_ERR_BAD_ARGUMENT), workspace too small or not 256-byte aligned
+ * (HMM_ERR_WORKSPACE).
+ *
+ * hmm_class_posterior_grad: gradients of a loss on the class posteriors -> dA (k,q,q), dpi (k,q), dE (k,b,L,q), with
+ * grad_out (k,b,L,num_classes) the upstream gradient Gc:
+ *   HMM_POST_PROB   loss = sum Gc P: hmm_posterior_grad(HMM_POST_PROB) with G[t][j] = Gc[t][class(j)], bit for bit.
+ *                   Gc is read in place: every lane finds its class once and loads Gc[t][class] where the state form
+ *                   loads G[t][j].  class_prob is ignored.
+ *   HMM_POST_LOG    loss = sum Gc log P: the prob-mode adjoint with G'[t][c] = Gc[t][c] / P_c[t], the IEEE fp32
+ *                   quotient, and G' = 0 where P_c == 0.  class_prob (k,b,L,num_classes), REQUIRED, is the forward's
+ *                   out_prob; a pre-pass writes G' into the workspace and the adjoints run in prob mode.
+ * Routing to the whole-sequence sweeps is hmm_posterior_grad's (model support, F <= 2e-6, HMM_OPT_PGCHUNK); log mode adds
+ * the class form of the exposed-weight rule: a sequence is redone whole when
+ *   F sum_{P_c >= 1e-8} |Gc| / P_c + sum_{P_c < 1e-8} |Gc|  >  1e-4 sum |Gc|.
+ * q = 1 gives exact zeros.  No atomics, 64-bit offsets, bit-identical repetition, one stream, capturable.
+ * Workspace: hmm_class_posterior_grad_workspace_bytes(k, b, L, q, num_classes) (0: unsupported shape, q or
+ * num_classes) = hmm_posterior_grad's layout first, rounded up to 256 bytes, then G' and the rule's per-sequence sums.
+ * hmm_posterior_grad_serial_count(k, b, L, q, workspace, workspace_bytes) THEREFORE READS A FINISHED
+ * hmm_class_posterior_grad CALL as it does hmm_posterior_grad's.
+ * Argument checks, before any HIP call and in this order: bad shape -1; q > 16 -2; mode not HMM_POST_PROB /
+ * HMM_POST_LOG -6; a NULL A / pi / E / state_class / grad_out / dA / dpi / dE / workspace, or class_prob in
+ * HMM_POST_LOG, -3; num_classes outside 1..16 or a table entry outside 0..num_classes-1 -6; a small or misaligned
+ * (256 bytes) workspace -4.
+ *
+ * hmm_class_posterior_pays / hmm_class_posterior_grad_pays (k, b, L, q): 1 exactly on the cells
+ * tools/experiments/class_posterior_time.py measured at least 1.25x ahead — the forward alone against hmm_posterior +
+ * the torch collapse + log, and the fused autograd node (both calls) against the composed one — as recorded in
+ * profiles/class_posterior.json; 0 everywhere else, everything not measured included.  As measured on
+ * one MI355X (one model, log mode, a label-style gradient with labels uniform over the classes; 7 states with 4
+ * classes and 15 states with 5; b x L = 1 x 100 000, 32 x 9 999, 1024 x 10 000, 1024 x 100 000): the forward is 1.39x
+ * to 4.79x ahead in all eight cells, which are exactly where hmm_class_posterior_pays is 1 (k = 1; q, b and L as
+ * measured); the node is 0.02x to 1.03x — such labels sit on improbable classes and the log rule above redoes their
+ * sequences whole, which the composed node's prob-mode state call never does — so hmm_class_posterior_grad_pays is 0
+ * everywhere.  Not measured: prob mode, dense gradients, other class counts, b > 1024, k > 1.
+ */
+int hmm_class_posterior_max_states(void);                       /* 16 */
+size_t hmm_class_posterior_workspace_bytes(int k, int b, int L, int q);
+int hmm_class_posterior_pays(int k, int b, int L, int q);
+int hmm_class_posterior(const float *A, const float *pi, const float *E,
+                        int k, int b, int L, int q, float eps,
+                        const int *state_class, int num_classes,
+                        float *out_prob, float *out_log, double *loglik,
+                        void *workspace, size_t workspace_bytes, void *stream);
+size_t hmm_class_posterior_grad_workspace_bytes(int k, int b, int L, int q, int num_classes);
+int hmm_class_posterior_grad_pays(int k, int b, int L, int q);
+int hmm_class_posterior_grad(const float *A, const float *pi, const float *E,
+                             int k, int b, int L, int q, float eps, int mode,
+                             const int *state_class, int num_classes, const float *class_prob,
+                             const float *grad_out, float *dA, float *dpi, float *dE,
+                             void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
