@@ -114,7 +114,7 @@ int hmm_class_posterior(const float *A, const float *pi, const float *E, int k, 
     int rc = make_route(HMM_OP_POSTERIOR, k, b, L, q, &r);
     if (rc) return rc;
     if (!A || !pi || !E || !state_class || !workspace || (!out_prob && !out_log)) return HMM_ERR_NULL_POINTER;
-    if (num_classes < 1 || num_classes > QP) return HMM_ERR_BAD_ARGUMENT;
+    if (num_classes < 1 || num_classes > QP || check_eps(eps)) return HMM_ERR_BAD_ARGUMENT;
     ClassOut cls{};
     cls.prob = out_prob; cls.logp = out_log; cls.ncls = num_classes;
     for (int s = 0; s < q; ++s) {                              // the table is read here, once, and travels by value
@@ -148,7 +148,7 @@ int hmm_class_posterior_grad(const float *A, const float *pi, const float *E, in
     if (!A || !pi || !E || !state_class || !grad_out || !dA || !dpi || !dE || !workspace ||
         (mode == HMM_POST_LOG && !class_prob))
         return HMM_ERR_NULL_POINTER;
-    if (num_classes < 1 || num_classes > QP) return HMM_ERR_BAD_ARGUMENT;
+    if (num_classes < 1 || num_classes > QP || check_eps(eps)) return HMM_ERR_BAD_ARGUMENT;
     PgClassG gl{};
     gl.C = num_classes;
     for (int s = 0; s < q; ++s) {                              // the table is read here, once, and travels by value

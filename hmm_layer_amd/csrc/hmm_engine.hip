@@ -2471,7 +2471,9 @@ __global__ __launch_bounds__(64) void k_exact_select(const int *__restrict__ top
                                                      int exact_mode, int margin, int *__restrict__ flags,
                                                      int *__restrict__ nexact, int *__restrict__ wtab,
                                                      int *__restrict__ wlist, int *__restrict__ wcnt,
-                                                     const int *__restrict__ exps = nullptr) {
+                                                     const int *__restrict__ exps = nullptr,
+                                                     const float *__restrict__ prefix = nullptr,
+                                                     const float *__restrict__ rstart = nullptr, float eps = 0.f) {
     const int seq = blockIdx.x, lane = threadIdx.x;
     const int C = p.C;
     const int tpv = topo[seq / p.b];
@@ -2480,6 +2482,24 @@ __global__ __launch_bounds__(64) void k_exact_select(const int *__restrict__ top
         return;
     }
     float *pc = psi + (size_t)seq * C;
+    // prefix, rstart (the posterior's scan plan): the reverse cell's clamp where chunk c hands over to chunk c - 1.
+    // backward_body clamps and flags the vector that leaves chunk c (rstart[c], R at the last position of chunk c - 1),
+    // but the gamma that weighs those flags belongs to chunk c - 1, whose kernel starts from the chunk scan's suffix
+    // vector: the same direction without the clamp.  Neither kernel sums that term; it is summed here, with alpha_hat
+    // at that position (the chunk scan's prefix of chunk c), and charged to chunk c: chunk c itself is right, what
+    // the birth changes is R before it, which is what a window before a flagged chunk recomputes from rstart[c].
+    if (prefix && exact_mode == HMM_EXACT_AUTO)
+        for (int c = lane; c < C; c += 64) {
+            if (c == 0) continue;
+            const float *a = prefix + ((size_t)seq * C + c) * QP, *r = rstart + ((size_t)seq * C + c) * QP;
+            float born = 0.f, all = 0.f;
+            for (int j = 0; j < p.q; ++j) {
+                const float w = fabsf(a[j]) * r[j];
+                all += w;
+                born += r[j] <= eps ? w : 0.f;
+            }
+            if (born > 0.f) pc[c] += born / all;
+        }
     if (exps && tpv != 0 && exact_mode == HMM_EXACT_AUTO)          // (every later loop visits chunk c from the same lane)
         for (int c = lane; c < C; c += 64)
             if (exps[((size_t)seq * C + c) * QP + QP - 1] != 0) pc[c] = 1.f;
@@ -3247,6 +3267,7 @@ int hmm_forward(const float *A, const float *pi, const float *E, int k, int b, i
     int rc = make_route(log_alpha ? HMM_OP_FORWARD : HMM_OP_LOGLIK, k, b, L, q, &r);
     if (rc) return rc;
     if (!A || !pi || !E || !loglik) return HMM_ERR_NULL_POINTER;
+    if ((rc = check_eps(eps))) return rc;
     if ((rc = check_ws(r.total, workspace, workspace_bytes))) return rc;
     char *ws = (char *)workspace;
     hipStream_t st = (hipStream_t)stream;
@@ -3282,6 +3303,7 @@ int hmm_backward(const float *A, const float *E, int k, int b, int L, int q, flo
     int rc = make_route(HMM_OP_BACKWARD, k, b, L, q, &r);
     if (rc) return rc;
     if (!A || !E || !log_beta) return HMM_ERR_NULL_POINTER;
+    if ((rc = check_eps(eps))) return rc;
     if ((rc = check_ws(r.total, workspace, workspace_bytes))) return rc;
     char *ws = (char *)workspace;
     hipStream_t st = (hipStream_t)stream;
@@ -3309,6 +3331,7 @@ static int posterior_impl(const float *A, const float *pi, const float *E, int k
     if (rc) return rc;
     if (!A || !pi || !E || !out) return HMM_ERR_NULL_POINTER;
     if (mode < HMM_POST_PROB || mode > HMM_POST_LOG_NO_LL) return HMM_ERR_BAD_ARGUMENT;
+    if ((rc = check_eps(eps))) return rc;
     if ((rc = check_ws(r.total, workspace, workspace_bytes))) return rc;
     char *ws = (char *)workspace;
     hipStream_t st = (hipStream_t)stream;
@@ -3362,6 +3385,7 @@ int hmm_posterior_decode(const float *A, const float *pi, const float *E, int k,
     if (rc) return rc;
     if (!A || !pi || !E || !label || !workspace) return HMM_ERR_NULL_POINTER;
     if (num_classes < 1 || num_classes > QP || (!state_class && num_classes != q)) return HMM_ERR_BAD_ARGUMENT;
+    if ((rc = check_eps(eps))) return rc;
     Decode dec{};
     dec.label = label; dec.conf = conf; dec.ncls = state_class ? num_classes : 0;
     for (int s = 0; s < q && state_class; ++s) {               // the table is read here, once, and travels by value
@@ -3394,6 +3418,7 @@ int hmm_posterior_decode_mid(const float *A, const float *pi, const float *E, in
     if (rc) return rc;
     if (!A || !pi || !E || !label || !workspace) return HMM_ERR_NULL_POINTER;
     if (num_classes < 1 || (state_class ? num_classes > QP : num_classes != q)) return HMM_ERR_BAD_ARGUMENT;
+    if ((rc = check_eps(eps))) return rc;
     DecodeMid dec{};
     dec.label = label; dec.conf = conf; dec.ncls = state_class ? num_classes : 0;
     for (int s = 0; s < q && state_class; ++s) {               // the table is read here, once, and travels by value

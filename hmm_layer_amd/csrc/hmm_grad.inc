@@ -394,6 +394,7 @@ int hmm_loglik_grad(const float *A, const float *pi, const float *E, int k, int 
     if (q > QP && q <= MQ_MAX) {                             // one wave per sequence (hmm_midq.inc)
         if (k < 1 || b < 1 || L < 1) return HMM_ERR_BAD_SHAPE;
         if (!A || !pi || !E || !dA || !dpi || !dE || !workspace) return HMM_ERR_NULL_POINTER;
+        if (check_eps(eps)) return HMM_ERR_BAD_ARGUMENT;
         if (pc_llgrad_wanted(k, b, L, q))
             return pc_loglik_grad(A, pi, E, k, b, L, q, eps, grad_loglik, dA, dpi, dE, loglik, (char *)workspace,
                                   workspace_bytes, (hipStream_t)stream);
@@ -407,6 +408,7 @@ int hmm_loglik_grad(const float *A, const float *pi, const float *E, int k, int 
     int rc = make_gradplan(k, b, L, q, &gp);
     if (rc) return rc;
     if (!A || !pi || !E || !dA || !dpi || !dE || !workspace) return HMM_ERR_NULL_POINTER;
+    if ((rc = check_eps(eps))) return rc;
     if (workspace_bytes < gp.total || ((uintptr_t)workspace & 255)) return HMM_ERR_WORKSPACE;
     const Plan &p = gp.p, &px = gp.px;
     char *ws = (char *)workspace;

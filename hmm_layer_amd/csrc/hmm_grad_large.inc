@@ -381,6 +381,7 @@ extern "C" int hmm_loglik_grad_large(const float *A, const float *pi, const floa
     if (k < 1 || b < 1 || L < 1 || q < 1) return HMM_ERR_BAD_SHAPE;
     if (q > GL_MAX) return HMM_ERR_Q_UNSUPPORTED;
     if (!A || !pi || !E || !dA || !dpi || !dE || !workspace) return HMM_ERR_NULL_POINTER;
+    if (check_eps(eps)) return HMM_ERR_BAD_ARGUMENT;
     GlLayout g;
     gl_layout(k, b, L, q, &g);
     if (workspace_bytes < g.total || ((uintptr_t)workspace & 255)) return HMM_ERR_WORKSPACE;

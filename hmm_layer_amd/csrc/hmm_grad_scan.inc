@@ -94,6 +94,7 @@ int hmm_loglik_grad_scan(const float *A, const float *pi, const float *E, int k,
     int rc = make_gsplan(k, b, L, q, &pc);
     if (rc) return rc;
     if (!A || !pi || !E || !dA || !dpi || !dE || !workspace) return HMM_ERR_NULL_POINTER;
+    if ((rc = check_eps(eps))) return rc;
     if (workspace_bytes < pc.total || ((uintptr_t)workspace & 255)) return HMM_ERR_WORKSPACE;
     char *ws = (char *)workspace;
     hipStream_t st = (hipStream_t)stream;

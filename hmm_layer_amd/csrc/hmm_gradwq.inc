@@ -340,6 +340,7 @@ int hmm_loglik_grad_walk(const float *A, const float *pi, const float *E, int k,
     const int ngrad = (dA ? 1 : 0) + (dpi ? 1 : 0) + (dE ? 1 : 0);
     if (!A || !pi || !E || !workspace || (ngrad != 0 && ngrad != 3) || (ngrad == 0 && !loglik))
         return HMM_ERR_NULL_POINTER;
+    if ((rc = check_eps(eps))) return rc;
     if ((rc = check_ws(p.total, workspace, workspace_bytes))) return rc;
     hipStream_t st = (hipStream_t)stream;
     WqSp *sp = ws_at<WqSp>(workspace, p.o_sp);

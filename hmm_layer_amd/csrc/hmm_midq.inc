@@ -331,7 +331,8 @@ __device__ __forceinline__ void mq_forward_body(const float *__restrict__ A, con
             const float S = mq_wave_sum_fast(sf);
             inv = __builtin_amdgcn_rcpf(S);
             x = sf;
-            lacc += (double)__builtin_amdgcn_logf(S);       // log2 (S is a normal number: >= eps^2); scaled at the end
+            // log2, scaled at the end (S is a normal number: >= eps^2 with eps >= HMM_EPS_MIN)
+            lacc += (double)__builtin_amdgcn_logf(S);
             if (Sout && j == 0) Sout[(size_t)row * L + t] = S;
             if (act) {
                 const float xn = sf * inv;

@@ -424,6 +424,7 @@ int hmm_posterior_grad(const float *A, const float *pi, const float *E, int k, i
     if (q > MQ_MAX) return HMM_ERR_Q_UNSUPPORTED;
     if (mode != HMM_POST_PROB && mode != HMM_POST_LOG) return HMM_ERR_BAD_ARGUMENT;
     if (!A || !pi || !E || !grad_out || !dA || !dpi || !dE || !workspace) return HMM_ERR_NULL_POINTER;
+    if (check_eps(eps)) return HMM_ERR_BAD_ARGUMENT;
     char *ws = (char *)workspace;
     hipStream_t st = (hipStream_t)stream;
     if (q == 1) {

@@ -528,6 +528,7 @@ extern "C" int hmm_posterior_grad_large(const float *A, const float *pi, const f
     if (q > GL_MAX) return HMM_ERR_Q_UNSUPPORTED;
     if (mode != HMM_POST_PROB && mode != HMM_POST_LOG) return HMM_ERR_BAD_ARGUMENT;
     if (!A || !pi || !E || !grad_out || !dA || !dpi || !dE || !workspace) return HMM_ERR_NULL_POINTER;
+    if (check_eps(eps)) return HMM_ERR_BAD_ARGUMENT;
     PglLayout g;
     pgl_layout(k, b, L, q, &g);
     if (workspace_bytes < g.total || ((uintptr_t)workspace & 255)) return HMM_ERR_WORKSPACE;

@@ -87,6 +87,7 @@ int hmm_posterior_grad_scan(const float *A, const float *pi, const float *E, int
         return hmm_posterior_grad(A, pi, E, k, b, L, q, eps, mode, grad_out, dA, dpi, dE, workspace, workspace_bytes, stream);
     if (mode != HMM_POST_PROB && mode != HMM_POST_LOG) return HMM_ERR_BAD_ARGUMENT;
     if (!A || !pi || !E || !grad_out || !dA || !dpi || !dE || !workspace) return HMM_ERR_NULL_POINTER;
+    if (check_eps(eps)) return HMM_ERR_BAD_ARGUMENT;
     PcPlan pc;
     int rc = make_gsplan(k, b, L, q, &pc);
     if (rc) return rc;

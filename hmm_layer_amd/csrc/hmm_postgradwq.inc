@@ -480,6 +480,7 @@ int hmm_posterior_grad_walk(const float *A, const float *pi, const float *E, int
     if (rc) return rc;
     if (mode != HMM_POST_PROB && mode != HMM_POST_LOG) return HMM_ERR_BAD_ARGUMENT;
     if (!A || !pi || !E || !grad_out || !dA || !dpi || !dE || !workspace) return HMM_ERR_NULL_POINTER;
+    if ((rc = check_eps(eps))) return rc;
     if ((rc = check_ws(p.total, workspace, workspace_bytes))) return rc;
     hipStream_t st = (hipStream_t)stream;
     WqSp *sp = ws_at<WqSp>(workspace, p.o_sp);
@@ -521,7 +522,7 @@ int hmm_class_posterior_grad_walk(const float *A, const float *pi, const float *
     if (!A || !pi || !E || !state_class || !grad_out || !dA || !dpi || !dE || !workspace ||
         (mode == HMM_POST_LOG && !class_prob))
         return HMM_ERR_NULL_POINTER;
-    if (num_classes < 1 || num_classes > QP) return HMM_ERR_BAD_ARGUMENT;
+    if (num_classes < 1 || num_classes > QP || check_eps(eps)) return HMM_ERR_BAD_ARGUMENT;
     PgwClassG gs{};
     gs.ncls = num_classes;
     for (int s = 0; s < q; ++s) {                              // the table is read here, once, and travels by value

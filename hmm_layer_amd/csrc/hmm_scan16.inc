@@ -119,9 +119,11 @@ static dim3 apply_grid(const Plan &p) { return dim3((unsigned)((apply_waves(p) +
 static dim3 win_grid(const Plan &p) { return dim3((unsigned)((p.NB < 4096 ? p.NB : 4096) + 3) / 4); }
 
 // the verdict per sequence from the certificate sums phi: flags, the window table and the counters
-static void s16_select(const Plan &p, const Ws16 &w, const Routing &rt, hipStream_t st) {
+// handover: the posterior's scan plan (k_backward has left rstart) — the clamp between two chunks is weighed as well
+static void s16_select(const Plan &p, const Ws16 &w, const Routing &rt, hipStream_t st, bool handover = false,
+                       float eps = 0.f) {
     launch(k_exact_select, dim3(p.NB), dim3(64), 0, st, rt.topo, w.phi, p, rt.exact_mode, win_margin(p), w.flags,
-           w.nexact, w.wtab, w.wlist, w.wcnt, w.exps);
+           w.nexact, w.wtab, w.wlist, w.wcnt, w.exps, handover ? w.prefix : nullptr, handover ? w.rstart : nullptr, eps);
 }
 
 // ---- batch groups for the posterior pipeline.  The sparse reduce kernel is VALU-bound and the
@@ -194,6 +196,10 @@ static int check_ws(size_t total, void *ws, size_t bytes) {
     if (bytes < total || ((uintptr_t)ws & 255)) return HMM_ERR_WORKSPACE;
     return HMM_OK;
 }
+
+// The clamp eps every entry point serves (include/hmm_engine.h, "The clamp eps"): the one check they all share.
+// The comparisons are false for NaN.
+static int check_eps(float eps) { return eps >= HMM_EPS_MIN && eps <= HMM_EPS_MAX ? HMM_OK : HMM_ERR_BAD_ARGUMENT; }
 
 // ---- the drivers
 
@@ -303,7 +309,7 @@ static int s16_apply(const float *A, const float *pi, const float *E, const Plan
     }
     if (allow_exact && dec) {
         Timed t(pr, HMM_KERNEL_EXACT, st);
-        s16_select(p, w, rt, st);
+        s16_select(p, w, rt, st, true, eps);
         launch(k_window_decode<DEC>, win_grid(p), dim3(256), 0, st, A, E, w.prefix, w.llpre, w.suffix, w.xend, w.rstart, w.ckpt,
                w.loglik, w.wtab, w.wlist, w.wcnt, w.flags, w.dfix, p, eps, win_margin(p), *dec);
         launch(k_exact_decode<DEC>, apply_grid(px), dim3(256), 0, st, A, pi, E, w.ckpt, w.loglik, routing_flagged(rt, w), px, eps,
@@ -312,7 +318,7 @@ static int s16_apply(const float *A, const float *pi, const float *E, const Plan
         // the serial kernels: per model as k_topo_check decided, per sequence from the clamp-born mass the
         // backward kernel just summed; their waves exit at once when nothing is routed
         Timed t(pr, HMM_KERNEL_EXACT, st);
-        s16_select(p, w, rt, st);
+        s16_select(p, w, rt, st, true, eps);
         launch(mode == HMM_POST_PROB ? k_window_posterior<0>
                : mode == HMM_POST_LOG ? k_window_posterior<1> : k_window_posterior<2>,
                win_grid(p), dim3(256), 0, st, A, E, w.prefix, w.llpre, w.suffix, w.xend, w.rstart, w.ckpt, w.loglik, out,

@@ -1045,6 +1045,22 @@ __global__ __launch_bounds__(256) void backward(const float *__restrict__ A, con
             else flush<NT>(os, lane, j * BLK, (top < GB ? top : GB) * BLK);
         }
     }
+    if (MODE != 3) {
+        // The handover.  Rv is now R at the last position of the chunk before, with the flags of the clamp that made it;
+        // the gamma that weighs them belongs to that chunk, whose kernel starts from the chunk scan's suffix vector: the
+        // same direction without the clamp.  It is weighed here, with alpha_hat at that position (the vector entering
+        // this chunk: block 0's checkpoint), and charged to this chunk (k_exact_select in hmm_engine.hip does the same
+        // for up to 16 states).
+        const bool hand = tl.valid && !tl.first;
+        XT<NT> gm;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const f4 x0 = hand ? *reinterpret_cast<const f4 *>(ck + 16 * t) : zero4;
+            gm.t[t] = abs4(x0) * Rv.t[t];
+        }
+        const float ig = __builtin_amdgcn_rcpf(sum_abs<NT>(gm));
+        phiacc = fmaf(lane_sum_neg<NT>(gm), hand ? ig : 0.f, phiacc);
+    }
     phiacc = col_sum(phiacc);
     if (MODE != 3 && g == 0 && tl.valid) phi[tl.chain] = phiacc;
     if (CERT3) {

@@ -100,6 +100,7 @@ int hmm_seqshard_reduce(const float *A, const float *E, int k, int b, int Ls, in
     int rc = make_ssplan(k, b, Ls, q, R, &sp);
     if (rc) return rc;
     if (!A || !E || !slab_op || !slab_exp || !workspace) return HMM_ERR_NULL_POINTER;
+    if (check_eps(eps)) return HMM_ERR_BAD_ARGUMENT;
     if (workspace_bytes < sp.total || ((uintptr_t)workspace & 255)) return HMM_ERR_WORKSPACE;
     Plan p = sp.p;
     p.seq_start = seq_start ? 1 : 0;
@@ -140,6 +141,7 @@ int hmm_seqshard_posterior(const float *A, const float *pi, const float *E, int 
     if (r < 0 || r >= R || (seq_start != 0) != (r == 0)) return HMM_ERR_BAD_ARGUMENT;
     if (mode < HMM_POST_PROB || mode > HMM_POST_LOG_NO_LL) return HMM_ERR_BAD_ARGUMENT;
     if (!A || !pi || !E || !all_ops || !all_exps || !out || !workspace) return HMM_ERR_NULL_POINTER;
+    if (check_eps(eps)) return HMM_ERR_BAD_ARGUMENT;
     if (workspace_bytes < sp.total || ((uintptr_t)workspace & 255)) return HMM_ERR_WORKSPACE;
     Plan p = sp.p;
     p.seq_start = seq_start ? 1 : 0;

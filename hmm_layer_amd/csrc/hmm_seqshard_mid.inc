@@ -150,6 +150,7 @@ int hmm_seqshard_mid_reduce(const float *A, const float *E, int k, int b, int Ls
     const int rc = make_ssmidplan(k, b, Ls, q, R, &sp);
     if (rc) return rc;
     if (!A || !E || !slab_op || !slab_exp || !workspace) return HMM_ERR_NULL_POINTER;
+    if (check_eps(eps)) return HMM_ERR_BAD_ARGUMENT;
     if (workspace_bytes < sp.total || ((uintptr_t)workspace & 255)) return HMM_ERR_WORKSPACE;
     sp.mp.p.seq_start = seq_start ? 1 : 0;
     if (sp.W == Q32) ssm_reduce<Scan32>(A, E, sp, eps, (char *)workspace, slab_op, slab_exp, (hipStream_t)stream);
@@ -167,6 +168,7 @@ int hmm_seqshard_mid_posterior(const float *A, const float *pi, const float *E, 
     if (r < 0 || r >= R || (seq_start != 0) != (r == 0)) return HMM_ERR_BAD_ARGUMENT;
     if (mode < HMM_POST_PROB || mode > HMM_POST_LOG_NO_LL) return HMM_ERR_BAD_ARGUMENT;
     if (!A || !pi || !E || !all_ops || !all_exps || !out || !workspace) return HMM_ERR_NULL_POINTER;
+    if (check_eps(eps)) return HMM_ERR_BAD_ARGUMENT;
     if (workspace_bytes < sp.total || ((uintptr_t)workspace & 255)) return HMM_ERR_WORKSPACE;
     sp.mp.p.seq_start = seq_start ? 1 : 0;
     if (sp.W == Q32)

@@ -480,7 +480,7 @@ int hmm_posterior_walk(const float *A, const float *pi, const float *E, int k, i
     int rc = make_wqplan(k, b, L, q, &p);
     if (rc) return rc;
     if (!A || !pi || !E || !out || !workspace) return HMM_ERR_NULL_POINTER;
-    if (mode < HMM_POST_PROB || mode > HMM_POST_LOG_NO_LL) return HMM_ERR_BAD_ARGUMENT;
+    if (mode < HMM_POST_PROB || mode > HMM_POST_LOG_NO_LL || check_eps(eps)) return HMM_ERR_BAD_ARGUMENT;
     if ((rc = check_ws(p.total, workspace, workspace_bytes))) return rc;
     hipStream_t st = (hipStream_t)stream;
     wq_walk(A, pi, E, k, b, L, q, eps, mode, out, p, (char *)workspace, nullptr, st);
@@ -501,7 +501,7 @@ int hmm_posterior_decode_wide(const float *A, const float *pi, const float *E, i
     int rc = make_wqplan(k, b, L, q, &p);
     if (rc) return rc;
     if (!A || !pi || !E || !label || !workspace) return HMM_ERR_NULL_POINTER;
-    if (num_classes < 1 || (state_class ? num_classes > QP : num_classes != q)) return HMM_ERR_BAD_ARGUMENT;
+    if (num_classes < 1 || (state_class ? num_classes > QP : num_classes != q) || check_eps(eps)) return HMM_ERR_BAD_ARGUMENT;
     DecodeWide dec{};
     dec.label = label; dec.conf = conf; dec.ncls = state_class ? num_classes : 0;
     for (int s = 0; s < q && state_class; ++s) {               // the table is read here, once, and travels by value
@@ -543,7 +543,7 @@ int hmm_class_posterior_walk(const float *A, const float *pi, const float *E, in
     int rc = make_wqplan(k, b, L, q, &p);
     if (rc) return rc;
     if (!A || !pi || !E || !state_class || !workspace || (!out_prob && !out_log)) return HMM_ERR_NULL_POINTER;
-    if (num_classes < 1 || num_classes > QP) return HMM_ERR_BAD_ARGUMENT;
+    if (num_classes < 1 || num_classes > QP || check_eps(eps)) return HMM_ERR_BAD_ARGUMENT;
     ClassWide cls{};
     cls.prob = out_prob; cls.logp = out_log; cls.ncls = num_classes;
     for (int s = 0; s < q; ++s) {                              // the table is read here, once, and travels by value

@@ -72,6 +72,21 @@ extern "C" {
 #define HMM_ERR_NO_DEVICE     -7
 #define HMM_ERR_NO_RCCL       -8   /* hmm_loglik_allreduce: the process has no RCCL loaded */
 
+/* The clamp eps.  Every entry point that takes `eps` serves HMM_EPS_MIN <= eps <= HMM_EPS_MAX and refuses anything
+ * else — smaller, larger, zero, negative, NaN, infinite — with HMM_ERR_BAD_ARGUMENT, after the null-pointer checks and
+ * before the workspace checks.  The lower end is where the kernels' arithmetic stops: a step's normaliser
+ * S = sum_j max(E_j, eps) max(R_j, eps) can be as small as q eps^2 (a row of zero emissions on a floored state), the
+ * kernels take its reciprocal and logarithm in fp32 with denormals flushed, so eps^2 has to be a normal number
+ * (eps >= 2^-63 = 1.08e-19); 1e-18 leaves a factor of 85 above that, and tests/test_eps_sweep_gpu.py holds every
+ * output of the 1..64-state kernels to the fp64 oracle there.  The upper end is the largest value that sweep holds them
+ * to the oracle at; nothing is known to break above it, it is simply where the evidence ends, and a clamp that carries
+ * more than a thousandth of every step's mass is not a rounding guard any more.  The domain is one for the whole
+ * library: the entry points for more than 64 states, the per-sequence walks, the class posteriors and the
+ * sequence-sharded calls check it too.  All of them accepted any float before (0, negative and NaN included) — this
+ * is a deliberate narrowing of the ABI.  The reference's default is 1e-16 (hmm_layer/MsaHmmCell.py:33). */
+#define HMM_EPS_MIN 1e-18f
+#define HMM_EPS_MAX 1e-3f
+
 /* operations, for hmm_workspace_bytes() */
 #define HMM_OP_LOGLIK     0   /* hmm_forward without log_alpha */
 #define HMM_OP_FORWARD    1   /* hmm_forward with log_alpha      */

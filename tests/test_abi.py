@@ -65,6 +65,23 @@ def test_null_and_shape_errors_without_device(lib):
     assert lib.hmm_posterior(None, None, None, 1, 1, 16, 5000, 1e-16, 0, None, None, None, 0, None) == -2
 
 
+@pytest.mark.parametrize("q", [15, 29, 48, 100])
+def test_eps_outside_the_domain_is_refused(lib, q):
+    # HMM_EPS_MIN = 1e-18 <= eps <= HMM_EPS_MAX = 1e-3 (include/hmm_engine.h): after the null pointers and the mode,
+    # before the workspace; zero, negative and non-finite values are always outside.  Every other entry point that
+    # takes eps: tests/test_eps_sweep_cpu.py::test_every_entry_point_refuses_eps_outside_the_domain
+    p = 0x10000                                                                 # never dereferenced
+    for eps in (0.0, -1e-16, float("nan"), float("inf"), 1e-20, 1e-30, 9.9e-19, 1.1e-3, 1.0):
+        assert lib.hmm_forward(p, p, p, 1, 2, 300, q, eps, p, p, p + 1, 1 << 40, None) == -6
+        assert lib.hmm_backward(p, p, 1, 2, 300, q, eps, p, p + 1, 1 << 40, None) == -6
+        assert lib.hmm_posterior(p, p, p, 1, 2, 300, q, eps, 0, p, None, p + 1, 1 << 40, None) == -6
+        assert lib.hmm_posterior(None, p, p, 1, 2, 300, q, eps, 0, p, None, p + 1, 1 << 40, None) == -3
+    for eps in (1e-18, 1e-16, 1e-6, 1e-3):                                      # served: on to the workspace check
+        assert lib.hmm_forward(p, p, p, 1, 2, 300, q, eps, p, p, p + 1, 1 << 40, None) == -4
+        assert lib.hmm_backward(p, p, 1, 2, 300, q, eps, p, p + 1, 1 << 40, None) == -4
+        assert lib.hmm_posterior(p, p, p, 1, 2, 300, q, eps, 0, p, None, p + 1, 1 << 40, None) == -4
+
+
 def test_host_wrapper_rejects_cpu_tensors(lib):
     A = torch.eye(3).unsqueeze(0)
     pi = torch.ones(3) / 3
