@@ -482,6 +482,16 @@ int hmm_viterbi_scan(const float *logA, const float *logpi, const float *logE,
  *   E           (b,L,q)    emission probabilities, the engine's input.  16-byte aligned (so is dx of
  *                          hmm_gene_emissions_grad and _grad_wide): tiles of 16 positions are stored as aligned
  *                          16-byte pieces.
+ * Limits: 1 <= q <= 64, 1 <= rows <= 32, 1 <= s <= 32, 0 <= nc <= 16 (hmm_gene_emissions_wide: 256 states and rows).
+ * Table entries out of range never index out of a table.  For this function and hmm_gene_emissions_wide the values
+ * below are pinned by tests (tests/test_emitter_sweep_gpu.py); the two backwards read state_row and state_codon
+ * through the same two clamps (em_row, em_codon), so the same holds for them by construction:
+ *   state_row[j] < 0 reads row 0 of B, state_row[j] >= rows reads row rows - 1;
+ *   state_codon[j] < 0 (any negative value, not only -1) makes state j free;
+ *   state_codon[j] >= nc reads table row nc - 1;
+ *   nc = 0 makes every state free whatever state_codon holds, and codon may then be NULL.
+ * The nucleotide columns need not be one-hot: a slot's distribution is its four base columns, plus 1/4 each (n_mass/4
+ * in right 3-mers) where the N column is exactly 1; any other value of the N column counts for nothing.
  */
 int hmm_gene_emissions(const float *x, int b, int L, int s, const float *B, int rows,
                        const int *state_row, const float *codon, int nc, const int *state_codon, int q,
@@ -590,7 +600,7 @@ int hmm_gene_emissions_grad(const float *x, int b, int L, int s, const float *B,
  * columns of dx and "dB written whole" are exactly those of the two functions above; so are the values (the forward
  * runs the same class-sum chain: where both apply, the results are bit-identical).
  * Limits: 1 <= q <= hmm_gene_emissions_wide_max_states() (256), 1 <= rows <= 256, s <= 32, nc <= 16.  Entries of
- * state_row outside 0..rows-1 are clamped (they never index out of B); entries of state_codon above nc-1 likewise.
+ * state_row and state_codon out of range, and nc = 0, mean what they mean for hmm_gene_emissions (above).
  * Checked before any HIP call, in this order: shape (HMM_ERR_BAD_SHAPE), limits (HMM_ERR_Q_UNSUPPORTED), pointers
  * (HMM_ERR_NULL_POINTER; for the grad: any input, the workspace, or both outputs NULL), workspace
  * (HMM_ERR_WORKSPACE: fewer than hmm_gene_emissions_grad_wide_workspace_bytes bytes, or not 256-byte aligned).
